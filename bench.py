@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — the SpGEMM hot path on MI355X, measured per the driver contract.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the line used to carry: the untimed per-kernel profiling pass and the roofline, the parity
+gate against the CPU oracle, the CPU baseline, the host-array entry point and (default workload, N=1) the short runs of
+the other workloads.  --dump-outputs DIR writes what the last timed step computed as .npy files (see dump_outputs).
 
 N > 1 without a launcher (WORLD_SIZE unset): this process starts the N ranks itself as a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ...` BEFORE it touches the GPU, waits, and relays
@@ -147,6 +152,46 @@ def traffic_for(workload, kernel, path=None):
                         f"{os.path.relpath(tj, ROOT)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, collected "
                         "separately (not in this run) on the same kernel sources (device_code_sha256 checked)")
     return None, stale
+
+
+DUMP_SEED = 20240601         # the fixed row sample of --dump-outputs
+DUMP_SAMPLE_ROWS = 4096
+DUMP_SAMPLE_NNZ = 2_000_000  # bound on the sampled entries: 24 MB, the whole dump stays below 64 MB at m <= 2 M
+
+
+def dump_outputs(out_dir, rowPtr, colInd, values):
+    """--dump-outputs: the CSR result C = (rowPtr, colInd, values) of the last timed step, as .npy files in DIR.  C itself
+    is ~1.8 GB at the headline size, so the files hold
+        row_nnz.npy         float64[m]  entries of every row (the structure's row lengths, exact)
+        row_value_sum.npy   float64[m]  sum of every row's values, accumulated in float64
+        sample_rows.npy     float64[k]  a fixed seeded sample of rows (DUMP_SEED; taken in sampled order while the
+                                        entries stay within DUMP_SAMPLE_NNZ, then sorted)
+        sample_rowPtr.npy   float64[k+1] offsets of the sampled rows inside the two arrays below
+        sample_colInd.npy   float64     their columns, sorted inside each row (the order of a row's entries is not part
+                                        of the result)
+        sample_values.npy   float32     their values, in the same order"""
+    os.makedirs(out_dir, exist_ok=True)
+    rp = np.asarray(rowPtr, dtype=np.int64)
+    m = len(rp) - 1
+    lens = np.diff(rp)
+    sums = np.zeros(m, dtype=np.float64)
+    live = lens > 0
+    if live.any():
+        sums[live] = np.add.reduceat(np.asarray(values), rp[:-1][live], dtype=np.float64)
+    rng = np.random.default_rng(DUMP_SEED)
+    cand = rng.permutation(m)[:DUMP_SAMPLE_ROWS]
+    rows = np.sort(cand[np.cumsum(lens[cand]) <= DUMP_SAMPLE_NNZ])
+    idx = np.concatenate([np.arange(rp[r], rp[r + 1]) for r in rows]) if len(rows) else np.zeros(0, dtype=np.int64)
+    owner = np.repeat(np.arange(len(rows)), lens[rows])
+    cols = np.asarray(colInd)[idx]
+    order = np.lexsort((cols, owner))
+    srp = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum(lens[rows], out=srp[1:])
+    out = {"row_nnz": lens.astype(np.float64), "row_value_sum": sums, "sample_rows": rows.astype(np.float64),
+           "sample_rowPtr": srp.astype(np.float64), "sample_colInd": cols[order].astype(np.float64),
+           "sample_values": np.asarray(values)[idx][order].astype(np.float32)}
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def self_launch(args):
@@ -390,18 +435,20 @@ def bench_spgemm(ctx, args, wl):
         runner.step(gather)
     P = runner.P
 
-    # ---- untimed profiling pass: every kernel bracketed by HIP events -> per-kernel averages, dominant kernel
-    set_timing(ALL_KERNELS)
-    prof_ms, nprof = {}, 3
-    for _ in range(nprof):
-        runner.step(gather)
-        for hnd in runner.handles:
-            for kname, ms in hnd.stats()["ms_kernel"].items():
-                prof_ms[kname] = prof_ms.get(kname, 0.0) + ms
-    prof_avg = {k_: v_ / nprof for k_, v_ in prof_ms.items()}
-    cand = {k_: v_ for k_, v_ in prof_avg.items() if k_ in KERNEL_BINS}
-    dom = max(cand, key=cand.get) if cand else None
-    dom_id = next((i for i in range(hs.NKERNELS) if hs.kernel_name(i) == dom), None) if dom else None
+    prof_avg, dom, dom_id, nprof = {}, None, None, 3
+    if args.full:
+        # ---- untimed profiling pass: every kernel bracketed by HIP events -> per-kernel averages, dominant kernel
+        set_timing(ALL_KERNELS)
+        prof_ms = {}
+        for _ in range(nprof):
+            runner.step(gather)
+            for hnd in runner.handles:
+                for kname, ms in hnd.stats()["ms_kernel"].items():
+                    prof_ms[kname] = prof_ms.get(kname, 0.0) + ms
+        prof_avg = {k_: v_ / nprof for k_, v_ in prof_ms.items()}
+        cand = {k_: v_ for k_, v_ in prof_avg.items() if k_ in KERNEL_BINS}
+        dom = max(cand, key=cand.get) if cand else None
+        dom_id = next((i for i in range(hs.NKERNELS) if hs.kernel_name(i) == dom), None) if dom else None
     set_timing(ALL_KERNELS if args.time_all_kernels else ((1 << dom_id) if dom_id is not None else 0))
 
     # ---- timed region
@@ -451,9 +498,12 @@ def bench_spgemm(ctx, args, wl):
         "pipeline_frac_of_hbm_peak": round(bytes_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS / world, 4),
     }
 
-    if rank == 0:
-        # ---- C of the last step on the host (parity gate; per-bin counts for the roofline)
+    if rank == 0 and (args.full or args.dump_outputs):
+        # ---- C of the last step on the host (--dump-outputs; parity gate and per-bin counts for the roofline)
         rpc, jc_h, cv_h = runner.result_host()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rpc, jc_h, cv_h)
+    if rank == 0 and args.full:
         rpc = rpc.astype(np.int64)
         r0, r1 = runner.local_rows()
         flops_rows, rpl = runner.local_row_flops()
@@ -542,6 +592,7 @@ def bench_spgemm(ctx, args, wl):
             if not ok:
                 emit(json.dumps(result))
                 raise SystemExit("parity gate failed")
+    if rank == 0:
         result["setup"] = {"generate_s": round(gen_s, 2), "host_cpus": os.cpu_count()}
     runner.release()
     return result if rank == 0 else None
@@ -587,7 +638,10 @@ def bench_rmcl(ctx, args, wl):
         # reference-made summary (threshold ties move a few entries), rows sum to 1, and one sampled iteration step by step
         # against the oracle (tests/helpers.assert_rmcl_step: equal rows, or rows that differ only in proven threshold ties)
         ok, why = True, ""
-        if not args.no_verify:
+        if rank == 0 and args.dump_outputs:
+            final = job.result(0)
+            dump_outputs(args.dump_outputs, final.rowPtr, final.colInd, final.values)
+        if args.full and not args.no_verify:
             final = job.result(0)
             rs = np.add.reduceat(final.values.astype(np.float64), final.rowPtr[:-1][np.diff(final.rowPtr) > 0])
             ok = bool(np.allclose(rs, 1.0, atol=1e-5)) and int(final.nnz) == final_nnz
@@ -630,7 +684,8 @@ def bench_rmcl(ctx, args, wl):
                 "GFLOPs": (round(2.0 * Ptot / (ms * 1e-3) / 1e9, 3) if Ptot else None),
                 "per_iteration_nnz": per_iter_nnz, "final_nnz": int(final_nnz),
                 "golden_final_nnz": (gold["per_iter"][iters - 1]["nnz"] if gold else None),
-                "parity": ("ok (nnz after every iteration within the threshold-tie drift of the reference summary; rows sum to 1; "
+                "parity": (None if not args.full else
+                           "ok (nnz after every iteration within the threshold-tie drift of the reference summary; rows sum to 1; "
                            "one iteration checked step by step against the oracle)" if ok_all else f"FAILED: {why}"),
                 "roofline": None, "cpu_baseline": None}
         job.close()
@@ -683,20 +738,24 @@ def bench_rmcl(ctx, args, wl):
     elapsed = time.perf_counter() - t0
     ms_per_step = elapsed * 1e3 / args.steps
     # beside it: the same loop as one hip_rmcl_expand_prune call per iteration (Mt packed every time), for the record
-    nside = min(args.steps, 5)
-    copies = [H.toGpuCSR() for _ in range(nside)]         # synchronous uploads
-    t1 = time.perf_counter()
-    for c_ in copies:
-        fin, _ = loop(c_, False)
-        fin.deviceDispose()
-    per_call_ms = (time.perf_counter() - t1) * 1e3 / nside
-    final = last.toCpuCSR()
+    per_call_ms = None
+    if args.full:
+        nside = min(args.steps, 5)
+        copies = [H.toGpuCSR() for _ in range(nside)]         # synchronous uploads
+        t1 = time.perf_counter()
+        for c_ in copies:
+            fin, _ = loop(c_, False)
+            fin.deviceDispose()
+        per_call_ms = (time.perf_counter() - t1) * 1e3 / nside
+    final = last.toCpuCSR() if (args.full or args.dump_outputs) else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final.rowPtr, final.colInd, final.values)
     last.deviceDispose()
     start.deviceDispose()
     G_.deviceDispose()
     # the call the reference's driver makes: host CSRs in, host CSR out (upload + the loop above + download), never `value`
     host_api = None
-    if not args.no_host_api:
+    if args.full and not args.no_host_api:
         hs.gpuRmclIter(iters, H, H)
         t2 = time.perf_counter()
         nh = 3
@@ -723,7 +782,7 @@ def bench_rmcl(ctx, args, wl):
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": wl["desc"], "name": wl["name"], "m": m, "nnz_Mt0": nnzA, "iterations": iters,
                    "products_per_step": P_total, "parallelism": "single GPU"},
-        "loop_one_call_per_iteration_ms": round(per_call_ms, 3),
+        "loop_one_call_per_iteration_ms": (round(per_call_ms, 3) if per_call_ms is not None else None),
         "host_api": host_api,
         "per_iteration": [{"P": p_["P"], "nnz_in": p_["nnz_in"], "kept": p_["kept"], "ms": round(p_["ms"], 3),
                            "alg_GBs": round(b_ / (p_["ms"] * 1e-3) / 1e9, 1)} for p_, b_ in zip(per, it_bytes)],
@@ -738,7 +797,7 @@ def bench_rmcl(ctx, args, wl):
                      "alg_bytes": "8(m+1) + 16 nnz(Mgt) + 8 P + 8 kept: the product is never written, only what survives the prune",
                      "loop_kernels_ms": {k_: round(v_, 3) for k_, v_ in sorted(kern_tot.items(), key=lambda kv: -kv[1])}},
     }
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         rs = np.add.reduceat(final.values.astype(np.float64), final.rowPtr[:-1][np.diff(final.rowPtr) > 0])
         ok = bool(np.allclose(rs, 1.0, atol=1e-5))
         if gold and iters <= len(gold["per_iter"]):                        # reference-made per-iteration summary
@@ -751,7 +810,7 @@ def bench_rmcl(ctx, args, wl):
         if not ok:
             emit(json.dumps(result))
             raise SystemExit("parity gate failed")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         if po.have_ref():                                                  # the reference's own multi-threaded loop, 2 iterations
             sample_it = min(2, iters)
             _, dt = po.ref_mt_rmcl(Mt, Mt, sample_it, opt=1)
@@ -798,7 +857,14 @@ def main():
                          "than ranks (ranks share devices; transport over host memory; not a performance number)")
     ap.add_argument("--time-all-kernels", action="store_true",
                     help="keep the HIP events of every kernel inside the timed region (diagnostic; costs ~3 %% of a step)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: profiling pass + roofline, parity gate, CPU baseline, host-array "
+                         "entry point, other workloads (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1 and args.no_gather:
+        raise SystemExit("--dump-outputs needs the gathered C: drop --no-gather")
     os.environ.setdefault("OMP_NUM_THREADS", str(os.cpu_count() or 1))   # cpu_baseline: all host threads
     protect_stdout()
     ctx = Ctx(args)
@@ -808,7 +874,7 @@ def main():
         return bench_rmcl(ctx, a, wl) if wl.get("gen") == "rmcl" else bench_spgemm(ctx, a, wl)
 
     result = run(args.workload, args)
-    if args.workload == "synth_1m_16" and ctx.world == 1 and not args.no_other_workloads and result is not None:
+    if args.full and args.workload == "synth_1m_16" and ctx.world == 1 and not args.no_other_workloads and result is not None:
         # The driver times ONE line: the other BASELINE configs ride on it as short runs (5 steps each, parity gate on, no
         # cpu baseline / host-api timing), so that their numbers are the driver's measurements too and not builder claims.
         # `value` stays the headline's.  (configs[3] = 1M/32 sharded over 2-8 GPUs is the N>1 run of this same script.)
@@ -816,7 +882,7 @@ def main():
         others = {}
         for name in ("synth_256k_16", "web_google_surrogate", "rmcl_500k"):
             a = copy.copy(args)
-            a.steps, a.warmup, a.no_cpu_baseline, a.no_host_api = 5, 2, True, True
+            a.steps, a.warmup, a.no_cpu_baseline, a.no_host_api, a.dump_outputs = 5, 2, True, True, None
             t0 = time.time()
             r = run(name, a)
             roof = r.get("roofline") or {}

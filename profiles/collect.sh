@@ -4,7 +4,7 @@
 # fit one pass on gfx950).  PMC passes use --kernel-trace only (never sys/hip/hsa trace together with --pmc).
 TAG=${1:-r04}; WL=${2:-synth_1m_16}
 OUT=$PWD/gpurun_out/prof_${TAG}_${WL}; rm -rf $OUT; mkdir -p $OUT
-ARGS="$PWD/bench.py --workload $WL --steps 5 --warmup 2 --no-verify --no-cpu-baseline --no-host-api --no-other-workloads"
+ARGS="$PWD/bench.py --workload $WL --steps 5 --warmup 2 --full --no-verify --no-cpu-baseline --no-host-api --no-other-workloads"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1; echo "trace exit=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $ARGS > $OUT/fetch.log 2>&1; echo "fetch exit=$?"

@@ -11,7 +11,7 @@ case "$mode" in
   tests)
     timeout -k 10 1100 python -m pytest ${@:-tests -m gpu -x -q} 2>&1 | tail -25 ;;
   bench)
-    wl="$1"; shift
+    wl="$1"; shift; set -- --full "$@"          # the summary reads the roofline (phases, kernels)
     timeout -k 10 500 python bench.py --workload "$wl" "$@" > gpurun_out/bench_$wl.json 2> gpurun_out/bench_$wl.err || { tail -5 gpurun_out/bench_$wl.err; exit 1; }
     python tools/bench_summary.py gpurun_out/bench_$wl.json ;;
   ab)
@@ -22,7 +22,7 @@ case "$mode" in
       for rep in $(seq 1 $REPS); do
         for arm in A B; do
           if [ $arm = A ]; then envs="$A"; else envs="$B"; fi
-          env $envs timeout -k 10 300 python bench.py --workload $wl --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-host-api \
+          env $envs timeout -k 10 300 python bench.py --workload $wl --steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --no-host-api \
             > gpurun_out/ab_${wl}_${arm}_$rep.json 2> gpurun_out/ab_${wl}_${arm}_$rep.err || { echo "$wl $arm $rep failed"; tail -3 gpurun_out/ab_${wl}_${arm}_$rep.err; exit 1; }
         done
       done

@@ -2,7 +2,7 @@
 # memory-side counters for the 1M workload (separate --pmc passes, kernel-trace only)
 WL=${1:-synth_1m_16}
 OUT=$PWD/gpurun_out/pmc_mem; rm -rf $OUT; mkdir -p $OUT
-ARGS="$PWD/bench.py --workload $WL --steps 2 --warmup 1 --no-verify --no-cpu-baseline"
+ARGS="$PWD/bench.py --workload $WL --steps 2 --warmup 1 --full --no-verify --no-cpu-baseline"
 cd /tmp && export TMPDIR=/tmp
 i=0
 for SET in "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum TCP_TCC_READ_REQ_sum" \
