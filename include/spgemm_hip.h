@@ -8,6 +8,8 @@
  * exit-on-error convention (nlibs/gpus/cuda_handle_error.h:7-15).
  *
  * Each declaration cites the reference interface it replaces (paths relative to the reference tree).
+ * The reference's other value type (QValue double, FDOUBLE, nlibs/tools/macro.h:3-6) has the *_f64 twins of the SpGEMM
+ * entry points and the row sort, section (5) below.
  * Thread model: one caller thread per handle; calls return after the device work has completed
  * (the reference's GPU path is blocking too: nlibs/gpus/gpu_csr_kernel.cu:162).
  */
@@ -344,6 +346,36 @@ int hip_resultsComparison(int m, int n, const int* hIC, const int* hJC, const fl
 /* ---- helpers the reference's drivers use around the path --------------------------------------- */
 /* CSR::makeOrdered on device arrays (nlibs/CSR.cc:73-86): sort every row by column, in place. */
 int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, float* dC);
+
+/* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
+ * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
+ * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,
+ * symbolic pass and scan are shared with the float path (they read the structure only), so C's structure is the float
+ * call's; the numeric kernels accumulate in double.  spgemm_stats is filled as for a float call: f64 numeric launches are
+ * timed into the SPGEMM_K_NUM_* slot of their bin (SPGEMM_NKERNELS and the struct layout are unchanged).
+ * Not available in double: R-MCL (hip_rmcl_*, hip_gpuRmclIter*), multi-GPU, hip_sgpuSpMM / hip_gpuFlopsClassify,
+ * COO -> CSR, mixed precision (float in, double accumulate).
+ * Measured on one MI355X: a double call takes 2.0x the float call on the 1 M-row power-law A*A,
+ * 1.45x on the web-graph surrogate. */
+/* CSR gpuSpMMWrapper for QValue double: cusparseDcsrgemm (nlibs/gpus/cusparse_spmm.cc:73).  Never takes the opt-in
+ * SPGEMM_PATH kernels. */
+int hip_gpuSpMM_f64(spgemm_handle* h,
+                    const int* dIA, const int* dJA, const double* dA, int nnzA,
+                    const int* dIB, const int* dJB, const double* dB, int nnzB,
+                    int m, int k, int n, int** dIC, int** dJC, double** dC, int* nnzC);
+/* numeric phase in double after hip_spgemm_symbolic on the same handle (one symbolic phase may be followed by either
+ * hip_spgemm_numeric or this); without a matching symbolic phase: SPGEMM_ERR_ARG */
+int hip_spgemm_numeric_f64(spgemm_handle* h,
+                           const int* dIA, const int* dJA, const double* dA, int nnzA,
+                           const int* dIB, const int* dJB, const double* dB, int nnzB,
+                           int m, int k, int n, const int* dIC, int* dJC, double* dC);
+/* host arrays in, malloc()ed host arrays out: the *_CSR_SpMM family with QValue double, mkl_dcsrmultcsr
+ * (nlibs/mkls/mkl_csr_kernel.cc:12,36); fills spgemm_hip_host_api_stats like hip_CSR_SpMM */
+int hip_CSR_SpMM_f64(const int* IA, const int* JA, const double* A, int nnzA,
+                     const int* IB, const int* JB, const double* B, int nnzB,
+                     int** IC, int** JC, double** C, int* nnzC, int m, int k, int n);
+/* CSR::makeOrdered with double values (nlibs/CSR.cc:73-86) */
+int hip_csr_sort_rows_f64(spgemm_handle* h, int m, const int* dIC, int* dJC, double* dC);
 
 /* device self-test of the wave/block primitives (scans, ballots); returns SPGEMM_OK or INTERNAL */
 int spgemm_hip_selftest(spgemm_handle* h);

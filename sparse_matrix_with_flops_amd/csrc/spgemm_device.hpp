@@ -2048,10 +2048,11 @@ __global__ void k_gather_flops(int m, const int* __restrict__ rowIds, const int*
 // primitives for this are nlibs/bitonic_sort.cuh:19-87 and mindex2-cuda/radix_sort.cuh:2-62.
 // Used by tests/drivers, not by the timed path.
 constexpr int SORT_MAX = 4096;
+template <class V>      // value type: float, or double for hip_csr_sort_rows_f64
 __global__ __launch_bounds__(256) void k_sort_rows(int m, const int* __restrict__ IC, int* __restrict__ JC,
-                                                    float* __restrict__ C, int* __restrict__ longUnsorted) {
+                                                    V* __restrict__ C, int* __restrict__ longUnsorted) {
   __shared__ int sk[SORT_MAX];
-  __shared__ float sv[SORT_MAX];
+  __shared__ V sv[SORT_MAX];
   __shared__ int unsorted;
   const int tid = threadIdx.x;
   for (int row = blockIdx.x; row < m; row += gridDim.x) {
@@ -2060,7 +2061,7 @@ __global__ __launch_bounds__(256) void k_sort_rows(int m, const int* __restrict_
     if (len <= SORT_MAX) {
       int p2 = 1;
       while (p2 < len) p2 <<= 1;
-      for (int i = tid; i < p2; i += 256) { sk[i] = i < len ? JC[s + i] : 0x7fffffff; sv[i] = i < len ? C[s + i] : 0.f; }
+      for (int i = tid; i < p2; i += 256) { sk[i] = i < len ? JC[s + i] : 0x7fffffff; sv[i] = i < len ? C[s + i] : V(0); }
       __syncthreads();
       for (int k = 2; k <= p2; k <<= 1) {
         for (int j = k >> 1; j > 0; j >>= 1) {
@@ -2069,7 +2070,7 @@ __global__ __launch_bounds__(256) void k_sort_rows(int m, const int* __restrict_
             if (ixj > i) {
               const bool up = (i & k) == 0;
               const int a = sk[i], b = sk[ixj];
-              if ((a > b) == up) { sk[i] = b; sk[ixj] = a; const float t = sv[i]; sv[i] = sv[ixj]; sv[ixj] = t; }
+              if ((a > b) == up) { sk[i] = b; sk[ixj] = a; const V t = sv[i]; sv[i] = sv[ixj]; sv[ixj] = t; }
             }
           }
           __syncthreads();
@@ -2094,8 +2095,9 @@ __global__ __launch_bounds__(256) void k_sort_rows(int m, const int* __restrict_
 // ping-pong between (JC, C) and (JS, CS) inside the row's own segment [IC[row], IC[row+1]); an odd number of passes
 // ends with a copy back.  Block = 256 threads; a pass = histogram of the row, scan of the 256 counts, then rounds of
 // 256 elements ranked with ballots (order inside the block = index order, so every pass is stable).
+template <class V>
 __global__ __launch_bounds__(256) void k_sort_long_rows(int m, const int* __restrict__ IC, int* __restrict__ JC,
-                                                         float* __restrict__ C, int* __restrict__ JS, float* __restrict__ CS,
+                                                         V* __restrict__ C, int* __restrict__ JS, V* __restrict__ CS,
                                                          int keyBits) {
   constexpr int NWV = 4;
   __shared__ int hist[256];
@@ -2116,8 +2118,8 @@ __global__ __launch_bounds__(256) void k_sort_long_rows(int m, const int* __rest
     const bool need = unsorted != 0;
     __syncthreads();
     if (!need) continue;
-    int* kin = JC + s; float* vin = C + s;
-    int* kout = JS + s; float* vout = CS + s;
+    int* kin = JC + s; V* vin = C + s;
+    int* kout = JS + s; V* vout = CS + s;
     int passes = 0;
     for (int shift = 0; shift < keyBits; shift += 8, ++passes) {
       hist[tid] = 0;
@@ -2140,7 +2142,7 @@ __global__ __launch_bounds__(256) void k_sort_long_rows(int m, const int* __rest
         const int i = i0 + tid;
         const bool valid = i < len;
         const int key = valid ? kin[i] : 0;
-        const float val = valid ? vin[i] : 0.f;
+        const V val = valid ? vin[i] : V(0);
         const int d = (key >> shift) & 255;
         unsigned long long peers = ballot64(valid);
 #pragma unroll
@@ -2163,7 +2165,7 @@ __global__ __launch_bounds__(256) void k_sort_long_rows(int m, const int* __rest
       __threadfence_block();
       __syncthreads();
       int* tk = kin; kin = kout; kout = tk;
-      float* tv = vin; vin = vout; vout = tv;
+      V* tv = vin; vin = vout; vout = tv;
     }
     if (passes & 1) {                                    // the sorted row sits in the scratch segment
       for (int i = tid; i < len; i += 256) { kout[i] = kin[i]; vout[i] = vin[i]; }

@@ -3,6 +3,7 @@
 // spgemm_device.hpp.  gfx950 only.  There is NO CPU fallback in this library: without a HIP device
 // every entry point fails with SPGEMM_ERR_NODEVICE / SPGEMM_ERR_HIP.
 #include "spgemm_device.hpp"
+#include "spgemm_f64_device.hpp"
 #include "chain_device.hpp"
 #include "../../include/spgemm_hip.h"
 
@@ -828,6 +829,104 @@ static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const
   return SPGEMM_OK;
 }
 
+// ---- double values (spgemm_f64_device.hpp): the numeric phase only; classification, symbolic pass and scan are the
+// float pipeline's.  One launch per bin, on the side streams launch_numeric uses, each timed into its bin's slot of
+// spgemm_stats.ms_kernel.  Rows of bin 8 wider than the multi-pass LDS kernel takes get device-memory tables: their largest
+// length sizes them (one small kernel and a host read, only when bin 8 has rows).
+static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB,
+                              const int* rowIds, const int* hostBinPtr, const int* dIC, int* dJC, double* dC,
+                              int** gbuf) {
+  const int2* sbl = h->sbl;
+  clear_stale_hip_error();
+  const int* bp = h->dsmall->binPtr;
+  int* err = &h->dsmall->err;
+  const int cu = h->numCU;
+  hipStream_t s = h->stream;
+  auto rows = [&](int lo, int hi) { return hostBinPtr[hi] - hostBinPtr[lo]; };
+  int wide[2] = {0, 0};                                // largest L_i of the rows beyond F64_PASS_MAXL, their number
+  int* gkeys = nullptr;
+  double* gvals = nullptr;
+  int gslots = 0, gblocks = 0;
+  if (rows(8, 9) > 0) {
+    int* dw = nullptr;
+    HIPCHK(pool().alloc((void**)&dw, sizeof(int) * 2));
+    *gbuf = dw;
+    HIPCHK(hipMemsetAsync(dw, 0, sizeof(int) * 2, s));
+    hipLaunchKernelGGL(k_num64_wide_rows, dim3(clampi(cdiv(rows(8, 9), 256), 1, cu)), dim3(256), 0, s, bp, 8, rowIds, dIC,
+                       F64_PASS_MAXL, dw);
+    if (hipMemcpyAsync(wide, dw, sizeof(wide), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return fail(SPGEMM_ERR_HIP, "f64 wide-row probe failed: %s", hipGetErrorString(hipGetLastError()));
+    if (wide[1] > 0) {
+      gslots = 64;
+      while (gslots < 2 * wide[0]) gslots <<= 1;
+      const size_t perBlock = (size_t)gslots * (sizeof(int) + sizeof(double));
+      gblocks = (int)std::max<size_t>(1, std::min<size_t>({(size_t)wide[1], (size_t)cu, (size_t(1) << 30) / perBlock}));
+      // one allocation: keys, then values (8-byte aligned: gslots is a multiple of 64)
+      HIPCHK(pool().alloc((void**)&gbuf[1], perBlock * (size_t)gblocks));
+      gkeys = gbuf[1];
+      gvals = reinterpret_cast<double*>(gkeys + (size_t)gslots * gblocks);
+    }
+  }
+  fork_streams(h);
+  if (rows(8, 9) > 0) {
+    hipStream_t st = h->side[3];
+    { KTimer t(h, SPGEMM_K_NUM_BIG, st);
+      hipLaunchKernelGGL((k_num64_rows<F64_BIG_THREADS, F64_LDS_TBL, false>), dim3(clampi(rows(8, 9), 1, cu)),
+                         dim3(F64_BIG_THREADS), 0, st, bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0,
+                         F64_PASS_MAXL, (int*)nullptr, (double*)nullptr, 0); }
+    if (gblocks > 0) { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);
+      hipLaunchKernelGGL((k_num64_rows<F64_BIG_THREADS, 1, true>), dim3(gblocks), dim3(F64_BIG_THREADS), 0, st, bp, 8,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, F64_PASS_MAXL + 1, 0x7fffffff, gkeys, gvals, gslots); }
+  }
+  if (rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
+    hipLaunchKernelGGL((k_num64_rows<512, 8192, false>), dim3(clampi(rows(7, 8), 1, cu)), dim3(512), 0, st, bp, 7, rowIds,
+                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+  if (rows(6, 7) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
+    hipLaunchKernelGGL((k_num64_rows<256, 4096, false>), dim3(clampi(rows(6, 7), 1, cu * 3)), dim3(256), 0, st, bp, 6, rowIds,
+                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+  if (rows(5, 6) > 0) { hipStream_t st = h->side[1]; KTimer t(h, SPGEMM_K_NUM_HASH1, st);
+    hipLaunchKernelGGL((k_num64_rows<64, 1024, false>), dim3(clampi(rows(5, 6), 1, cu * 12)), dim3(64), 0, st, bp, 5, rowIds,
+                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+  if (rows(4, 5) > 0) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_NUM_G16, st);
+    hipLaunchKernelGGL((k_num64_g16<128, 4>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st, bp, 4, 5, rowIds,
+                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops); }
+  if (rows(1, 4) > 0) { KTimer t(h, SPGEMM_K_NUM_SMALL4);
+    hipLaunchKernelGGL((k_num64_g16<32, 1>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, s, bp, 1, 4, rowIds,
+                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops); }
+  join_streams(h);
+  HIPCHK(hipGetLastError());
+  return SPGEMM_OK;
+}
+
+// phase 2 with double values, into caller-provided dJC/dC (the twin of numeric_phase)
+static int numeric_phase_f64(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB, int m,
+                             const int* dIC, int* dJC, double* dC) {
+  if (h->sym_m != m) return fail(SPGEMM_ERR_ARG, "numeric phase without a matching symbolic phase on this handle");
+  hipStream_t s = h->stream;
+  const int nnzC = (int)h->mirror.nnzC64;
+  int* gbuf[2] = {nullptr, nullptr};                   // the probe word pair and the device-memory tables (pool blocks)
+  auto cleanup = [&](int rc) { pool().release(gbuf[0]); pool().release(gbuf[1]); return rc; };
+  hipEventRecord(h->ev[4], s);
+  if (m > 0 && nnzC > 0) {
+    if (!dJC || !dC) return fail(SPGEMM_ERR_ARG, "output buffers are null");
+    if (int rc = launch_numeric_f64(h, dIA, dA, dJB, dB, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC, gbuf)) {
+      (void)hipStreamSynchronize(s);
+      return cleanup(rc);
+    }
+  }
+  hipEventRecord(h->ev[5], s);
+  if (hipMemcpyAsync(&h->hsmall->err, &h->dsmall->err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return cleanup(fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError())));
+  h->sym_m = -1;
+  if (h->hsmall->err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err));
+  spgemm_stats& st = h->stats;
+  hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
+  st.ms_total += st.ms_numeric;
+  collect_kernel_times(h, false);
+  return cleanup(SPGEMM_OK);
+}
+
 static int spgemm_device(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
                          const int* dIB, const int* dJB, const float* dB, int nnzB, int m, int k, int n,
                          const PreClass* pre, int** dICp, int** dJCp, float** dCp, int* nnzCp) {
@@ -1012,6 +1111,47 @@ extern "C" int hip_spgemm_numeric(spgemm_handle* h, const int* dIA, const int* d
   CHK(check_common(dIB, dJB, dB, nnzB, "B"));
   HIPCHK(hipSetDevice(h->device));
   return numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
+}
+
+// double values: symbolic_phase -> scan/alloc -> f64 numeric (never the opt-in SPGEMM_PATH kernels)
+extern "C" int hip_gpuSpMM_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
+                               const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
+                               int** dICp, int** dJCp, double** dCp, int* nnzCp) {
+  if (!dICp || !dJCp || !dCp || !nnzCp) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dICp = nullptr; *dJCp = nullptr; *dCp = nullptr; *nnzCp = 0;
+  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
+  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
+  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
+  if (!h) CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  CHK(ws_ensure(h, m));
+  int* dIC = nullptr;
+  int* dJC = nullptr;
+  double* dC = nullptr;
+  auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
+  HIPCHK(pool().alloc((void**)&dIC, sizeof(int) * ((size_t)m + 1)));
+  int nnzC = 0;
+  int rc = symbolic_phase(h, dIA, dJA, nnzA, dIB, dJB, m, k, n, nullptr, dIC, &nnzC);
+  if (rc) return cleanup(rc);
+  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
+      hipSuccess != pool().alloc((void**)&dC, sizeof(double) * (size_t)std::max(nnzC, 1)))
+    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
+  rc = numeric_phase_f64(h, dIA, dA, dJB, dB, m, dIC, dJC, dC);
+  if (rc) return cleanup(rc);
+  *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
+  return SPGEMM_OK;
+}
+
+extern "C" int hip_spgemm_numeric_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
+                                      const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
+                                      const int* dIC, int* dJC, double* dC) {
+  (void)k;
+  if (!h) return fail(SPGEMM_ERR_ARG, "hip_spgemm_numeric_f64 needs a handle");
+  if (!dIC) return fail(SPGEMM_ERR_ARG, "dIC is null");
+  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
+  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
+  HIPCHK(hipSetDevice(h->device));
+  return numeric_phase_f64(h, dIA, dA, dJB, dB, m, dIC, dJC, dC);
 }
 
 extern "C" int hip_csr_row_flops(spgemm_handle* h, const int* dIA, const int* dJA, const int* dIB, int m,
@@ -1312,8 +1452,14 @@ static int copy_pageable(int dev, const CopyJob* jobs, int njobs, bool toDevice)
   return SPGEMM_OK;
 }
 
-extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nnzA, const int* IB, const int* JB,
-                            const float* B, int nnzB, int** IC, int** JC, float** C, int* nnzC, int m, int k, int n) {
+// the device product hip_CSR_SpMM{,_f64} runs between the copies
+template <class V>
+using DeviceSpMM = int (*)(spgemm_handle*, const int*, const int*, const V*, int, const int*, const int*, const V*, int, int,
+                           int, int, int**, int**, V**, int*);
+
+template <class V>
+static int csr_spmm_host(DeviceSpMM<V> device_spmm, const int* IA, const int* JA, const V* A, int nnzA, const int* IB,
+                         const int* JB, const V* B, int nnzB, int** IC, int** JC, V** C, int* nnzC, int m, int k, int n) {
   if (!IC || !JC || !C || !nnzC) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *IC = nullptr; *JC = nullptr; *C = nullptr; *nnzC = 0;
   if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension");
@@ -1325,9 +1471,9 @@ extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nn
   CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
   int *dIA = nullptr, *dJA = nullptr, *dIB = nullptr, *dJB = nullptr, *dIC = nullptr, *dJC = nullptr;
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr;
+  V *dA = nullptr, *dB = nullptr, *dC = nullptr;
   int *hIC = nullptr, *hJC = nullptr;
-  float* hC = nullptr;
+  V* hC = nullptr;
   auto cleanup = [&](int rc) {
     for (void* p : {(void*)dIA, (void*)dJA, (void*)dA, (void*)dIB, (void*)dJB, (void*)dB, (void*)dIC, (void*)dJC, (void*)dC})
       pool().release(p);
@@ -1344,18 +1490,18 @@ extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nn
   up.push_back(CopyJob{(void*)(src), (void*)dst, (size_t)(bytes)});
   UP(dIA, IA, sizeof(int) * ((size_t)m + 1));
   UP(dJA, JA, sizeof(int) * (size_t)nnzA);
-  UP(dA, A, sizeof(float) * (size_t)nnzA);
+  UP(dA, A, sizeof(V) * (size_t)nnzA);
   if (!same) {
     UP(dIB, IB, sizeof(int) * ((size_t)k + 1));
     UP(dJB, JB, sizeof(int) * (size_t)nnzB);
-    UP(dB, B, sizeof(float) * (size_t)nnzB);
+    UP(dB, B, sizeof(V) * (size_t)nnzB);
   }
 #undef UP
   if ((rc = copy_pageable(h->device, up.data(), (int)up.size(), true))) return cleanup(rc);
   h->host_api.ms_h2d = ms_since(t0);
   const auto t1 = std::chrono::steady_clock::now();
   int nz = 0;
-  rc = hip_gpuSpMM(h, dIA, dJA, dA, nnzA, same ? dIA : dIB, same ? dJA : dJB, same ? dA : dB, nnzB, m, k, n, &dIC,
+  rc = device_spmm(h, dIA, dJA, dA, nnzA, same ? dIA : dIB, same ? dJA : dJB, same ? dA : dB, nnzB, m, k, n, &dIC,
                    &dJC, &dC, &nz);
   if (rc) return cleanup(rc);
   h->host_api.ms_device = ms_since(t1);
@@ -1363,10 +1509,10 @@ extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nn
   // outputs must be malloc()ed: the caller's CSR::dispose() is free() (nlibs/CSR.h:323-327)
   hIC = (int*)malloc(sizeof(int) * ((size_t)m + 1));
   hJC = (int*)malloc(sizeof(int) * (size_t)std::max(nz, 1));
-  hC = (float*)malloc(sizeof(float) * (size_t)std::max(nz, 1));
+  hC = (V*)malloc(sizeof(V) * (size_t)std::max(nz, 1));
   if (!hIC || !hJC || !hC) return cleanup(fail(SPGEMM_ERR_NOMEM, "host malloc of C failed"));
   const CopyJob down[3] = {{hIC, dIC, sizeof(int) * ((size_t)m + 1)}, {hJC, dJC, sizeof(int) * (size_t)nz},
-                           {hC, dC, sizeof(float) * (size_t)nz}};
+                           {hC, dC, sizeof(V) * (size_t)nz}};
   if ((rc = copy_pageable(h->device, down, 3, false))) return cleanup(rc);
   h->host_api.ms_d2h = ms_since(t2);
   h->host_api.ms_total = ms_since(t0);
@@ -1375,6 +1521,16 @@ extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nn
   h->host_api.bytes_d2h = (long long)(down[0].bytes + down[1].bytes + down[2].bytes);
   *IC = hIC; *JC = hJC; *C = hC; *nnzC = nz;
   return cleanup(SPGEMM_OK);
+}
+
+extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nnzA, const int* IB, const int* JB,
+                            const float* B, int nnzB, int** IC, int** JC, float** C, int* nnzC, int m, int k, int n) {
+  return csr_spmm_host<float>(hip_gpuSpMM, IA, JA, A, nnzA, IB, JB, B, nnzB, IC, JC, C, nnzC, m, k, n);
+}
+
+extern "C" int hip_CSR_SpMM_f64(const int* IA, const int* JA, const double* A, int nnzA, const int* IB, const int* JB,
+                                const double* B, int nnzB, int** IC, int** JC, double** C, int* nnzC, int m, int k, int n) {
+  return csr_spmm_host<double>(hip_gpuSpMM_f64, IA, JA, A, nnzA, IB, JB, B, nnzB, IC, JC, C, nnzC, m, k, n);
 }
 
 // phases of the latest hip_CSR_SpMM (host arrays in, host arrays out) on the default handle
@@ -1829,7 +1985,8 @@ extern "C" int hip_gpuRmclIter(int maxIter, int rows, int cols, const int* gIA, 
 // ------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------
-extern "C" int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, float* dC) {
+template <class V>
+static int sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, V* dC) {
   if (m < 0 || !dIC) return fail(SPGEMM_ERR_ARG, "bad argument");
   if (!h) CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
@@ -1838,12 +1995,12 @@ extern "C" int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* d
   hipStream_t s = h->stream;
   int* dcnt = nullptr;
   int* JS = nullptr;
-  float* CS = nullptr;
+  V* CS = nullptr;
   auto cleanup = [&](int rc) { pool().release(dcnt); pool().release(JS); pool().release(CS); return rc; };
   auto hipfail = [&](const char* what) { return cleanup(fail(SPGEMM_ERR_HIP, "sort rows: %s: %s", what, hipGetErrorString(hipGetLastError()))); };
   if (pool().alloc((void**)&dcnt, sizeof(int)) != hipSuccess) return hipfail("allocation");
   if (hipMemsetAsync(dcnt, 0, sizeof(int), s) != hipSuccess) return hipfail("memset");
-  hipLaunchKernelGGL(k_sort_rows, dim3(clampi(m, 1, h->numCU * 8)), dim3(256), 0, s, m, dIC, dJC, dC, dcnt);
+  hipLaunchKernelGGL(k_sort_rows<V>, dim3(clampi(m, 1, h->numCU * 8)), dim3(256), 0, s, m, dIC, dJC, dC, dcnt);
   int info[2] = {0, 0};                                // unsorted rows longer than SORT_MAX, nnz
   if (hipMemcpyAsync(&info[0], dcnt, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipMemcpyAsync(&info[1], dIC + m, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -1852,14 +2009,22 @@ extern "C" int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* d
   if (info[0] > 0 && info[1] > 0) {
     // the long rows sort between their segment of (JC, C) and the same segment of a scratch copy
     if (pool().alloc((void**)&JS, sizeof(int) * (size_t)info[1]) != hipSuccess ||
-        pool().alloc((void**)&CS, sizeof(float) * (size_t)info[1]) != hipSuccess)
+        pool().alloc((void**)&CS, sizeof(V) * (size_t)info[1]) != hipSuccess)
       return hipfail("scratch allocation");
     // column bits: the columns of a valid CSR are < 2^31; take the width from the largest possible key
     const int keyBits = 31;
-    hipLaunchKernelGGL(k_sort_long_rows, dim3(clampi(info[0], 1, h->numCU * 4)), dim3(256), 0, s, m, dIC, dJC, dC, JS, CS, keyBits);
+    hipLaunchKernelGGL(k_sort_long_rows<V>, dim3(clampi(info[0], 1, h->numCU * 4)), dim3(256), 0, s, m, dIC, dJC, dC, JS, CS, keyBits);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return hipfail("long rows");
   }
   return cleanup(SPGEMM_OK);
+}
+
+extern "C" int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, float* dC) {
+  return sort_rows<float>(h, m, dIC, dJC, dC);
+}
+
+extern "C" int hip_csr_sort_rows_f64(spgemm_handle* h, int m, const int* dIC, int* dJC, double* dC) {
+  return sort_rows<double>(h, m, dIC, dJC, dC);
 }
 
 extern "C" int spgemm_hip_selftest(spgemm_handle* h) {

@@ -10,6 +10,10 @@ Mirrors (reference file:line):
   sgpuSpMMWrapper(...)        sgpuSpMMWrapper                  mindex2-cuda/kernel.cu:311-427
   scudaSpMM(hA, hB)           scudaSpMM                        mindex2-cuda/nGpuSpMM.cc:245-279
 
+Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
+carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
+*_f64 entry points for float64 operands.  Mixing the two raises SpgemmError before any device work.
+
 There is no CPU fallback: if the library or a HIP device is missing, calls raise SpgemmError.
 PyTorch is not needed here; bench.py / dist.py use it only for device memory and torch.distributed.
 """
@@ -28,6 +32,7 @@ HV_LEN = 9
 NKERNELS = 21
 _I = C.POINTER(C.c_int)
 _F = C.POINTER(C.c_float)
+_D = C.POINTER(C.c_double)
 
 EXPORTS = [
     "spgemm_hip_last_error", "spgemm_hip_device_count", "spgemm_hip_create", "spgemm_hip_destroy",
@@ -43,7 +48,9 @@ EXPORTS = [
     "hip_sharded_spmm_handle", "spgemm_hip_rccl_available", "spgemm_hip_pool_trim",
     "hip_sharded_rmcl_create", "hip_sharded_rmcl_run", "hip_sharded_rmcl_continue", "hip_sharded_rmcl_result", "hip_sharded_rmcl_iter_nnz",
     "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
+    "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
 ]
+VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
 XCHG_NAMES = {0: "auto", 1: "rccl", 2: "peer", 3: "host"}
 UNIQUE_ID_BYTES = 128
@@ -134,6 +141,11 @@ def lib():
         L.hip_gpuRmclIter.argtypes = [C.c_int, C.c_int, C.c_int, _I, _I, _F, C.c_int, _I, _I, _F, C.c_int,
                                       C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _I]
         L.hip_csr_sort_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hip_CSR_SpMM_f64.argtypes = [_I, _I, _D, C.c_int, _I, _I, _D, C.c_int, C.POINTER(_I), C.POINTER(_I),
+                                       C.POINTER(_D), _I, C.c_int, C.c_int, C.c_int]
+        L.hip_gpuSpMM_f64.argtypes = L.hip_gpuSpMM.argtypes
+        L.hip_spgemm_numeric_f64.argtypes = L.hip_spgemm_numeric.argtypes
+        L.hip_csr_sort_rows_f64.argtypes = L.hip_csr_sort_rows.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -286,26 +298,33 @@ class CSR:
     Host CSRs hold numpy arrays; device CSRs (from toGpuCSR / gpuSpMMWrapper) hold raw device
     pointers in the same fields, exactly as the reference reuses one struct for both."""
 
-    def __init__(self, values=None, colInd=None, rowPtr=None, rows=0, cols=0, nnz=0, on_device=False):
+    def __init__(self, values=None, colInd=None, rowPtr=None, rows=0, cols=0, nnz=0, on_device=False, dtype=None):
         self.values, self.colInd, self.rowPtr = values, colInd, rowPtr
         self.rows, self.cols, self.nnz = int(rows), int(cols), int(nnz)
         self.on_device = on_device
+        # value type: a host CSR's values array says it; a device CSR (raw pointers) carries it here
+        if dtype is None:
+            dtype = values.dtype if isinstance(values, np.ndarray) else np.float32
+        self.dtype = np.dtype(dtype)
 
     @staticmethod
-    def from_arrays(rowPtr, colInd, values, rows, cols):
+    def from_arrays(rowPtr, colInd, values, rows, cols, dtype=np.float32):
+        """dtype: np.float32 (QValue float, the default) or np.float64 (the reference's FDOUBLE build)."""
+        dtype = _value_dtype(dtype)
         rowPtr = np.ascontiguousarray(rowPtr, dtype=np.int32)
-        return CSR(np.ascontiguousarray(values, dtype=np.float32), np.ascontiguousarray(colInd, dtype=np.int32),
-                   rowPtr, rows, cols, int(rowPtr[-1]) if len(rowPtr) else 0)
+        return CSR(np.ascontiguousarray(values, dtype=dtype), np.ascontiguousarray(colInd, dtype=np.int32),
+                   rowPtr, rows, cols, int(rowPtr[-1]) if len(rowPtr) else 0, dtype=dtype)
 
     # -- nlibs/CSR.cc:342-379 ------------------------------------------------------------------
     def toGpuCSR(self):
         assert not self.on_device
-        return CSR(h2d(self.values), h2d(self.colInd), h2d(self.rowPtr), self.rows, self.cols, self.nnz, True)
+        return CSR(h2d(self.values), h2d(self.colInd), h2d(self.rowPtr), self.rows, self.cols, self.nnz, True,
+                   dtype=self.dtype)
 
     def toCpuCSR(self):
         assert self.on_device
-        return CSR(d2h(self.values, self.nnz, np.float32), d2h(self.colInd, self.nnz, np.int32),
-                   d2h(self.rowPtr, self.rows + 1, np.int32), self.rows, self.cols, self.nnz, False)
+        return CSR(d2h(self.values, self.nnz, self.dtype), d2h(self.colInd, self.nnz, np.int32),
+                   d2h(self.rowPtr, self.rows + 1, np.int32), self.rows, self.cols, self.nnz, False, dtype=self.dtype)
 
     def deviceDispose(self):
         assert self.on_device
@@ -327,19 +346,37 @@ class CSR:
         assert not self.on_device and not B.on_device
         if self.cols != B.rows:
             raise SpgemmError(f"shape mismatch: A is {self.rows}x{self.cols}, B is {B.rows}x{B.cols}")
+        f64 = _common_dtype(self, B) == np.float64
         L = lib()
-        ic, jc, cv, nnz = _I(), _I(), _F(), C.c_int(0)
-        rc = L.hip_CSR_SpMM(self.rowPtr.ctypes.data_as(_I), self.colInd.ctypes.data_as(_I), self.values.ctypes.data_as(_F),
-                            self.nnz, B.rowPtr.ctypes.data_as(_I), B.colInd.ctypes.data_as(_I), B.values.ctypes.data_as(_F),
-                            B.nnz, C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz), self.rows, self.cols, B.cols)
-        _check(rc, "hip_CSR_SpMM")
+        P = _D if f64 else _F
+        ic, jc, cv, nnz = _I(), _I(), P(), C.c_int(0)
+        fn, name = (L.hip_CSR_SpMM_f64, "hip_CSR_SpMM_f64") if f64 else (L.hip_CSR_SpMM, "hip_CSR_SpMM")
+        rc = fn(self.rowPtr.ctypes.data_as(_I), self.colInd.ctypes.data_as(_I), self.values.ctypes.data_as(P),
+                self.nnz, B.rowPtr.ctypes.data_as(_I), B.colInd.ctypes.data_as(_I), B.values.ctypes.data_as(P),
+                B.nnz, C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz), self.rows, self.cols, B.cols)
+        _check(rc, name)
         n = nnz.value
         rp = np.ctypeslib.as_array(ic, shape=(self.rows + 1,)).copy()
         ci = np.ctypeslib.as_array(jc, shape=(n,)).copy() if n else np.zeros(0, np.int32)
-        v = np.ctypeslib.as_array(cv, shape=(n,)).copy() if n else np.zeros(0, np.float32)
+        v = np.ctypeslib.as_array(cv, shape=(n,)).copy() if n else np.zeros(0, self.dtype)
         for p in (ic, jc, cv):                      # CSR::dispose() == free() (nlibs/CSR.h:323-327)
             L.free(C.cast(p, C.c_void_p))
-        return CSR(v, ci, rp, self.rows, B.cols, n)
+        return CSR(v, ci, rp, self.rows, B.cols, n, dtype=self.dtype)
+
+
+def _value_dtype(dtype):
+    dt = np.dtype(dtype)
+    if dt not in VALUE_DTYPES:
+        raise SpgemmError(f"unsupported value dtype {dt}: float32 or float64")
+    return dt
+
+
+def _common_dtype(A, B):
+    """the value type of A*B; float32 and float64 operands do not mix (there is no mixed-precision path)"""
+    a, b = _value_dtype(A.dtype), _value_dtype(B.dtype)
+    if a != b:
+        raise SpgemmError(f"mixed value types: A is {a}, B is {b} (convert one operand)")
+    return a
 
 
 def host_api_timed(A, B, reps=3):
@@ -373,11 +410,13 @@ def gpuSpMMWrapper(dA, dB, handle=None):
     assert dA.on_device and dB.on_device
     if dA.cols != dB.rows:
         raise SpgemmError("shape mismatch")
+    f64 = _common_dtype(dA, dB) == np.float64
     ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    rc = lib().hip_gpuSpMM(handle.ptr if handle else None, *_dev_args(dA), *_dev_args(dB), dA.rows, dA.cols, dB.cols,
-                           C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
-    _check(rc, "hip_gpuSpMM")
-    return CSR(cv.value, jc.value, ic.value, dA.rows, dB.cols, nnz.value, True)
+    fn, name = (lib().hip_gpuSpMM_f64, "hip_gpuSpMM_f64") if f64 else (lib().hip_gpuSpMM, "hip_gpuSpMM")
+    rc = fn(handle.ptr if handle else None, *_dev_args(dA), *_dev_args(dB), dA.rows, dA.cols, dB.cols,
+            C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
+    _check(rc, name)
+    return CSR(cv.value, jc.value, ic.value, dA.rows, dB.cols, nnz.value, True, dtype=dA.dtype)
 
 
 def gpu_spmm_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
@@ -387,6 +426,16 @@ def gpu_spmm_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
                            C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
                            C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
     _check(rc, "hip_gpuSpMM")
+    return ic.value, jc.value, cv.value, nnz.value
+
+
+def gpu_spmm_raw_f64(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
+    """gpu_spmm_raw with float64 values (hip_gpuSpMM_f64)."""
+    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    rc = lib().hip_gpuSpMM_f64(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
+                               C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
+                               C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
+    _check(rc, "hip_gpuSpMM_f64")
     return ic.value, jc.value, cv.value, nnz.value
 
 
@@ -404,6 +453,13 @@ def spgemm_numeric_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, 
     _check(lib().hip_spgemm_numeric(handle.ptr, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
                                     C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
                                     C.c_void_p(IC), C.c_void_p(JC_out), C.c_void_p(C_out)), "hip_spgemm_numeric")
+
+
+def spgemm_numeric_raw_f64(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out):
+    """Phase 2 with float64 values (hip_spgemm_numeric_f64) after spgemm_symbolic_raw on the same handle."""
+    _check(lib().hip_spgemm_numeric_f64(handle.ptr, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
+                                        C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
+                                        C.c_void_p(IC), C.c_void_p(JC_out), C.c_void_p(C_out)), "hip_spgemm_numeric_f64")
 
 
 def d2d(dst, src, nbytes):
@@ -797,5 +853,8 @@ def gpuRmclIter_sharded(group, maxIter, Mgt, Mt):
 
 
 def sort_rows_device(dC, handle=None):
-    _check(lib().hip_csr_sort_rows(handle.ptr if handle else None, dC.rows, C.c_void_p(dC.rowPtr),
-                                   C.c_void_p(dC.colInd), C.c_void_p(dC.values)), "hip_csr_sort_rows")
+    """CSR::makeOrdered on a device CSR (hip_csr_sort_rows, or hip_csr_sort_rows_f64 for float64 values)."""
+    f64 = _value_dtype(dC.dtype) == np.float64
+    fn, name = (lib().hip_csr_sort_rows_f64, "hip_csr_sort_rows_f64") if f64 else (lib().hip_csr_sort_rows, "hip_csr_sort_rows")
+    _check(fn(handle.ptr if handle else None, dC.rows, C.c_void_p(dC.rowPtr), C.c_void_p(dC.colInd),
+              C.c_void_p(dC.values)), name)

@@ -1,0 +1,92 @@
+"""CPU: the double-precision entry points (hip_*_f64) check their arguments without a GPU, the Python mirror carries the
+value type, mixed float32/float64 operands are refused before any device work, and the float64 test reference agrees with
+scipy."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from f64ref import Host64, spgemm_f64
+from helpers import po, random_csr
+from sparse_matrix_with_flops_amd import hipspgemm as hs
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    import __graft_entry__ as ge
+    ge.build()
+
+
+def test_f64_argument_errors_do_not_need_a_gpu():
+    L = hs.lib()
+    n = C.c_int(-1)
+    ic, jc, cv = hs._I(), hs._I(), hs._D()
+    rp = np.zeros(2, np.int32)
+    rc = L.hip_CSR_SpMM_f64(rp.ctypes.data_as(hs._I), None, None, 0, rp.ctypes.data_as(hs._I), None, None, 0,
+                            C.byref(ic), C.byref(jc), C.byref(cv), C.byref(n), -1, 1, 1)
+    assert rc == 2                                          # SPGEMM_ERR_ARG
+    bad = np.array([0, 2, 1], np.int32)
+    ci = np.zeros(2, np.int32)
+    v = np.zeros(2, np.float64)
+    rc = L.hip_CSR_SpMM_f64(bad.ctypes.data_as(hs._I), ci.ctypes.data_as(hs._I), v.ctypes.data_as(hs._D), 1,
+                            bad.ctypes.data_as(hs._I), ci.ctypes.data_as(hs._I), v.ctypes.data_as(hs._D), 1,
+                            C.byref(ic), C.byref(jc), C.byref(cv), C.byref(n), 2, 2, 2)
+    assert rc == 5 and b"rowPtr" in L.spgemm_hip_last_error()
+    # the device entry points refuse null outputs / a missing handle before touching a device
+    assert L.hip_gpuSpMM_f64(None, None, None, None, 0, None, None, None, 0, 1, 1, 1, None, None, None, None) == 2
+    assert L.hip_spgemm_numeric_f64(None, None, None, None, 0, None, None, None, 0, 1, 1, 1, None, None, None) == 2
+
+
+def test_from_arrays_keeps_the_value_type():
+    A = hs.CSR.from_arrays([0, 2], [0, 1], [1.0 + 2.0 ** -40, 2.0], 1, 2, dtype=np.float64)
+    assert A.values.dtype == np.float64 and A.dtype == np.float64
+    assert A.values[0] == 1.0 + 2.0 ** -40                  # not rounded through float32
+    D = hs.CSR.from_arrays([0, 2], [0, 1], [1.0, 2.0], 1, 2)
+    assert D.values.dtype == np.float32 and D.dtype == np.float32
+    with pytest.raises(hs.SpgemmError):
+        hs.CSR.from_arrays([0, 1], [0], [1], 1, 1, dtype=np.int32)
+
+
+def test_mixed_dtypes_raise_before_device_work():
+    a = hs.CSR(None, None, None, 2, 2, 0, on_device=True, dtype=np.float32)   # no device memory behind it: never used
+    b = hs.CSR(None, None, None, 2, 2, 0, on_device=True, dtype=np.float64)
+    with pytest.raises(hs.SpgemmError, match="mixed"):
+        hs.gpuSpMMWrapper(a, b)
+    with pytest.raises(hs.SpgemmError, match="mixed"):
+        hs.gpuSpMMWrapper(b, a)
+    ha = hs.CSR.from_arrays([0, 1], [0], [1.0], 1, 1)
+    hb = hs.CSR.from_arrays([0, 1], [0], [1.0], 1, 1, dtype=np.float64)
+    with pytest.raises(hs.SpgemmError, match="mixed"):
+        ha.hip_spmm(hb)
+
+
+@pytest.mark.parametrize("seed", range(3))
+def test_f64_reference_agrees_with_scipy(seed):
+    sp = pytest.importorskip("scipy.sparse")
+    rng = np.random.default_rng(seed)
+    r, k, c = (int(x) for x in rng.integers(5, 60, size=3))
+    A = random_csr(r, k, 0.2, seed, sorted_rows=False)
+    B = random_csr(k, c, 0.2, seed + 10, sorted_rows=False)
+    A64 = Host64(A.rowPtr, A.colInd, A.values, r, k)
+    B64 = Host64(B.rowPtr, B.colInd, B.values, k, c)
+    ref = spgemm_f64(A64, B64)
+    sa = sp.csr_matrix((A64.values, A64.colInd, A64.rowPtr), shape=(r, k))
+    sb = sp.csr_matrix((B64.values, B64.colInd, B64.rowPtr), shape=(k, c))
+    dense = (sa @ sb).toarray()
+    got = np.zeros((r, c))
+    rows = np.repeat(np.arange(r), np.diff(ref.rowPtr))
+    got[rows, ref.colInd] = ref.values
+    assert np.allclose(got, dense, rtol=1e-12, atol=1e-12)
+    # the structure is the reference's (structural zeros kept): the float32 oracle's, column-sorted
+    want = po.sequential_spmm(A, B).canonical()
+    assert np.array_equal(ref.rowPtr, want.rowPtr) and np.array_equal(ref.colInd, want.colInd)
+    assert np.all(ref.nterms >= 1) and np.all(ref.absSum >= np.abs(ref.values))
+
+
+def test_f64_reference_keeps_structural_zeros_and_repeats():
+    # (1)(1) + (1)(-1) = 0 stays an entry; a repeated column of B adds up
+    A = Host64([0, 2], [0, 1], [1.0, 1.0], 1, 2)
+    B = Host64([0, 2, 3], [0, 0, 0], [1.0, 0.5, -1.5], 2, 1)
+    ref = spgemm_f64(A, B)
+    assert list(ref.rowPtr) == [0, 1] and list(ref.colInd) == [0]
+    assert ref.values[0] == 0.0 and ref.nterms[0] == 3 and ref.absSum[0] == 3.0
