@@ -89,6 +89,9 @@ int  spgemm_hip_pool_trim(int device);            /* idle cached blocks of `devi
 int  spgemm_hip_memcpy_h2d(void* dst, const void* src, size_t bytes);
 int  spgemm_hip_memcpy_d2h(void* dst, const void* src, size_t bytes);
 int  spgemm_hip_memcpy_d2d(void* dst, const void* src, size_t bytes);   /* device to device, same GPU */
+/* waits for all work queued on the current device; a device-to-device copy above may return before it has run, so a
+ * caller that times one (tools/reorder_bench.py) or hands its destination to another stream waits here */
+int  spgemm_hip_device_synchronize(void);
 
 /* ---- (1) host arrays in, host arrays out ------------------------------------------------------
  * Replaces the *_CSR_SpMM family:  sequential_CSR_SpMM / omp_CSR_SpMM / static_omp_CSR_SpMM /
@@ -346,6 +349,45 @@ int hip_resultsComparison(int m, int n, const int* hIC, const int* hJC, const fl
 /* ---- helpers the reference's drivers use around the path --------------------------------------- */
 /* CSR::makeOrdered on device arrays (nlibs/CSR.cc:73-86): sort every row by column, in place. */
 int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, float* dC);
+
+/* ---- reordering a device CSR: row / column permutations and the transpose --------------------------------------------
+ * All arrays are device pointers; outputs come from the library pool (release with spgemm_hip_free); h == NULL = the
+ * default handle; a call returns after the device work has completed.  Argument checks (null output, negative size,
+ * nnz > 0 with null arrays -> SPGEMM_ERR_ARG) run before any device is touched.  Every value that becomes an address
+ * (rowSrc, colMap, dP, rowPtr, a column renamed through colMap) is validated by a read-only pass that completes before
+ * it is used: bad input -> SPGEMM_ERR_INPUT with a message, outputs NULL, the handle stays usable.
+ *
+ * hip_csr_permute: B = rows of A taken in the order rowSrc, columns renamed by colMap:
+ *   row i of B = row rowSrc[i] of A, entries in A's in-row order; column c of A becomes colMap[c].
+ * rowSrc == NULL / colMap == NULL: identity on that side (both NULL: a deep copy).
+ * rowSrc must be a permutation of 0..m-1, colMap of 0..n-1.
+ *   CSR::PM(P)   = (rowSrc = P,  colMap = NULL)      nlibs/CSR.cc:431-445
+ *   CSR::MP(P)   = (rowSrc = NULL, colMap = P)       nlibs/CSR.cc:447-464
+ *   CSR::PMPt(P) = (rowSrc = P,  colMap = Pt)        nlibs/CSR.cc:466-473   (square only)
+ *   CSR::PtMP(P) = (rowSrc = Pt, colMap = P)         nlibs/CSR.cc:475-482   (square only)
+ * One pass over the entries (PMPt builds no PM temporary).  Rows of B are not column-sorted after a column rename (as in
+ * the reference); hip_csr_sort_rows does that. */
+int hip_csr_permute(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                    const int* dRowSrc, const int* dColMap, int** dIB, int** dJB, float** dB);
+int hip_csr_permute_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                        const int* dRowSrc, const int* dColMap, int** dIB, int** dJB, double** dB);
+
+/* permutationTranspose (nlibs/tools/util.cc:162-168): dPt[dP[i]] = i, dPt caller-allocated int[len];
+ * dP not a permutation of 0..len-1 -> SPGEMM_ERR_INPUT and dPt is not written */
+int hip_permutation_transpose(spgemm_handle* h, int len, const int* dP, int* dPt);
+
+/* CSR::rowDescendingOrderPermutation (nlibs/CSR.cc:484-494): *dP = int[m], rows by descending length.
+ * Rows of equal length keep ascending row id (the reference's key_value_qsort is unstable: its tie order is no contract). */
+int hip_csr_row_descending_permutation(spgemm_handle* h, int m, const int* dIA, int** dP);
+
+/* T = A^T: dIT[n+1], dJT[nnz], dAT[nnz] (the transposed load readSNAPFile(isTrans), nlibs/COO.h:19, for any device CSR).
+ * Stable: row c of T holds the entries of column c of A in A's storage order, so its row ids ascend, and entries with the
+ * same row id keep their order.  T is column-sorted whenever no row of A repeats a column, whether or not A's rows were
+ * sorted.  A column outside [0,n) -> SPGEMM_ERR_INPUT. */
+int hip_csr_transpose(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                      int** dIT, int** dJT, float** dAT);
+int hip_csr_transpose_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                          int** dIT, int** dJT, double** dAT);
 
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs

@@ -139,6 +139,97 @@ CSR CSR::hip_spmm(const CSR& B, const int stride) const {
   return CSR(C, JC, IC, rows, B.cols, nnzC);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// reordering (nlibs/CSR.cc:431-494): upload, one device call, download into malloc()ed arrays
+// ---------------------------------------------------------------------------------------------------------------
+static int* upload_ints(const int* src, int n, const char* what) {
+  int* d = 0;
+  hip_or_die(spgemm_hip_malloc((void**)&d, sizeof(int) * (size_t)(n > 0 ? n : 1)), what);
+  if (n > 0) hip_or_die(spgemm_hip_memcpy_h2d(d, src, sizeof(int) * (size_t)n), what);
+  return d;
+}
+
+// device Pt of a host P (permutationTranspose, nlibs/tools/util.cc:162-168); *dPp receives the uploaded P
+static int* device_inverse(const int P[], int len, int** dPp, const char* what) {
+  *dPp = upload_ints(P, len, what);
+  int* dPt = 0;
+  hip_or_die(spgemm_hip_malloc((void**)&dPt, sizeof(int) * (size_t)(len > 0 ? len : 1)), what);
+  hip_or_die(hip_permutation_transpose(0, len, *dPp, dPt), what);
+  return dPt;
+}
+
+// B = rows of M in the order dRowSrc, columns renamed by dColMap (device permutations, either may be null)
+static CSR permuted(const CSR& M, const int* dRowSrc, const int* dColMap, const char* what) {
+  CSR dM = M.toGpuCSR(), dB;
+  dB.rows = M.rows; dB.cols = M.cols; dB.nnz = M.nnz;
+  hip_or_die(hip_csr_permute(0, M.rows, M.cols, M.nnz, dM.rowPtr, dM.colInd, dM.values, dRowSrc, dColMap, &dB.rowPtr,
+                             &dB.colInd, &dB.values), what);
+  CSR B = dB.toCpuCSR();
+  dB.deviceDispose();
+  dM.deviceDispose();
+  return B;
+}
+
+static void need_square(const CSR& M, const char* what) {
+  if (M.rows != M.cols) { printf("%s: the matrix is %dx%d, not square\n", what, M.rows, M.cols); exit(EXIT_FAILURE); }
+}
+
+CSR CSR::PM(const int P[]) const {              // nlibs/CSR.cc:431-445
+  int* dP = upload_ints(P, rows, "PM");
+  CSR B = permuted(*this, dP, 0, "PM");
+  spgemm_hip_free(dP);
+  return B;
+}
+
+CSR CSR::MP(const int P[]) const {              // nlibs/CSR.cc:447-464
+  int* dP = upload_ints(P, cols, "MP");
+  CSR B = permuted(*this, 0, dP, "MP");
+  spgemm_hip_free(dP);
+  return B;
+}
+
+CSR CSR::PMPt(const int P[]) const {            // nlibs/CSR.cc:466-473
+  need_square(*this, "PMPt");
+  int* dP = 0;
+  int* dPt = device_inverse(P, rows, &dP, "PMPt");
+  CSR B = permuted(*this, dP, dPt, "PMPt");
+  spgemm_hip_free(dP);
+  spgemm_hip_free(dPt);
+  return B;
+}
+
+CSR CSR::PtMP(const int P[]) const {            // nlibs/CSR.cc:475-482
+  need_square(*this, "PtMP");
+  int* dP = 0;
+  int* dPt = device_inverse(P, rows, &dP, "PtMP");
+  CSR B = permuted(*this, dPt, dP, "PtMP");
+  spgemm_hip_free(dP);
+  spgemm_hip_free(dPt);
+  return B;
+}
+
+int* CSR::rowDescendingOrderPermutation() {     // nlibs/CSR.cc:484-494
+  int* dI = upload_ints(rowPtr, rows + 1, "rowDescendingOrderPermutation");
+  int* dP = 0;
+  hip_or_die(hip_csr_row_descending_permutation(0, rows, dI, &dP), "rowDescendingOrderPermutation");
+  int* permu = (int*)must_malloc(sizeof(int) * (size_t)rows, "permu");
+  if (rows > 0) hip_or_die(spgemm_hip_memcpy_d2h(permu, dP, sizeof(int) * (size_t)rows), "rowDescendingOrderPermutation");
+  spgemm_hip_free(dP);
+  spgemm_hip_free(dI);
+  return permu;
+}
+
+CSR CSR::transpose() const {                    // readSNAPFile(isTrans), nlibs/COO.h:19, after the load
+  CSR dM = toGpuCSR(), dT;
+  dT.rows = cols; dT.cols = rows; dT.nnz = nnz;
+  hip_or_die(hip_csr_transpose(0, rows, cols, nnz, dM.rowPtr, dM.colInd, dM.values, &dT.rowPtr, &dT.colInd, &dT.values),
+             "transpose");
+  CSR T = dT.toCpuCSR();
+  dT.deviceDispose();
+  dM.deviceDispose();
+  return T;
+}
+
 long long CSR::spMMFlops(const CSR& B) const {
   long long p = 0;
   for (int q = 0; q < nnz; ++q) { const int j = colInd[q]; p += B.rowPtr[j + 1] - B.rowPtr[j]; }

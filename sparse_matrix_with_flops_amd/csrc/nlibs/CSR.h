@@ -42,6 +42,16 @@ struct CSR {
   // the reference's signatures; accepted and ignored.  Exits on error like the reference's GPU path.
   CSR hip_spmm(const CSR& B, const int stride = 512) const;
 
+  // reordering, nlibs/CSR.cc:431-494, on the MI355X through hip_csr_permute / hip_csr_transpose /
+  // hip_csr_row_descending_permutation: host CSR in (uploaded), host CSR out (arrays malloc()ed, dispose() stays valid).
+  // P is a host permutation of the rows (PM) or columns (MP); PMPt / PtMP need a square matrix.  Exit on error.
+  CSR PM(const int P[]) const;          // nlibs/CSR.cc:431-445: row i of the result = row P[i]
+  CSR MP(const int P[]) const;          // nlibs/CSR.cc:447-464: column c becomes P[c]
+  CSR PMPt(const int P[]) const;        // nlibs/CSR.cc:466-473: one pass, no PM temporary
+  CSR PtMP(const int P[]) const;        // nlibs/CSR.cc:475-482: undoes PMPt(P)
+  int* rowDescendingOrderPermutation(); // nlibs/CSR.cc:484-494: malloc()ed int[rows]; equal lengths by ascending row id
+  CSR transpose() const;                // the transposed load (readSNAPFile(isTrans), nlibs/COO.h:19) for any CSR
+
   // 2 * (number of intermediate products), the reference's original getSpMMFlops (nlibs/cpu_csr_kernel.cc:39-56)
   long long spMMFlops(const CSR& B) const;
 

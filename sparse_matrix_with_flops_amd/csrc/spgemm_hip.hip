@@ -443,6 +443,12 @@ extern "C" int spgemm_hip_memcpy_d2d(void* dst, const void* src, size_t bytes) {
   return SPGEMM_OK;
 }
 
+// hipMemcpy device-to-device may return before the copy has run; this waits for everything queued on the current device
+extern "C" int spgemm_hip_device_synchronize(void) {
+  HIPCHK(hipDeviceSynchronize());
+  return SPGEMM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launch sequence
 // ------------------------------------------------------------------------------------------------
@@ -2057,6 +2063,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // COO -> CSR on the device (the step in front of the path)
 // ------------------------------------------------------------------------------------------------
 #include "coo_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
+// reordering a device CSR: row / column permutations, transpose
+// ------------------------------------------------------------------------------------------------
+#include "reorder_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL

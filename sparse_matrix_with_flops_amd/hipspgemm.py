@@ -49,6 +49,8 @@ EXPORTS = [
     "hip_sharded_rmcl_create", "hip_sharded_rmcl_run", "hip_sharded_rmcl_continue", "hip_sharded_rmcl_result", "hip_sharded_rmcl_iter_nnz",
     "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
     "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
+    "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
+    "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
 ]
 VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
@@ -146,6 +148,14 @@ def lib():
         L.hip_gpuSpMM_f64.argtypes = L.hip_gpuSpMM.argtypes
         L.hip_spgemm_numeric_f64.argtypes = L.hip_spgemm_numeric.argtypes
         L.hip_csr_sort_rows_f64.argtypes = L.hip_csr_sort_rows.argtypes
+        L.hip_csr_permute.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p] + [C.POINTER(C.c_void_p)] * 3
+        L.hip_csr_permute_f64.argtypes = L.hip_csr_permute.argtypes
+        L.hip_permutation_transpose.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.hip_csr_row_descending_permutation.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.hip_csr_transpose.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + \
+            [C.POINTER(C.c_void_p)] * 3
+        L.hip_csr_transpose_f64.argtypes = L.hip_csr_transpose.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -363,6 +373,92 @@ class CSR:
             L.free(C.cast(p, C.c_void_p))
         return CSR(v, ci, rp, self.rows, B.cols, n, dtype=self.dtype)
 
+    # -- reordering (nlibs/CSR.cc:431-494) through the device entry points; host CSR in -> host CSR out (uploaded and
+    #    downloaded around the call), device CSR in -> device CSR out, like the rest of the mirror --------------------
+    def _on_device(self, fn):
+        """fn(device CSR) -> device CSR; wraps the upload / download for a host-resident self"""
+        if self.on_device:
+            return fn(self)
+        d = self.toGpuCSR()
+        try:
+            out = fn(d)
+        finally:
+            d.deviceDispose()
+        try:
+            return out.toCpuCSR()
+        finally:
+            out.deviceDispose()
+
+    def _permuted(self, rowP, colP, handle):
+        f64 = _value_dtype(self.dtype) == np.float64
+
+        def run(d):
+            ups = [h2d(x) if x is not None else None for x in (rowP, colP)]
+            try:
+                raw = csr_permute_raw_f64 if f64 else csr_permute_raw
+                ib, jb, vb = raw(handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values, ups[0], ups[1])
+            finally:
+                for p in ups:
+                    dev_free(p)
+            return CSR(vb, jb, ib, d.rows, d.cols, d.nnz, True, dtype=d.dtype)
+        return self._on_device(run)
+
+    def PM(self, P, handle=None):
+        """CSR::PM (nlibs/CSR.cc:431-445): row i of the result is row P[i] of self.  P: host int32 permutation."""
+        return self._permuted(_host_perm(P, self.rows, "PM"), None, handle)
+
+    def MP(self, P, handle=None):
+        """CSR::MP (nlibs/CSR.cc:447-464): column c of self becomes column P[c]; rows are left unsorted."""
+        return self._permuted(None, _host_perm(P, self.cols, "MP"), handle)
+
+    def PMPt(self, P, handle=None):
+        """CSR::PMPt (nlibs/CSR.cc:466-473), square only: PM(P) then MP(Pt), in one pass over the entries."""
+        _need_square(self, "PMPt")
+        P = _host_perm(P, self.rows, "PMPt")
+        return self._permuted(P, permutation_transpose(P, handle), handle)
+
+    def PtMP(self, P, handle=None):
+        """CSR::PtMP (nlibs/CSR.cc:475-482), square only: MP(P) then PM(Pt); undoes PMPt(P)."""
+        _need_square(self, "PtMP")
+        P = _host_perm(P, self.rows, "PtMP")
+        return self._permuted(permutation_transpose(P, handle), P, handle)
+
+    def transpose(self, handle=None):
+        """self^T on the device (hip_csr_transpose): stable, so the result is column-sorted when no row repeats a column."""
+        f64 = _value_dtype(self.dtype) == np.float64
+
+        def run(d):
+            raw = csr_transpose_raw_f64 if f64 else csr_transpose_raw
+            it, jt, vt = raw(handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values)
+            return CSR(vt, jt, it, d.cols, d.rows, d.nnz, True, dtype=d.dtype)
+        return self._on_device(run)
+
+    def rowDescendingOrderPermutation(self, handle=None):
+        """CSR::rowDescendingOrderPermutation (nlibs/CSR.cc:484-494) -> host int32[rows]: rows by descending length, rows
+        of equal length by ascending id."""
+        rp = self.rowPtr if self.on_device else h2d(self.rowPtr)
+        try:
+            dp = row_descending_permutation_raw(handle, self.rows, rp)
+        finally:
+            if not self.on_device:
+                dev_free(rp)
+        try:
+            return d2h(dp, self.rows, np.int32)
+        finally:
+            dev_free(dp)
+
+
+def _need_square(M, what):
+    if M.rows != M.cols:
+        raise SpgemmError(f"{what} needs a square matrix, this one is {M.rows}x{M.cols}")
+
+
+def _host_perm(P, length, what):
+    P = np.ascontiguousarray(P, dtype=np.int32)
+    if P.ndim != 1 or len(P) != length:
+        raise SpgemmError(f"{what}: P has {P.size} entries, the matrix side has {length}")
+    return P
+
 
 def _value_dtype(dtype):
     dt = np.dtype(dtype)
@@ -467,6 +563,11 @@ def d2d(dst, src, nbytes):
     _check(lib().spgemm_hip_memcpy_d2d(C.c_void_p(dst), C.c_void_p(src), int(nbytes)), "spgemm_hip_memcpy_d2d")
 
 
+def device_synchronize():
+    """Wait for all work queued on the current device (a d2d copy may return before it has run)."""
+    _check(lib().spgemm_hip_device_synchronize(), "spgemm_hip_device_synchronize")
+
+
 def rmcl_prune_raw(handle, m, IC, JC, CV, nnz=None):
     """hip_rmcl_prune on raw device pointers: inflate/prune/normalise the rows of C, compacted into new pool arrays.
     nnz (optional): nnz(C) when the caller knows it (hip_rmcl_prune_n: no device read for it).
@@ -561,6 +662,69 @@ def coo_to_csr(rows, cols, ri, ci, v, flags, handle=None):
         for p in (dr, dc, dv):
             dev_free(p)
     return CSR(av, ja, ia, rows, cols, n, True)
+
+
+def _csr_permute(fn, name, handle, m, n, nnz, IA, JA, VA, rowSrc, colMap):
+    ib, jb, vb = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA),
+              C.c_void_p(rowSrc), C.c_void_p(colMap), C.byref(ib), C.byref(jb), C.byref(vb)), name)
+    return ib.value, jb.value, vb.value
+
+
+def csr_permute_raw(handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
+    """hip_csr_permute on raw device pointers (rowSrc / colMap: device int arrays or None = identity) -> (dIB, dJB, dB)
+    from the library pool (release with dev_free)."""
+    return _csr_permute(lib().hip_csr_permute, "hip_csr_permute", handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
+
+
+def csr_permute_raw_f64(handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
+    """csr_permute_raw with float64 values (hip_csr_permute_f64)."""
+    return _csr_permute(lib().hip_csr_permute_f64, "hip_csr_permute_f64", handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
+
+
+def _csr_transpose(fn, name, handle, m, n, nnz, IA, JA, VA):
+    it, jt, vt = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA),
+              C.byref(it), C.byref(jt), C.byref(vt)), name)
+    return it.value, jt.value, vt.value
+
+
+def csr_transpose_raw(handle, m, n, nnz, IA, JA, VA):
+    """hip_csr_transpose on raw device pointers -> (dIT[n+1], dJT, dAT) from the library pool (release with dev_free)."""
+    return _csr_transpose(lib().hip_csr_transpose, "hip_csr_transpose", handle, m, n, nnz, IA, JA, VA)
+
+
+def csr_transpose_raw_f64(handle, m, n, nnz, IA, JA, VA):
+    """csr_transpose_raw with float64 values (hip_csr_transpose_f64)."""
+    return _csr_transpose(lib().hip_csr_transpose_f64, "hip_csr_transpose_f64", handle, m, n, nnz, IA, JA, VA)
+
+
+def permutation_transpose_raw(handle, length, dP, dPt):
+    """hip_permutation_transpose on raw device pointers: dPt[dP[i]] = i (dPt: caller's device int[length])."""
+    _check(lib().hip_permutation_transpose(handle.ptr if handle else None, int(length), C.c_void_p(dP), C.c_void_p(dPt)),
+           "hip_permutation_transpose")
+
+
+def row_descending_permutation_raw(handle, m, IA):
+    """hip_csr_row_descending_permutation on a raw device rowPtr -> device int[m] from the pool (release with dev_free)."""
+    dp = C.c_void_p()
+    _check(lib().hip_csr_row_descending_permutation(handle.ptr if handle else None, int(m), C.c_void_p(IA), C.byref(dp)),
+           "hip_csr_row_descending_permutation")
+    return dp.value
+
+
+def permutation_transpose(P, handle=None):
+    """permutationTranspose (nlibs/tools/util.cc:162-168) on the device: host int32 P in, host Pt out, Pt[P[i]] = i."""
+    P = np.ascontiguousarray(P, dtype=np.int32)
+    if P.ndim != 1:
+        raise SpgemmError("permutation_transpose: P must be one-dimensional")
+    dp, dpt = h2d(P), dev_alloc(P.nbytes)
+    try:
+        permutation_transpose_raw(handle, len(P), dp, dpt)
+        return d2h(dpt, len(P), np.int32)
+    finally:
+        dev_free(dp)
+        dev_free(dpt)
 
 
 def row_flops_raw(handle, IA, JA, IB, m, out_ptr):
