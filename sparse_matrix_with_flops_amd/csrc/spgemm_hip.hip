@@ -8,7 +8,9 @@
 #include "../../include/spgemm_hip.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -18,11 +20,17 @@
 #include <mutex>
 #include <sys/mman.h>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace smf;
 
 static_assert(NBINS == SPGEMM_NBINS, "bin count of the kernels and of the C ABI differ");
+#ifdef SMF_ABLATE
+constexpr bool kAblate = true;      // diagnostic build: the ablated float kernels break their invariants on purpose
+#else
+constexpr bool kAblate = false;
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -224,12 +232,25 @@ struct spgemm_handle {
 static std::mutex g_count_mu;
 static std::map<int, int> g_handles_on;          // device -> live handles (the pool is trimmed when the last one goes)
 
+// the workspace blocks sized by the row count: where each pointer lives and its bytes for `cap` rows
+struct WsBlock { void** ptr; size_t bytes; };
+static std::array<WsBlock, 9> ws_blocks(spgemm_handle* h, size_t cap) {
+  const size_t nblk = (cap + K1_THREADS - 1) / K1_THREADS;
+  const size_t ntile = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE + 1;
+  return {{{(void**)&h->rowFlops, sizeof(int) * cap},
+           {(void**)&h->binId, cap},
+           {(void**)&h->blockHist, sizeof(int) * nblk * NSLOTS},
+           {(void**)&h->blockOff, sizeof(int) * nblk * NSLOTS},
+           {(void**)&h->rowIds, sizeof(int) * cap},
+           {(void**)&h->tileSum, sizeof(unsigned long long) * ntile},
+           {(void**)&h->blockP, sizeof(unsigned long long) * nblk},
+           {(void**)&h->batchStart, sizeof(int) * (3 * cap + 64)},
+           {(void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)}}};
+}
+
 static int ws_free(spgemm_handle* h) {
-  hipFree(h->rowFlops); hipFree(h->binId); hipFree(h->blockHist); hipFree(h->blockOff);
-  hipFree(h->rowIds); hipFree(h->tileSum); hipFree(h->blockP); hipFree(h->batchStart); hipFree(h->chainWords);
-  h->batchStart = nullptr; h->chainWords = nullptr;
-  h->rowFlops = nullptr; h->binId = nullptr; h->blockHist = nullptr; h->blockOff = nullptr;
-  h->rowIds = nullptr; h->tileSum = nullptr; h->blockP = nullptr; h->cap_m = -1;
+  for (const WsBlock& b : ws_blocks(h, 0)) { hipFree(*b.ptr); *b.ptr = nullptr; }
+  h->cap_m = -1;
   return SPGEMM_OK;
 }
 
@@ -247,19 +268,14 @@ static int ws_ensure(spgemm_handle* h, int m) {
   if (m <= h->cap_m) return SPGEMM_OK;
   ws_free(h);
   const size_t cap = (size_t)m + (size_t)m / 8 + 1024;
-  const size_t nblk = (cap + K1_THREADS - 1) / K1_THREADS;
-  const size_t ntile = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE + 1;
-  HIPCHK(hipMalloc((void**)&h->rowFlops, sizeof(int) * cap));
-  HIPCHK(hipMalloc((void**)&h->binId, cap));
-  HIPCHK(hipMalloc((void**)&h->blockHist, sizeof(int) * nblk * NSLOTS));
-  HIPCHK(hipMalloc((void**)&h->blockOff, sizeof(int) * nblk * NSLOTS));
-  HIPCHK(hipMalloc((void**)&h->rowIds, sizeof(int) * cap));
-  HIPCHK(hipMalloc((void**)&h->tileSum, sizeof(unsigned long long) * ntile));
-  HIPCHK(hipMalloc((void**)&h->blockP, sizeof(unsigned long long) * nblk));
-  HIPCHK(hipMalloc((void**)&h->batchStart, sizeof(int) * (3 * cap + 64)));
-  HIPCHK(hipMalloc((void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)));
+  for (const WsBlock& b : ws_blocks(h, cap)) HIPCHK(hipMalloc(b.ptr, b.bytes));
   h->cap_m = (int)std::min<size_t>(cap, 0x7fffffff);
   return SPGEMM_OK;
+}
+
+// an integer knob of the handle from the environment; a value outside [lo, hi] is ignored
+static void env_int(const char* name, int lo, int hi, int* field) {
+  if (const char* e = getenv(name)) { const int v = atoi(e); if (v >= lo && v <= hi) *field = v; }
 }
 
 extern "C" int spgemm_hip_device_count(int* count) {
@@ -290,15 +306,15 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   for (auto& u : h->kused) u = false;
   { const char* e = getenv("SPGEMM_CONCURRENT"); h->serial = !(e && e[0] == '1'); }
 #ifdef SMF_ABLATE
-  { const char* e = getenv("SPGEMM_ABLATE"); int v = e ? atoi(e) : 0; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(smf::g_ablate), &v, sizeof(int))); }
+  { int v = 0; env_int("SPGEMM_ABLATE", INT_MIN, INT_MAX, &v); HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(smf::g_ablate), &v, sizeof(int))); }
 #endif
-  { const char* e = getenv("SPGEMM_H1SYM"); if (e) { const int c = atoi(e); if (c >= 1 && c <= 32) h->h1sym = c; } }
-  { const char* e = getenv("SPGEMM_H1NUM"); if (e) { const int c = atoi(e); if (c >= 1 && c <= 32) h->h1num = c; } }
-  { const char* e = getenv("SPGEMM_BHMARGIN"); if (e) { const int c = atoi(e); if (c >= 10 && c <= 400) h->bhMargin = c; } }
-  { const char* e = getenv("SPGEMM_BHCAP"); if (e) { const int c = atoi(e); if (c >= 1024 && c <= BH_CAP_MAX) h->bhCap = c; } }
-  { const char* e = getenv("SPGEMM_PATH"); if (e) { const int v = atoi(e); if (v >= 0 && v <= 2) h->pathMode = v; } }
-  { const char* e = getenv("SPGEMM_CHAIN_CFG"); if (e) h->chainCfg = atoi(e); }
-  { const char* e = getenv("SPGEMM_U"); if (e) { const int u = atoi(e); if (u == 2 || u == 4 || u == 8) h->U = u; } }
+  env_int("SPGEMM_H1SYM", 1, 32, &h->h1sym);
+  env_int("SPGEMM_H1NUM", 1, 32, &h->h1num);
+  env_int("SPGEMM_BHMARGIN", 10, 400, &h->bhMargin);
+  env_int("SPGEMM_BHCAP", 1024, BH_CAP_MAX, &h->bhCap);
+  env_int("SPGEMM_PATH", 0, 2, &h->pathMode);
+  env_int("SPGEMM_CHAIN_CFG", INT_MIN, INT_MAX, &h->chainCfg);   // unchecked: chain_cfg() maps anything else to 0
+  { int u = h->U; env_int("SPGEMM_U", 2, 8, &u); if (u == 2 || u == 4 || u == 8) h->U = u; }
   for (auto& st : h->side) {
     if (h->serial) st = h->stream;
     else HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -508,19 +524,28 @@ static void join_streams(spgemm_handle* h) {
   }
 }
 
-#define LAUNCH_NUM(NW, TBL, grid, block, st, ...)                                                               \
-  do {                                                                                                         \
-    if (pcnt && pmode == 2) hipLaunchKernelGGL((k_num_hash<NW, TBL, 2, 2>), grid, block, 0, st, __VA_ARGS__, pcnt); \
-    else if (pcnt) hipLaunchKernelGGL((k_num_hash<NW, TBL, 2, 1>), grid, block, 0, st, __VA_ARGS__, pcnt);     \
-    else LAUNCH_U(k_num_hash, NW, TBL, grid, block, st, __VA_ARGS__, (int*)nullptr);                           \
-  } while (0)
-
 #define LAUNCH_U(KERN, NW, TBL, grid, block, st, ...)                                              \
   do {                                                                                             \
     if (h->U == 8) hipLaunchKernelGGL((KERN<NW, TBL, 8>), grid, block, 0, st, __VA_ARGS__);        \
     else if (h->U == 4) hipLaunchKernelGGL((KERN<NW, TBL, 4>), grid, block, 0, st, __VA_ARGS__);   \
     else hipLaunchKernelGGL((KERN<NW, TBL, 2>), grid, block, 0, st, __VA_ARGS__);                  \
   } while (0)
+
+// The numeric kernels take the fused R-MCL prune as a template argument: 0 plain SpGEMM, 1 prune, 2 prune with no symbolic
+// pass below bin 8.  This is the one place it is derived from pcnt/pmode: f is called with it as a compile-time constant.
+template <class F>
+static void with_prune_arg(const int* pcnt, int pmode, F f) {
+  if (pcnt && pmode == 2) f(std::integral_constant<int, 2>());
+  else if (pcnt) f(std::integral_constant<int, 1>());
+  else f(std::integral_constant<int, 0>());
+}
+
+// k_num_hash: the rounds-in-flight variants (SPGEMM_U) exist for the plain kernel only
+#define LAUNCH_NUM(NW, TBL, grid, block, st, ...)                                                                  \
+  with_prune_arg(pcnt, pmode, [&](auto prune) {                                                                    \
+    if constexpr (prune != 0) hipLaunchKernelGGL((k_num_hash<NW, TBL, 2, prune>), grid, block, 0, st, __VA_ARGS__, pcnt); \
+    else LAUNCH_U(k_num_hash, NW, TBL, grid, block, st, __VA_ARGS__, (int*)nullptr);                               \
+  })
 
 // flops + bins: K1, K2, K3.  Also presets IC[row] for rows with 0 / 1 products.
 // nnzA >= 0: the per-entry records h->sbl are (re)built first and the row sums read them; nnzA < 0 (entry points of
@@ -659,19 +684,13 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
     if (nb > 0) LAUNCH_NUM(1, 1024, dim3(grid8(nb, cu * 16)), dim3(64), st, sb, SLOT_H1B,
                          rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 7 * 32, h->rowFlops); }
   if (rows(4, 5) > 0) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_NUM_G16, st);
-    if (pcnt && pmode == 2) hipLaunchKernelGGL((k_num_g16<128, 4, 2>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
-                                               bp, 4, 5, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt);
-    else if (pcnt) hipLaunchKernelGGL((k_num_g16<128, 4, 1>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
-                                      bp, 4, 5, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt);
-    else hipLaunchKernelGGL((k_num_g16<128, 4>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
-                            bp, 4, 5, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, (int*)nullptr); }
+    with_prune_arg(pcnt, pmode, [&](auto prune) {
+      hipLaunchKernelGGL((k_num_g16<128, 4, decltype(prune)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
+                         bp, 4, 5, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   if (minBin <= 1 && rows(1, 4) > 0) { KTimer t(h, SPGEMM_K_NUM_SMALL4);   // 1..16 products: 16-lane flattened kernel, one round per row
-    if (pcnt && pmode == 2) hipLaunchKernelGGL((k_num_g16<32, 1, 2>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
-                                               bp, 1, 4, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt);
-    else if (pcnt) hipLaunchKernelGGL((k_num_g16<32, 1, 1>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
-                                      bp, 1, 4, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt);
-    else hipLaunchKernelGGL((k_num_g16<32, 1>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
-                            bp, 1, 4, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, (int*)nullptr); }
+    with_prune_arg(pcnt, pmode, [&](auto prune) {
+      hipLaunchKernelGGL((k_num_g16<32, 1, decltype(prune)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
+                         bp, 1, 4, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   join_streams(h);
   HIPCHK(hipGetLastError());
   return SPGEMM_OK;
@@ -751,7 +770,68 @@ static int check_common(const void* a, const void* b, const void* c, int nnz, co
 struct PreClass { const int* drowIds; const int* hv; const int* dflops; };
 static int unpack_classification(spgemm_handle* h, int m, const PreClass& pre, int* dIC);
 
-// phase 1: classify + symbolic + scan; one host sync at the end (nnzC, bin sizes, error flags)
+// C = A*B on device arrays as the routes below pass it around, and where the caller wants the result (arrays of the pool)
+template <class V> struct Product { const int* IA; const int* JA; const V* A; int nnzA; const int* IB; const int* JB; const V* B; int m, k, n; };
+template <class V> struct Result { int** IC; int** JC; V** C; int* nnz; };
+
+// What a route publishes as spgemm_stats from the mirror it read (publish_stats).  Counts and bins always come from the mirror.
+enum class StatsForm {
+  OneShot,       // phases queued back to back: ms_scan_alloc = ev2->ev4 (scan + allocation of C), ms_total = elapsed ev0->ev5
+  OneShotNoNnz,  // the same for the fused R-MCL step without a symbolic pass: nnz(C) is never computed, nnzC = -1
+  Symbolic,      // end of a symbolic phase: ms_scan_alloc = ev2->ev3, ms_numeric = 0, ms_total = sum of the parts (numeric_phase adds its own)
+  CountsOnly,    // R-MCL loop form: nnzC = -1 and no event is read, the host runs ahead of the stream
+  Classified,    // hip_gpuFlopsClassify: no product is computed; nnzC and the phase times are left alone
+};
+
+static void publish_stats(spgemm_handle* h, const HostMirror& hm, StatsForm form) {
+  spgemm_stats& st = h->stats;
+  st.total_flops = (long long)hm.totalP;
+  for (int b = 0; b < NBINS; ++b) st.bin_rows[b] = hm.binPtr[b + 1] - hm.binPtr[b];
+  if (form == StatsForm::Classified) return collect_kernel_times(h, true);
+  st.nnzC = (form == StatsForm::OneShot || form == StatsForm::Symbolic) ? (int)std::min<unsigned long long>(hm.nnzC64, 0x7fffffffULL) : -1;
+  if (form == StatsForm::CountsOnly) return;
+  const bool twoPhase = form == StatsForm::Symbolic;
+  hipEventElapsedTime(&st.ms_classify, h->ev[0], h->ev[1]);
+  hipEventElapsedTime(&st.ms_symbolic, h->ev[1], h->ev[2]);
+  hipEventElapsedTime(&st.ms_scan_alloc, h->ev[2], h->ev[twoPhase ? 3 : 4]);
+  if (twoPhase) {
+    st.ms_numeric = 0.f;
+    st.ms_total = st.ms_classify + st.ms_symbolic + st.ms_scan_alloc;
+  } else {
+    hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
+    hipEventElapsedTime(&st.ms_total, h->ev[0], h->ev[5]);
+  }
+  collect_kernel_times(h, true);
+}
+
+// dsmall -> hsmall, then wait for the stream: the host round trip that ends a phase
+static bool fetch_mirror(spgemm_handle* h) {
+  return hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, h->stream) == hipSuccess &&
+         hipStreamSynchronize(h->stream) == hipSuccess;
+}
+
+// ... kept as h->mirror, and what the device reported turned into a status; `phase` names the caller in the message.
+// `deferred`: error flags the caller handles itself -- when one of them is set the error word is left to the caller.
+static int read_mirror(spgemm_handle* h, const char* phase, int deferred = 0) {
+  if (!fetch_mirror(h)) return fail(SPGEMM_ERR_HIP, "%s failed: %s", phase, hipGetErrorString(hipGetLastError()));
+  h->mirror = *h->hsmall;
+  const HostMirror& hm = h->mirror;
+  if (hm.err && !(hm.err & deferred)) return fail(SPGEMM_ERR_INTERNAL, "device invariant broken in %s (flags=%d)", phase, hm.err);
+  if (hm.nnzC64 > 0x7fffffffULL) return fail(SPGEMM_ERR_OVERFLOW, "nnz(C)=%llu does not fit int32 CSR", hm.nnzC64);
+  return SPGEMM_OK;
+}
+
+// phase 1, finish: the one host sync (nnzC, bin sizes, error flags); leaves the phase pending for numeric_phase.
+// Also ends a one-shot call whose symbolic kernels are queued but whose product is too large to size C by it.
+static int finish_symbolic(spgemm_handle* h, int m, int* nnzCp) {
+  CHK(read_mirror(h, "symbolic phase"));
+  publish_stats(h, h->mirror, StatsForm::Symbolic);
+  h->sym_m = m;
+  *nnzCp = (int)h->mirror.nnzC64;
+  return SPGEMM_OK;
+}
+
+// phase 1: classify + symbolic + scan are queued with ev[0..3] around them, then finish_symbolic
 static int symbolic_phase(spgemm_handle* h, const int* dIA, const int* dJA, int nnzA, const int* dIB, const int* dJB,
                           int m, int k, int n, const PreClass* pre, int* dIC, int* nnzCp) {
   (void)k;
@@ -774,26 +854,7 @@ static int symbolic_phase(spgemm_handle* h, const int* dIA, const int* dJA, int 
   if (m > 0) CHK(launch_scan(h, dIC, m, &h->dsmall->nnzC64));
   else HIPCHK(hipMemsetAsync(dIC, 0, sizeof(int), s));
   hipEventRecord(h->ev[3], s);
-  if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return fail(SPGEMM_ERR_HIP, "symbolic phase failed: %s", hipGetErrorString(hipGetLastError()));
-  h->mirror = *h->hsmall;
-  const HostMirror& hm = h->mirror;
-  if (hm.err) return fail(SPGEMM_ERR_INTERNAL, "device invariant broken in symbolic phase (flags=%d)", hm.err);
-  if (hm.nnzC64 > 0x7fffffffULL) return fail(SPGEMM_ERR_OVERFLOW, "nnz(C)=%llu does not fit int32 CSR", hm.nnzC64);
-  spgemm_stats& st = h->stats;
-  st.total_flops = (long long)hm.totalP;
-  st.nnzC = (int)hm.nnzC64;
-  for (int b = 0; b < NBINS; ++b) st.bin_rows[b] = hm.binPtr[b + 1] - hm.binPtr[b];
-  hipEventElapsedTime(&st.ms_classify, h->ev[0], h->ev[1]);
-  hipEventElapsedTime(&st.ms_symbolic, h->ev[1], h->ev[2]);
-  hipEventElapsedTime(&st.ms_scan_alloc, h->ev[2], h->ev[3]);
-  st.ms_numeric = 0.f;
-  st.ms_total = st.ms_classify + st.ms_symbolic + st.ms_scan_alloc;
-  collect_kernel_times(h, true);
-  h->sym_m = m;
-  *nnzCp = (int)hm.nnzC64;
-  return SPGEMM_OK;
+  return finish_symbolic(h, m, nnzCp);
 }
 
 // room for the big rows' bitmaps next time (rank kernel only)
@@ -806,33 +867,6 @@ static void grow_bitmaps(spgemm_handle* h, int n) {
     if (hipMalloc((void**)&h->bigBitmaps, (size_t)cap * BIG_WORDS * sizeof(unsigned)) == hipSuccess) h->bm_cap = cap;
     else { h->bm_cap = 0; (void)hipGetLastError(); }
   }
-}
-
-// phase 2: numeric into caller-provided dJC/dC; one host sync at the end (error flags)
-static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, const int* dIB,
-                         const int* dJB, const float* dB, int m, int n, const int* dIC, int* dJC, float* dC) {
-  if (h->sym_m != m) return fail(SPGEMM_ERR_ARG, "numeric phase without a matching symbolic phase on this handle");
-  hipStream_t s = h->stream;
-  const int nnzC = (int)h->mirror.nnzC64;
-  hipEventRecord(h->ev[4], s);
-  if (m > 0 && nnzC > 0) {
-    if (!dJC || !dC) return fail(SPGEMM_ERR_ARG, "output buffers are null");
-    CHK(launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC));
-  }
-  hipEventRecord(h->ev[5], s);
-  if (hipMemcpyAsync(&h->hsmall->err, &h->dsmall->err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError()));
-  h->sym_m = -1;
-#ifndef SMF_ABLATE
-  if (h->hsmall->err) return fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err);
-#endif
-  spgemm_stats& st = h->stats;
-  hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
-  st.ms_total += st.ms_numeric;
-  collect_kernel_times(h, false);
-  grow_bitmaps(h, n);
-  return SPGEMM_OK;
 }
 
 // ---- double values (spgemm_f64_device.hpp): the numeric phase only; classification, symbolic pass and scan are the
@@ -904,195 +938,197 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   return SPGEMM_OK;
 }
 
-// phase 2 with double values, into caller-provided dJC/dC (the twin of numeric_phase)
-static int numeric_phase_f64(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB, int m,
-                             const int* dIC, int* dJC, double* dC) {
+// the numeric launch of either value type behind one name.  `scratch` (double only): pool blocks that the caller releases
+// once the kernels are done -- the probe word pair and the device-memory tables
+static int launch_numeric_of(spgemm_handle* h, const int* dIA, const float* dA, const int* dJB, const float* dB, int n,
+                             const int* dIC, int* dJC, float* dC, int**) {
+  return launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC);
+}
+static int launch_numeric_of(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB, int,
+                             const int* dIC, int* dJC, double* dC, int** scratch) {
+  return launch_numeric_f64(h, dIA, dA, dJB, dB, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC, scratch);
+}
+
+// phase 2: numeric into caller-provided dJC/dC; one host sync at the end (error flags)
+template <class V>
+static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const V* dA, const int* dIB, const int* dJB,
+                         const V* dB, int m, int n, const int* dIC, int* dJC, V* dC) {
+  (void)dJA; (void)dIB;
+  constexpr bool isFloat = std::is_same<V, float>::value;
   if (h->sym_m != m) return fail(SPGEMM_ERR_ARG, "numeric phase without a matching symbolic phase on this handle");
   hipStream_t s = h->stream;
   const int nnzC = (int)h->mirror.nnzC64;
-  int* gbuf[2] = {nullptr, nullptr};                   // the probe word pair and the device-memory tables (pool blocks)
-  auto cleanup = [&](int rc) { pool().release(gbuf[0]); pool().release(gbuf[1]); return rc; };
+  int* scratch[2] = {nullptr, nullptr};
+  auto done = [&](int rc) { pool().release(scratch[0]); pool().release(scratch[1]); return rc; };
   hipEventRecord(h->ev[4], s);
   if (m > 0 && nnzC > 0) {
     if (!dJC || !dC) return fail(SPGEMM_ERR_ARG, "output buffers are null");
-    if (int rc = launch_numeric_f64(h, dIA, dA, dJB, dB, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC, gbuf)) {
-      (void)hipStreamSynchronize(s);
-      return cleanup(rc);
+    if (int rc = launch_numeric_of(h, dIA, dA, dJB, dB, n, dIC, dJC, dC, scratch)) {
+      if (!isFloat) (void)hipStreamSynchronize(s);     // kernels already queued may read the scratch blocks
+      return done(rc);
     }
   }
   hipEventRecord(h->ev[5], s);
+  // (only the error word: the rest of the mirror was read at the end of the symbolic phase)
   if (hipMemcpyAsync(&h->hsmall->err, &h->dsmall->err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return cleanup(fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError())));
+    return done(fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError())));
   h->sym_m = -1;
-  if (h->hsmall->err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err));
+  if (!(kAblate && isFloat) && h->hsmall->err)
+    return done(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err));
   spgemm_stats& st = h->stats;
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
   collect_kernel_times(h, false);
-  return cleanup(SPGEMM_OK);
+  if (isFloat) grow_bitmaps(h, n);
+  return done(SPGEMM_OK);
 }
 
-static int spgemm_device(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
-                         const int* dIB, const int* dJB, const float* dB, int nnzB, int m, int k, int n,
-                         const PreClass* pre, int** dICp, int** dJCp, float** dCp, int* nnzCp) {
-  if (!dICp || !dJCp || !dCp || !nnzCp) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dICp = nullptr; *dJCp = nullptr; *dCp = nullptr; *nnzCp = 0;
-  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
-  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
-  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  CHK(ws_ensure(h, m));
-  int* dIC = nullptr;
+// The end of every route that has nnz(C) on the host: allocate colInd/values exactly, run the numeric phase, hand the three
+// arrays to the caller.  Owns dIC: on failure it goes back to the pool with the rest.
+template <class V>
+static int finish_exact(spgemm_handle* h, const Product<V>& p, int nnzC, int* dIC, const Result<V>& out) {
+  int* dJC = nullptr;
+  V* dC = nullptr;
+  auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
+  const size_t cap = (size_t)std::max(nnzC, 1);
+  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * cap) || hipSuccess != pool().alloc((void**)&dC, sizeof(V) * cap))
+    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
+  if (int rc = numeric_phase(h, p.IA, p.JA, p.A, p.IB, p.JB, p.B, p.m, p.n, dIC, dJC, dC)) return cleanup(rc);
+  *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = nnzC;
+  return SPGEMM_OK;
+}
+
+// the two-phase pipeline from its start: symbolic phase, exact allocation, numeric phase.  Owns dIC like finish_exact.
+template <class V>
+static int two_phase(spgemm_handle* h, const Product<V>& p, const PreClass* pre, int* dIC, const Result<V>& out) {
+  int nnzC = 0;
+  if (int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, pre, dIC, &nnzC)) { pool().release(dIC); return rc; }
+  return finish_exact(h, p, nnzC, dIC, out);
+}
+
+// what the C-producing entry points do first: outputs cleared, arguments checked, handle, device, workspace, C.rowPtr
+template <class V>
+static int begin_product(spgemm_handle** hp, const Product<V>& p, int nnzB, const Result<V>& out, int** dIC) {
+  if (!out.IC || !out.JC || !out.C || !out.nnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *out.IC = nullptr; *out.JC = nullptr; *out.C = nullptr; *out.nnz = 0;
+  if (p.m < 0 || p.k < 0 || p.n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", p.m, p.k, p.n);
+  CHK(check_common(p.IA, p.JA, p.A, p.nnzA, "A"));
+  CHK(check_common(p.IB, p.JB, p.B, nnzB, "B"));
+  if (!*hp) CHK(default_handle(hp));
+  HIPCHK(hipSetDevice((*hp)->device));
+  CHK(ws_ensure(*hp, p.m));
+  HIPCHK(pool().alloc((void**)dIC, sizeof(int) * ((size_t)p.m + 1)));
+  return SPGEMM_OK;
+}
+
+// ---- hip_gpuSpMM without a caller's classification.  SPGEMM_PATH (opt-in): rows up to ChainCfg::smallMax products are dealt
+// across rows by the wave-per-batch kernels (chain_device.hpp, round 4) -- pathMode 1 in two passes (counts, scan, entries),
+// pathMode 2 in ONE pass (no symbolic pass, no scan: a chained prefix places them); the bins above keep their per-row kernels.
+struct OptInPath { bool chain, wb2; int minBin; bool skipH1A; };
+static OptInPath opt_in_path(const spgemm_handle* h) {
+  const bool chain = h->pathMode == 2, wb2 = h->pathMode == 1;
+  return {chain, wb2, (chain || wb2) ? chain_cfg(h).minBin : 0, (chain || wb2) && chain_cfg(h).skipH1A};
+}
+
+// Front half: classification, symbolic kernels and scan are queued with no host round trip; the classification (bin sizes,
+// P) is copied to the host while the symbolic kernels run and lands in *mid.
+static int one_shot_front(spgemm_handle* h, const Product<float>& p, const OptInPath& o, int* dIC, HostMirror* mid) {
+  hipStream_t s = h->stream;
+  hipEventRecord(h->ev[0], s);
+  h->cur_rowIds = h->rowIds;
+  CHK(launch_classify(h, p.IA, p.JA, p.IB, p.m, p.nnzA, dIC));
+  if (o.chain || o.wb2) CHK(launch_cut(h, p.m));
+  hipEventRecord(h->ev[1], s);
+  if (hipMemcpyAsync(h->hmid, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipEventRecord(h->evMid, s) != hipSuccess)
+    return fail(SPGEMM_ERR_HIP, "classification copy failed: %s", hipGetErrorString(hipGetLastError()));
+  if (o.wb2) CHK(launch_wbatch<WB_SYM>(h, p.m, p.IA, nullptr, p.JB, nullptr, dIC, nullptr, nullptr, 0));
+  CHK(launch_symbolic(h, p.IA, p.JB, p.m, p.n, h->cur_rowIds, dIC, o.minBin, o.skipH1A));
+  hipEventRecord(h->ev[2], s);
+  if (!o.chain) CHK(launch_scan(h, dIC, p.m, &h->dsmall->nnzC64));
+  hipEventRecord(h->ev[3], s);
+  if (hipEventSynchronize(h->evMid) != hipSuccess)
+    return fail(SPGEMM_ERR_HIP, "classification failed: %s", hipGetErrorString(hipGetLastError()));
+  *mid = *h->hmid;
+  return SPGEMM_OK;
+}
+
+// Back half: colInd/values are allocated with capC entries -- P, an upper bound of nnz(C) (8*P bytes: HBM is 288 GB), or on
+// the one-pass path what the previous, identical-looking call produced (the kernels never write past that and say so if it
+// was not enough) -- so that the numeric kernels can be queued right behind the scan; nnz(C) and the error flags are read
+// once, at the end.  Owns dIC.
+static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInPath& o, const HostMirror& mid, size_t capC,
+                         int* dIC, const Result<float>& out) {
+  const unsigned long long P = mid.totalP;
+  hipStream_t s = h->stream;
   int* dJC = nullptr;
   float* dC = nullptr;
   auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
-  HIPCHK(pool().alloc((void**)&dIC, sizeof(int) * ((size_t)m + 1)));
-  int nnzC = 0;
-  if (!pre && m > 0) {
-    // One-shot path, no host round trip between the phases: the classification (bin sizes, P) is copied to the host
-    // while the symbolic kernels run; colInd/values are allocated with P entries (an upper bound of nnz(C), 8*P bytes --
-    // HBM is 288 GB) so that the numeric kernels can be queued right behind the scan; nnz(C) and the error flags are
-    // read once, at the end.  A product with P beyond the bound below takes the two-phase path.
-    hipStream_t s = h->stream;
-    hipEventRecord(h->ev[0], s);
-    h->cur_rowIds = h->rowIds;
-    int rc = launch_classify(h, dIA, dJA, dIB, m, nnzA, dIC);
-    if (rc) return cleanup(rc);
-    // Rows up to ChainCfg::smallMax products are dealt across rows by the wave-per-batch kernels (chain_device.hpp, round 4):
-    // pathMode 1 in two passes (counts, scan, entries), pathMode 2 in ONE pass (no symbolic pass and no scan for them: a chained
-    // prefix over the batches places them); the bins above keep their per-row kernels.
-    const bool chainPath = h->pathMode == 2, wb2 = h->pathMode == 1;
-    const int minBin = (chainPath || wb2) ? chain_cfg(h).minBin : 0;
-    const bool skipH1A = (chainPath || wb2) && chain_cfg(h).skipH1A;
-    if ((chainPath || wb2) && (rc = launch_cut(h, m))) return cleanup(rc);
-    hipEventRecord(h->ev[1], s);
-    if (hipMemcpyAsync(h->hmid, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipEventRecord(h->evMid, s) != hipSuccess)
-      return cleanup(fail(SPGEMM_ERR_HIP, "classification copy failed: %s", hipGetErrorString(hipGetLastError())));
-    if (wb2 && (rc = launch_wbatch<WB_SYM>(h, m, dIA, nullptr, dJB, nullptr, dIC, nullptr, nullptr, 0))) return cleanup(rc);
-    if ((rc = launch_symbolic(h, dIA, dJB, m, n, h->cur_rowIds, dIC, minBin, skipH1A))) return cleanup(rc);
-    hipEventRecord(h->ev[2], s);
-    if (!chainPath && (rc = launch_scan(h, dIC, m, &h->dsmall->nnzC64))) return cleanup(rc);
-    hipEventRecord(h->ev[3], s);
-    if (hipEventSynchronize(h->evMid) != hipSuccess)
-      return cleanup(fail(SPGEMM_ERR_HIP, "classification failed: %s", hipGetErrorString(hipGetLastError())));
-    const HostMirror mid = *h->hmid;
-    const unsigned long long P = mid.totalP;
-    // A product that compresses (real web graphs: nnz(C)/P ~ 0.5) would hold twice the memory it needs when sized by P.
-    // The handle remembers the previous call: the same shape and product count with nnz(C) < 3/4 P sends this call down
-    // the two-phase path (exact allocation, one more host round trip -- cheap next to the halved footprint).
-    const bool compressive = h->prev_m == m && h->prev_P == P && h->prev_nnzC >= 0 &&
-                             (double)h->prev_nnzC < 0.75 * (double)P;
-    // (one-pass path: a compressive product gets exactly the entries its previous, identical-looking call produced; the
-    // kernels never write past that and say so if it was not enough -- the call is then redone the two-phase way)
-    if (P <= (1ull << 30) && (!compressive || chainPath)) {
-      const size_t capC = compressive ? (size_t)std::max<long long>(h->prev_nnzC, 1ll) : (size_t)std::max<unsigned long long>(P, 1ull);
-      if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * capC) ||
-          hipSuccess != pool().alloc((void**)&dC, sizeof(float) * capC))
-        return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%llu entries) failed", P));
-      hipEventRecord(h->ev[4], s);
-      h->mirror = mid;                                 // bin sizes for the numeric launch grids
-      if (chainPath && (rc = launch_wbatch<WB_CHAIN>(h, m, dIA, dA, dJB, dB, dIC, dJC, dC, (long long)capC))) return cleanup(rc);
-      if (wb2 && P > 0 && (rc = launch_wbatch<WB_NUM>(h, m, dIA, dA, dJB, dB, dIC, dJC, dC, (long long)capC))) return cleanup(rc);
-      if (P > 0 && (rc = launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, mid.binPtr, dIC, dJC, dC, nullptr, 1, minBin, skipH1A))) return cleanup(rc);
-      hipEventRecord(h->ev[5], s);
-      if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess)
-        return cleanup(fail(SPGEMM_ERR_HIP, "SpGEMM failed: %s", hipGetErrorString(hipGetLastError())));
-      h->mirror = *h->hsmall;
-      h->sym_m = -1;
-      const HostMirror& hm = h->mirror;
-      if (chainPath && (hm.err & ERRF_CHAIN_CAP)) {
-        // C sized from the previous call was too small for this product (same shape and product count, more distinct
-        // columns): nothing was written out of bounds; forget the guess and compute the product the two-phase way
-        pool().release(dJC); pool().release(dC);
-        dJC = nullptr; dC = nullptr;
-        h->prev_m = -1; h->prev_nnzC = -1;
-        rc = symbolic_phase(h, dIA, dJA, nnzA, dIB, dJB, m, k, n, nullptr, dIC, &nnzC);
-        if (rc) return cleanup(rc);
-        if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
-            hipSuccess != pool().alloc((void**)&dC, sizeof(float) * (size_t)std::max(nnzC, 1)))
-          return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-        rc = numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
-        if (rc) return cleanup(rc);
-        *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
-        return SPGEMM_OK;
-      }
-#ifndef SMF_ABLATE
-      if (hm.err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken (flags=%d)", hm.err));
-#endif
-      if (hm.nnzC64 > 0x7fffffffULL) return cleanup(fail(SPGEMM_ERR_OVERFLOW, "nnz(C)=%llu does not fit int32 CSR", hm.nnzC64));
-      spgemm_stats& st = h->stats;
-      st.total_flops = (long long)hm.totalP;
-      st.nnzC = (int)hm.nnzC64;
-      for (int b = 0; b < NBINS; ++b) st.bin_rows[b] = hm.binPtr[b + 1] - hm.binPtr[b];
-      hipEventElapsedTime(&st.ms_classify, h->ev[0], h->ev[1]);
-      hipEventElapsedTime(&st.ms_symbolic, h->ev[1], h->ev[2]);
-      hipEventElapsedTime(&st.ms_scan_alloc, h->ev[2], h->ev[4]);
-      hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
-      hipEventElapsedTime(&st.ms_total, h->ev[0], h->ev[5]);
-      collect_kernel_times(h, true);
-      grow_bitmaps(h, n);
-      h->prev_m = m; h->prev_P = P; h->prev_nnzC = (long long)hm.nnzC64;
-      *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = (int)hm.nnzC64;
-      return SPGEMM_OK;
-    }
-    // P too large for a speculative allocation: finish the symbolic phase the two-phase way (kernels already queued)
-    if (chainPath) {
-      // (the one-pass path queued only the symbolic kernels of its counted rows: run the whole two-pass pipeline instead)
-      rc = symbolic_phase(h, dIA, dJA, nnzA, dIB, dJB, m, k, n, nullptr, dIC, &nnzC);
-      if (rc) return cleanup(rc);
-      h->prev_m = m; h->prev_P = P; h->prev_nnzC = nnzC;
-      if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
-          hipSuccess != pool().alloc((void**)&dC, sizeof(float) * (size_t)std::max(nnzC, 1)))
-        return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-      rc = numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
-      if (rc) return cleanup(rc);
-      *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
-      return SPGEMM_OK;
-    }
-    if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return cleanup(fail(SPGEMM_ERR_HIP, "symbolic phase failed: %s", hipGetErrorString(hipGetLastError())));
-    h->mirror = *h->hsmall;
-    if (h->mirror.err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in symbolic phase (flags=%d)", h->mirror.err));
-    if (h->mirror.nnzC64 > 0x7fffffffULL) return cleanup(fail(SPGEMM_ERR_OVERFLOW, "nnz(C)=%llu does not fit int32 CSR", h->mirror.nnzC64));
-    h->stats.total_flops = (long long)h->mirror.totalP;
-    h->stats.nnzC = (int)h->mirror.nnzC64;
-    for (int b = 0; b < NBINS; ++b) h->stats.bin_rows[b] = h->mirror.binPtr[b + 1] - h->mirror.binPtr[b];
-    hipEventElapsedTime(&h->stats.ms_classify, h->ev[0], h->ev[1]);
-    hipEventElapsedTime(&h->stats.ms_symbolic, h->ev[1], h->ev[2]);
-    hipEventElapsedTime(&h->stats.ms_scan_alloc, h->ev[2], h->ev[3]);
-    h->stats.ms_total = h->stats.ms_classify + h->stats.ms_symbolic + h->stats.ms_scan_alloc;
-    collect_kernel_times(h, true);
-    h->sym_m = m;
-    nnzC = (int)h->mirror.nnzC64;
-    h->prev_m = m; h->prev_P = P; h->prev_nnzC = nnzC;
-    if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
-        hipSuccess != pool().alloc((void**)&dC, sizeof(float) * (size_t)std::max(nnzC, 1)))
-      return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-    rc = numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
-    if (rc) return cleanup(rc);
-    *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
-    return SPGEMM_OK;
+  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * capC) || hipSuccess != pool().alloc((void**)&dC, sizeof(float) * capC))
+    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%llu entries) failed", P));
+  hipEventRecord(h->ev[4], s);
+  h->mirror = mid;                                     // bin sizes for the numeric launch grids
+  int rc = SPGEMM_OK;
+  if (o.chain) rc = launch_wbatch<WB_CHAIN>(h, p.m, p.IA, p.A, p.JB, p.B, dIC, dJC, dC, (long long)capC);
+  if (!rc && o.wb2 && P > 0) rc = launch_wbatch<WB_NUM>(h, p.m, p.IA, p.A, p.JB, p.B, dIC, dJC, dC, (long long)capC);
+  if (!rc && P > 0) rc = launch_numeric(h, p.IA, p.A, p.JB, p.B, p.n, h->cur_rowIds, mid.binPtr, dIC, dJC, dC, nullptr, 1, o.minBin, o.skipH1A);
+  if (rc) return cleanup(rc);
+  hipEventRecord(h->ev[5], s);
+  rc = read_mirror(h, "SpGEMM", kAblate ? ~0 : o.chain ? ERRF_CHAIN_CAP : 0);
+  if (rc != SPGEMM_ERR_HIP) h->sym_m = -1;             // the mirror of a pending symbolic phase is gone
+  if (rc) return cleanup(rc);
+  const HostMirror& hm = h->mirror;
+  if (o.chain && (hm.err & ERRF_CHAIN_CAP)) {          // (this condition misses overflows in rows above smallMax: ADVICE.md)
+    // C sized from the previous call was too small for this product (same shape and product count, more distinct
+    // columns): nothing was written out of bounds; forget the guess and compute the product the two-phase way
+    pool().release(dJC); pool().release(dC);
+    h->prev_m = -1; h->prev_nnzC = -1;
+    return two_phase(h, p, nullptr, dIC, out);
   }
-  int rc = symbolic_phase(h, dIA, dJA, nnzA, dIB, dJB, m, k, n, pre, dIC, &nnzC);
-  if (rc) return cleanup(rc);
-  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
-      hipSuccess != pool().alloc((void**)&dC, sizeof(float) * (size_t)std::max(nnzC, 1)))
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-  rc = numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
-  if (rc) return cleanup(rc);
-  *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
+  publish_stats(h, hm, StatsForm::OneShot);
+  grow_bitmaps(h, p.n);
+  h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = (long long)hm.nnzC64;
+  *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = (int)hm.nnzC64;
   return SPGEMM_OK;
+}
+
+// C = A*B in float, five routes:
+//   1 one-shot            C sized by P, one host sync at the end (the default)
+//   2 capacity redo       one-pass path only: C sized by the previous call was too small, two-phase pipeline from its start
+//   3 chain, P too large  the one-pass path queued only part of the symbolic kernels: two-phase pipeline from its start
+//   4 P too large         P > 2^30, or a product known to compress: the queued symbolic phase is finished, C sized exactly
+//   5 pre-classified      a caller's classification, or no rows: two-phase pipeline
+// prev_m/prev_P/prev_nnzC (allocation policy of the next call): set by routes 1, 3 and 4, reset by 2, left alone by 5.
+static int spgemm_device(spgemm_handle* h, const Product<float>& p, int nnzB, const PreClass* pre, const Result<float>& out) {
+  int* dIC = nullptr;
+  CHK(begin_product(&h, p, nnzB, out, &dIC));
+  if (pre || p.m == 0) return two_phase(h, p, pre, dIC, out);                                  // route 5
+  const OptInPath o = opt_in_path(h);
+  HostMirror mid;
+  int rc = one_shot_front(h, p, o, dIC, &mid);
+  if (rc) { pool().release(dIC); return rc; }
+  const unsigned long long P = mid.totalP;
+  // A product that compresses (real web graphs: nnz(C)/P ~ 0.5) would hold twice the memory it needs when sized by P.
+  // The handle remembers the previous call: the same shape and product count with nnz(C) < 3/4 P sends this call down
+  // the two-phase path (exact allocation, one more host round trip -- cheap next to the halved footprint).
+  const bool compressive = h->prev_m == p.m && h->prev_P == P && h->prev_nnzC >= 0 && (double)h->prev_nnzC < 0.75 * (double)P;
+  if (P <= (1ull << 30) && (!compressive || o.chain)) {
+    const size_t capC = compressive ? (size_t)std::max<long long>(h->prev_nnzC, 1ll) : (size_t)std::max<unsigned long long>(P, 1ull);
+    return one_shot_back(h, p, o, mid, capC, dIC, out);                                          // routes 1 and 2
+  }
+  int nnzC = 0;
+  rc = o.chain ? symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, nullptr, dIC, &nnzC)   // route 3
+               : finish_symbolic(h, p.m, &nnzC);                                                      // route 4
+  if (rc) { pool().release(dIC); return rc; }
+  h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = nnzC;
+  return finish_exact(h, p, nnzC, dIC, out);
 }
 
 extern "C" int hip_gpuSpMM(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
                            const int* dIB, const int* dJB, const float* dB, int nnzB, int m, int k, int n,
                            int** dIC, int** dJC, float** dC, int* nnzC) {
-  return spgemm_device(h, dIA, dJA, dA, nnzA, dIB, dJB, dB, nnzB, m, k, n, nullptr, dIC, dJC, dC, nnzC);
+  return spgemm_device(h, {dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n}, nnzB, nullptr, {dIC, dJC, dC, nnzC});
 }
 
 extern "C" int hip_spgemm_symbolic(spgemm_handle* h, const int* dIA, const int* dJA, int nnzA, const int* dIB,
@@ -1119,33 +1155,15 @@ extern "C" int hip_spgemm_numeric(spgemm_handle* h, const int* dIA, const int* d
   return numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
 }
 
-// double values: symbolic_phase -> scan/alloc -> f64 numeric (never the opt-in SPGEMM_PATH kernels)
+// double values: the two-phase pipeline with the f64 numeric launch (never the opt-in SPGEMM_PATH kernels)
 extern "C" int hip_gpuSpMM_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
                                const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
                                int** dICp, int** dJCp, double** dCp, int* nnzCp) {
-  if (!dICp || !dJCp || !dCp || !nnzCp) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dICp = nullptr; *dJCp = nullptr; *dCp = nullptr; *nnzCp = 0;
-  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
-  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
-  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  CHK(ws_ensure(h, m));
+  const Product<double> p{dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n};
+  const Result<double> out{dICp, dJCp, dCp, nnzCp};
   int* dIC = nullptr;
-  int* dJC = nullptr;
-  double* dC = nullptr;
-  auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
-  HIPCHK(pool().alloc((void**)&dIC, sizeof(int) * ((size_t)m + 1)));
-  int nnzC = 0;
-  int rc = symbolic_phase(h, dIA, dJA, nnzA, dIB, dJB, m, k, n, nullptr, dIC, &nnzC);
-  if (rc) return cleanup(rc);
-  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)std::max(nnzC, 1)) ||
-      hipSuccess != pool().alloc((void**)&dC, sizeof(double) * (size_t)std::max(nnzC, 1)))
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-  rc = numeric_phase_f64(h, dIA, dA, dJB, dB, m, dIC, dJC, dC);
-  if (rc) return cleanup(rc);
-  *dICp = dIC; *dJCp = dJC; *dCp = dC; *nnzCp = nnzC;
-  return SPGEMM_OK;
+  CHK(begin_product(&h, p, nnzB, out, &dIC));
+  return two_phase(h, p, nullptr, dIC, out);
 }
 
 extern "C" int hip_spgemm_numeric_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
@@ -1157,7 +1175,7 @@ extern "C" int hip_spgemm_numeric_f64(spgemm_handle* h, const int* dIA, const in
   CHK(check_common(dIA, dJA, dA, nnzA, "A"));
   CHK(check_common(dIB, dJB, dB, nnzB, "B"));
   HIPCHK(hipSetDevice(h->device));
-  return numeric_phase_f64(h, dIA, dA, dJB, dB, m, dIC, dJC, dC);
+  return numeric_phase(h, dIA, dJA, dA, dIB, dJB, dB, m, n, dIC, dJC, dC);
 }
 
 extern "C" int hip_csr_row_flops(spgemm_handle* h, const int* dIA, const int* dJA, const int* dIB, int m,
@@ -1173,8 +1191,7 @@ extern "C" int hip_csr_row_flops(spgemm_handle* h, const int* dIA, const int* dJ
   if (rc == SPGEMM_OK && m > 0 &&
       hipMemcpyAsync(dRowFlops, h->rowFlops, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
     rc = fail(SPGEMM_ERR_HIP, "copy of row flops failed");
-  if (rc == SPGEMM_OK && (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                          hipStreamSynchronize(h->stream) != hipSuccess))
+  if (rc == SPGEMM_OK && !fetch_mirror(h))
     rc = fail(SPGEMM_ERR_HIP, "row flops failed: %s", hipGetErrorString(hipGetLastError()));
   pool().release(tmpIC);
   if (rc) return rc;
@@ -1231,14 +1248,10 @@ extern "C" int hip_gpuFlopsClassify(spgemm_handle* h, const int* dIA, const int*
   } else {
     hipMemsetAsync(fl, 0, sizeof(int), s);
   }
-  if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return cleanup(fail(SPGEMM_ERR_HIP, "classify failed: %s", hipGetErrorString(hipGetLastError())));
+  if (!fetch_mirror(h)) return cleanup(fail(SPGEMM_ERR_HIP, "classify failed: %s", hipGetErrorString(hipGetLastError())));
   hv_from_binptr(h->hsmall->binPtr, hv, hv_len);
   if (total_flops) *total_flops = (long long)h->hsmall->totalP;
-  h->stats.total_flops = (long long)h->hsmall->totalP;
-  for (int b = 0; b < NBINS; ++b) h->stats.bin_rows[b] = h->hsmall->binPtr[b + 1] - h->hsmall->binPtr[b];
-  collect_kernel_times(h, true);
+  publish_stats(h, *h->hsmall, StatsForm::Classified);
   pool().release(tmpIC);
   *drowIds = ids;
   *dflops = fl;
@@ -1305,7 +1318,7 @@ extern "C" int hip_sgpuSpMM(spgemm_handle* h, const int* dIA, const int* dJA, co
                             const int* drowIds, const int hv[SPGEMM_HV_LEN], const int* dflops, int** dIC, int** dJC,
                             float** dC, int* nnzC) {
   PreClass pre{drowIds, hv, dflops};
-  return spgemm_device(h, dIA, dJA, dA, nnzA, dIB, dJB, dB, nnzB, m, k, n, &pre, dIC, dJC, dC, nnzC);
+  return spgemm_device(h, {dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n}, nnzB, &pre, {dIC, dJC, dC, nnzC});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1684,8 +1697,8 @@ static int rmcl_expand_prune_core(spgemm_handle* h, const int* dIA, const int* d
     if (dIBlen && (rc = rmcl_pack_rows(h, k, dIB, dIBlen, dJB, dB, &bI, &bJ, &bV, &bn))) return rc;
     int *cI = nullptr, *cJ = nullptr, cn = 0;
     float* cA = nullptr;
-    rc = spgemm_device(h, dIA, dJA, dA, nnzA, dIBlen ? bI : dIB, dIBlen ? bJ : dJB, dIBlen ? bV : dB, bn, m, k, n, nullptr,
-                       &cI, &cJ, &cA, &cn);
+    rc = spgemm_device(h, {dIA, dJA, dA, nnzA, dIBlen ? bI : dIB, dIBlen ? bJ : dJB, dIBlen ? bV : dB, m, k, n}, bn, nullptr,
+                       {&cI, &cJ, &cA, &cn});
     if (!rc) rc = rmcl_prune_impl(h, m, cn, cI, cJ, cA, dIN, dJN, dCN, nnzN);
     pool().release(cI); pool().release(cJ); pool().release(cA);
     pool().release(bI); pool().release(bJ); pool().release(bV);
@@ -1761,52 +1774,36 @@ static int rmcl_expand_prune_core(spgemm_handle* h, const int* dIA, const int* d
   if ((rc = launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, mid.binPtr, dIC, dJC, dC, cnt, nosym ? 2 : 1))) return cleanup(rc);
   hipEventRecord(h->ev[5], s);
   if ((pack || mode == RMCL_BLOCK) && (rc = launch_scan(h, cnt, m, &h->dsmall->kept64))) return cleanup(rc);
-  if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess)
-    return hipfail("numeric phase");
+  // the rows stay where the epilogues wrote them, as {start, end} pairs for the next classification (queued behind this kernel)
+  auto leave_extents = [&]() {
+    int2* se = nullptr;
+    if (hipSuccess != pool().alloc((void**)&se, sizeof(int2) * (size_t)m)) return hipfail("device allocation failed");
+    hipLaunchKernelGGL(k_zip_extents, dim3(cdiv(m, 256)), dim3(256), 0, s, m, dIC, cnt, se);
+    if (hipGetLastError() != hipSuccess) { pool().release(se); return hipfail("extent launch"); }
+    *dIN = dIC; *dLenN = cnt; *dSEN = se; *dJN = dJC; *dCN = dC; *nnzN = (int)P;
+    return SPGEMM_OK;
+  };
   if (mode == RMCL_EXTENTS && errPending && h->ktiming == 0) {
     // Loop form: nothing of this iteration is needed on the host before the next one starts -- its classification is
     // queued behind the numeric kernels, and the error flags are looked at after that classification's event (above).
     // The host runs ahead and the GPU does not idle between iterations.  (With per-kernel timing on, the events have to
     // be read now: the call waits as before.)
-    int2* se = nullptr;
-    if (hipSuccess != pool().alloc((void**)&se, sizeof(int2) * (size_t)m)) return hipfail("device allocation failed");
-    hipLaunchKernelGGL(k_zip_extents, dim3(cdiv(m, 256)), dim3(256), 0, s, m, dIC, cnt, se);
-    if (hipGetLastError() != hipSuccess) { pool().release(se); return hipfail("extent launch"); }
-    spgemm_stats& st0 = h->stats;
-    st0.total_flops = (long long)mid.totalP;
-    st0.nnzC = -1;
-    for (int b = 0; b < NBINS; ++b) st0.bin_rows[b] = mid.binPtr[b + 1] - mid.binPtr[b];
+    if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess)
+      return hipfail("numeric phase");                 // (read_mirror's copy without its wait)
+    if ((rc = leave_extents())) return rc;
+    publish_stats(h, mid, StatsForm::CountsOnly);
     *errPending = true;
-    *dIN = dIC; *dLenN = cnt; *dSEN = se; *dJN = dJC; *dCN = dC; *nnzN = (int)P;
     return SPGEMM_OK;
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return hipfail("numeric phase");
-  h->mirror = *h->hsmall;
+  if ((rc = read_mirror(h, "rmcl expand+prune"))) return cleanup(rc);
   const HostMirror& hm = h->mirror;
-  if (hm.err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken (flags=%d)", hm.err));
-  spgemm_stats& st = h->stats;
-  st.total_flops = (long long)hm.totalP;
-  st.nnzC = nosym ? -1 : (int)std::min<unsigned long long>(hm.nnzC64, 0x7fffffffULL);   // not computed without the symbolic pass
-  for (int b = 0; b < NBINS; ++b) st.bin_rows[b] = hm.binPtr[b + 1] - hm.binPtr[b];
-  hipEventElapsedTime(&st.ms_classify, h->ev[0], h->ev[1]);
-  hipEventElapsedTime(&st.ms_symbolic, h->ev[1], h->ev[2]);
-  hipEventElapsedTime(&st.ms_scan_alloc, h->ev[2], h->ev[4]);
-  hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
-  hipEventElapsedTime(&st.ms_total, h->ev[0], h->ev[5]);
-  collect_kernel_times(h, true);
+  publish_stats(h, hm, nosym ? StatsForm::OneShotNoNnz : StatsForm::OneShot);
   grow_bitmaps(h, n);
   if (mode == RMCL_BLOCK) {                          // scratch rows + the row pointer of the packed block
     *dIN = dIC; *dLenN = cnt; *dJN = dJC; *dCN = dC; *nnzN = (int)hm.kept64;
     return SPGEMM_OK;
   }
-  if (!pack) {                                       // the rows stay where the epilogues wrote them
-    int2* se = nullptr;
-    if (hipSuccess != pool().alloc((void**)&se, sizeof(int2) * (size_t)m)) return hipfail("device allocation failed");
-    hipLaunchKernelGGL(k_zip_extents, dim3(cdiv(m, 256)), dim3(256), 0, s, m, dIC, cnt, se);
-    if (hipGetLastError() != hipSuccess) { pool().release(se); return hipfail("extent launch"); }
-    *dIN = dIC; *dLenN = cnt; *dSEN = se; *dJN = dJC; *dCN = dC; *nnzN = (int)P;
-    return SPGEMM_OK;                                // stream order: the next classification runs behind the kernel
-  }
+  if (!pack) return leave_extents();
   const int nz = (int)hm.kept64;                     // <= nnz(C) <= P <= 2^30
   if (hipSuccess != pool().alloc((void**)&JN, sizeof(int) * (size_t)std::max(nz, 1)) ||
       hipSuccess != pool().alloc((void**)&CN, sizeof(float) * (size_t)std::max(nz, 1)))

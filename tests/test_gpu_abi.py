@@ -254,3 +254,95 @@ def test_compressive_product_is_not_held_at_twice_its_size():
     dA.deviceDispose()
     dB.deviceDispose()
     h.close()
+
+
+def _with_two_preset_rows(A):
+    """A plus one empty row and one row whose only entry points at itself (one product): square, two rows larger."""
+    m = A.rows
+    rp = np.concatenate([A.rowPtr, [A.nnz, A.nnz + 1]]).astype(np.int32)
+    ci = np.concatenate([A.colInd, [m + 1]]).astype(np.int32)
+    v = np.concatenate([A.values, [1.0]]).astype(np.float32)
+    return po.CSRHost(rp, ci, v, m + 2, m + 2)
+
+
+def test_stats_agree_across_routes(monkeypatch):
+    """Every route through the host pipeline publishes the same counts for the same product, and its own, documented notion
+    of the phase times.  C = A*A on a power-law matrix whose rows fill every bin (plus an empty row and a one-product row
+    for the two preset bins), through: (a) the one-shot call, twice; (b) symbolic + numeric; (c) caller's classification +
+    hip_sgpuSpMM; (d) double values; (e) SPGEMM_PATH=1; (f) SPGEMM_PATH=2.  nnzC and bin_rows agree with the CPU oracle
+    everywhere; total_flops too, except on (c), where it is 0 (the caller's classification carries no product total).
+    The two-phase routes (b, c, d) report ms_total as the float sum of the four parts; the one-shot routes (a, e, f) report
+    elapsed time, which is at least each part."""
+    A = _with_two_preset_rows(synth_csr(8192, 5, 2))
+    m = A.rows
+    want = po.omp_spmm(A, A)
+    flops = np.asarray(po.row_flops(A, A), dtype=np.int64)
+    P = int(flops.sum())
+    bins = np.bincount(np.searchsorted([0, 1, 4, 16, 64, 512, 2048, 4096], flops), minlength=9).tolist()
+    assert all(b > 0 for b in bins) and bins[0] == 1 and bins[1] == 1, bins
+    assert want.nnz > 0.75 * P                              # (a)'s second call stays on the one-shot route
+    monkeypatch.delenv("SPGEMM_PATH", raising=False)
+    monkeypatch.delenv("SPGEMM_CHAIN_CFG", raising=False)
+    dA = to_hs(A).toGpuCSR()
+    args = (dA.rowPtr, dA.colInd, dA.values, A.nnz)
+    stats = {}
+
+    def one_shot(h, calls):
+        for _ in range(calls):
+            hs.gpuSpMMWrapper(dA, dA, h).deviceDispose()
+        return h.stats()
+
+    h = hs.Handle(0)
+    stats["a"] = one_shot(h, 2)
+    h.close()
+
+    h = hs.Handle(0)
+    dIC = hs.dev_alloc(4 * (m + 1))
+    nnz = hs.spgemm_symbolic_raw(h, dA.rowPtr, dA.colInd, A.nnz, dA.rowPtr, dA.colInd, A.nnz, m, m, m, dIC)
+    assert nnz == want.nnz
+    dJC, dC = hs.dev_alloc(4 * nnz), hs.dev_alloc(4 * nnz)
+    hs.spgemm_numeric_raw(h, *args, *args, m, m, m, dIC, dJC, dC)
+    stats["b"] = h.stats()
+    for p in (dIC, dJC, dC):
+        hs.dev_free(p)
+    h.close()
+
+    h = hs.Handle(0)
+    hv, _, ids, fl, tot = hs.gpuFlopsClassify(dA, dA, h)
+    assert tot == P
+    hs.sgpuSpMMWrapper(dA, dA, ids, hv, fl, h).deviceDispose()
+    stats["c"] = h.stats()
+    hs.dev_free(ids)
+    hs.dev_free(fl)
+    h.close()
+
+    h = hs.Handle(0)
+    dV64 = hs.h2d(A.values.astype(np.float64))
+    args64 = (dA.rowPtr, dA.colInd, dV64, A.nnz)
+    ic, jc, cv, nnz = hs.gpu_spmm_raw_f64(h, *args64, *args64, m, m, m)
+    assert nnz == want.nnz
+    stats["d"] = h.stats()
+    for p in (ic, jc, cv, dV64):
+        hs.dev_free(p)
+    h.close()
+
+    for route, path in (("e", 1), ("f", 2)):
+        monkeypatch.setenv("SPGEMM_PATH", str(path))
+        h = hs.Handle(0)                                    # the handle reads its path when it is made
+        stats[route] = one_shot(h, 1)
+        h.close()
+    dA.deviceDispose()
+
+    parts = ("ms_classify", "ms_symbolic", "ms_scan_alloc", "ms_numeric")
+    for route in sorted(stats):
+        st = stats[route]
+        print(route, {k: st[k] for k in ("total_flops", "nnzC", "bin_rows", "ms_total") + parts})
+    for route, st in sorted(stats.items()):
+        assert st["nnzC"] == want.nnz, route
+        assert st["bin_rows"] == bins, route
+        assert st["total_flops"] == (0 if route == "c" else P), route
+        assert st["ms_numeric"] > 0 and st["ms_total"] >= st["ms_numeric"], route
+        if route in "bcd":
+            assert st["ms_total"] == pytest.approx(sum(st[k] for k in parts), rel=1e-5), route
+        else:
+            assert all(st["ms_total"] >= st[k] for k in parts), route
