@@ -1613,7 +1613,9 @@ struct BigHashShared {
   int spillCnt[BH_MAXCLS];
   int emitted;
   int ovf;                       // a parking region overflowed: redo the row without parking
+  int full;                      // a hash class outgrew the table: redo the row with more, better mixed classes
 };
+static_assert(sizeof(BigHashShared) <= 160 * 1024, "k_num_bighash: more LDS than a CU has");
 
 __device__ __forceinline__ int block_sum_16(int v, int* red) {
   const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -1799,6 +1801,23 @@ __global__ __launch_bounds__(BIG_THREADS) void k_num_big(const int* __restrict__
 __device__ __forceinline__ unsigned bh_class(int col, unsigned npass) {
   return ((((unsigned)col * 0x85ebca6bu) >> 16) * npass) >> 16;     // second hash, independent of the slot hash
 }
+// One multiplication cannot spread every input: the columns i*s of a banded or grid row are an arithmetic progression, and
+// for some strides s (5599 and its small multiples, 509, ...) the products s*0x85ebca6b stay in a narrow range of the top 16
+// bits, so that ALL of them land in one class, whatever npass.  A class that outgrows the table is noticed by the block
+// (BigHashShared::full) and the row is redone with twice the classes, cut by this full avalanche mixer (murmur3's
+// finaliser) salted with the attempt, BH_RETRIES times at most before the call fails.  The first attempt keeps the cheap
+// function: it is on the hot path of every multi-pass row, and real rows pass it.
+// Cost of a failed attempt: the flag is read at the end of the pass, and until then every trip that brings a column the full
+// table cannot take probes all of its slots before it gives up, so a resonant row pays its walk several times over before
+// the redo (milliseconds for a row of 300 000 columns; DESIGN.md 2b has the measured test times).  Rows that fit never enter
+// that loop.  The state after the last retry has failed too (ERRF_TABLE_FULL, and ERRF_COUNT_MISMATCH because the emitted
+// counter was reset) needs an input built against the salted mixer: no test reaches it.
+constexpr int BH_RETRIES = 3;
+__device__ __forceinline__ unsigned bh_class_mixed(int col, unsigned npass, int attempt) {
+  unsigned x = (unsigned)col ^ ((unsigned)attempt * 0x9e3779b9u);
+  x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
+  return __umulhi(x, npass);
+}
 
 #ifdef SMF_STAMPS
 // diagnostic build: cycles of wave 0 of every block, summed per phase of k_num_bighash (read with spgemm_hip_debug_stamps)
@@ -1839,107 +1858,129 @@ __global__ __launch_bounds__(BIG_THREADS) void k_num_bighash(const int* __restri
     const int outBase = cur.x0;
     const int outEnd = cur.x1;
     const int want = outEnd - outBase;
-    const unsigned npass = (unsigned)((want + bhCap - 1) / bhCap);
-    // class c >= 1 parks in its own region of `stride` pairs: the expected class size (the classes are a hash of the
-    // column, so products/npass) plus a margin.  A class that outgrows its region raises sh.ovf and the row is redone
-    // the slow way (one walk per pass) -- rare, and never wrong.
+    unsigned classes = (unsigned)((want + bhCap - 1) / bhCap);
     const int flops = cur.x2;
-    const int stride = (int)min((long long)flops, (long long)flops * marginPct / (100ll * (long long)npass) + 256ll);
-    const bool canSpill = npass > 1 && npass <= (unsigned)BH_MAXCLS && park != nullptr &&
-                          (long long)(npass - 1) * stride <= (long long)spillCap;
-    const int perPass = (want + (int)npass - 1) / (int)npass;
-    // any multiple of 1024 slots: FOUR times the distinct columns of a pass when that fits (2x / 3x / 4x: 0.845 / 0.832 /
-    // 0.830 ms -- the lock-step probe loop pays for the longest chain of its 128 products, see table_size)
-    const int size = min(BH_SLOTS, max(BIG_THREADS, (4 * perPass + BIG_THREADS - 1) / BIG_THREADS * BIG_THREADS));
-    const int shift = 0;
-    const int per = size / BIG_NW;
-    bool useSpill = canSpill;
     STAMP(0)
-    for (unsigned pass = 0; pass < npass;) {
-      clear_slots(sh.tab, size, tid, BIG_THREADS);
-      if (pass == 0 && tid < BH_MAXCLS) sh.spillCnt[tid] = 0;
-      if (pass == 0 && tid == 0) { sh.emitted = 0; sh.ovf = 0; }
-      __syncthreads();
-      STAMP(1)
-      if (pass == 0 || !useSpill) {
-        for_each_product<BIG_NW, BH_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
-                                              [&](const bool (&act)[BH_U], const int (&col)[BH_U], const float (&val)[BH_U], int) {
-          STAMP_IN(ti_)
-          bool mine[BH_U];
-          unsigned cls[BH_U];
+    // One attempt at the row with `npass` classes; true when a class held more columns than the table has slots (sh.full).
+    // RETRY (a type, so that the first attempt compiles to the code it always was and the redo sits beside it, cold): the
+    // classes are cut by bh_class_mixed and the table is used whole.
+    auto attempt_row = [&](auto retry, const unsigned npass, const int attempt) -> bool {
+      constexpr bool RETRY = decltype(retry)::value;
+      // class c >= 1 parks in its own region of `stride` pairs: the expected class size (the classes are a hash of the
+      // column, so products/npass) plus a margin.  A class that outgrows its region raises sh.ovf and the row is redone
+      // the slow way (one walk per pass) -- rare, and never wrong.
+      const int stride = (int)min((long long)flops, (long long)flops * marginPct / (100ll * (long long)npass) + 256ll);
+      const bool canSpill = npass > 1 && npass <= (unsigned)BH_MAXCLS && park != nullptr &&
+                            (long long)(npass - 1) * stride <= (long long)spillCap;
+      const int perPass = (want + (int)npass - 1) / (int)npass;
+      // any multiple of 1024 slots: FOUR times the distinct columns of a pass when that fits (2x / 3x / 4x: 0.845 / 0.832 /
+      // 0.830 ms -- the lock-step probe loop pays for the longest chain of its 128 products, see table_size); a redone row
+      // takes the whole table
+      const int size = RETRY ? BH_SLOTS : min(BH_SLOTS, max(BIG_THREADS, (4 * perPass + BIG_THREADS - 1) / BIG_THREADS * BIG_THREADS));
+      const int shift = 0;
+      const int per = size / BIG_NW;
+      bool useSpill = canSpill;
+      bool full = false;
+      for (unsigned pass = 0; pass < npass;) {
+        clear_slots(sh.tab, size, tid, BIG_THREADS);
+        if (pass == 0 && tid < BH_MAXCLS) sh.spillCnt[tid] = 0;
+        if (pass == 0 && tid == 0) { sh.emitted = 0; sh.ovf = 0; sh.full = 0; }
+        __syncthreads();
+        STAMP(1)
+        if (pass == 0 || !useSpill) {
+          for_each_product<BIG_NW, BH_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
+                                                [&](const bool (&act)[BH_U], const int (&col)[BH_U], const float (&val)[BH_U], int) {
+            STAMP_IN(ti_)
+            bool mine[BH_U];
+            unsigned cls[BH_U];
 #pragma unroll
-          for (int u = 0; u < BH_U; ++u) {
-            cls[u] = npass == 1 ? 0u : bh_class(col[u], npass);
-            mine[u] = act[u] && cls[u] == pass;
-          }
-          hash_accum_multi<false>(sh.tab, size, shift, mine, col, val, &sh.st.dummy[lane_id()], err);
-          STAMP_OUT(3, ti_)
-          STAMP_IN(tp_)
-          if (useSpill) {                              // block-uniform; here pass == 0
-            for (unsigned c = 1; c < npass; ++c) {
-              unsigned long long mk[BH_U];
-              int total = 0;
+            for (int u = 0; u < BH_U; ++u) {
+              cls[u] = npass == 1 ? 0u : RETRY ? bh_class_mixed(col[u], npass, attempt) : bh_class(col[u], npass);
+              mine[u] = act[u] && cls[u] == pass;
+            }
+            hash_accum_multi<false>(sh.tab, size, shift, mine, col, val, &sh.st.dummy[lane_id()], &sh.full);
+            STAMP_OUT(3, ti_)
+            STAMP_IN(tp_)
+            if (useSpill) {                              // block-uniform; here pass == 0
+              for (unsigned c = 1; c < npass; ++c) {
+                unsigned long long mk[BH_U];
+                int total = 0;
 #pragma unroll
-              for (int u = 0; u < BH_U; ++u) { mk[u] = ballot64(act[u] && cls[u] == c); total += __popcll(mk[u]); }
-              if (total) {                             // wave-uniform
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&sh.spillCnt[c], total);
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (base + total > stride) {           // wave-uniform: region full, the row will be redone
-                  if (lane == 0) sh.ovf = 1;
-                } else {
-                  int2* const dst = park + (size_t)(c - 1) * (size_t)stride;
+                for (int u = 0; u < BH_U; ++u) { mk[u] = ballot64(act[u] && cls[u] == c); total += __popcll(mk[u]); }
+                if (total) {                             // wave-uniform
+                  int base = 0;
+                  if (lane == 0) base = atomicAdd(&sh.spillCnt[c], total);
+                  base = __builtin_amdgcn_readfirstlane(base);
+                  if (base + total > stride) {           // wave-uniform: region full, the row will be redone
+                    if (lane == 0) sh.ovf = 1;
+                  } else {
+                    int2* const dst = park + (size_t)(c - 1) * (size_t)stride;
 #pragma unroll
-                  for (int u = 0; u < BH_U; ++u) {
-                    if (act[u] && cls[u] == c) dst[base + mask_rank(mk[u])] = make_int2(col[u], __float_as_int(val[u]));
-                    base += __popcll(mk[u]);
+                    for (int u = 0; u < BH_U; ++u) {
+                      if (act[u] && cls[u] == c) dst[base + mask_rank(mk[u])] = make_int2(col[u], __float_as_int(val[u]));
+                      base += __popcll(mk[u]);
+                    }
                   }
                 }
               }
             }
+            STAMP_OUT(4, tp_)
+          });
+          STAMP(2)
+          if (pass == 0 && useSpill && sh.ovf) {        // block-uniform (read after the walk's closing barrier)
+            __syncthreads();                             // everyone has seen the flag before it is reset
+            useSpill = false;
+            continue;                                    // pass 0 again, without parking: table and counters are reset
           }
-          STAMP_OUT(4, tp_)
-        });
-        STAMP(2)
-        if (pass == 0 && useSpill && sh.ovf) {        // block-uniform (read after the walk's closing barrier)
-          __syncthreads();                             // everyone has seen the flag before it is reset
-          useSpill = false;
-          continue;                                    // pass 0 again, without parking: table and counters are reset
+        } else {
+          // stream this class's parked pairs; the next batch is in flight while the current one is inserted
+          const int cnt = sh.spillCnt[pass];            // written in pass 0, read-only since its closing barrier
+          const int2* const src = park + (size_t)(pass - 1) * (size_t)stride;
+          int2 nxt[BH_U];
+#pragma unroll
+          for (int u = 0; u < BH_U; ++u) { const int idx = u * BIG_THREADS + tid; nxt[u] = src[idx < cnt ? idx : 0]; }
+          for (int i0 = 0; i0 < cnt; i0 += BIG_THREADS * BH_U) {
+            bool mine[BH_U];
+            int col[BH_U];
+            float val[BH_U];
+#pragma unroll
+            for (int u = 0; u < BH_U; ++u) {
+              col[u] = nxt[u].x;
+              val[u] = __int_as_float(nxt[u].y);
+              mine[u] = i0 + u * BIG_THREADS + tid < cnt;
+            }
+#pragma unroll
+            for (int u = 0; u < BH_U; ++u) {
+              const int idx = i0 + BIG_THREADS * BH_U + u * BIG_THREADS + tid;
+              nxt[u] = src[idx < cnt ? idx : 0];
+            }
+            hash_accum_multi<false>(sh.tab, size, shift, mine, col, val, &sh.st.dummy[lane_id()], &sh.full);
+          }
+          __syncthreads();
+          STAMP(5)
         }
-      } else {
-        // stream this class's parked pairs; the next batch is in flight while the current one is inserted
-        const int cnt = sh.spillCnt[pass];            // written in pass 0, read-only since its closing barrier
-        const int2* const src = park + (size_t)(pass - 1) * (size_t)stride;
-        int2 nxt[BH_U];
-#pragma unroll
-        for (int u = 0; u < BH_U; ++u) { const int idx = u * BIG_THREADS + tid; nxt[u] = src[idx < cnt ? idx : 0]; }
-        for (int i0 = 0; i0 < cnt; i0 += BIG_THREADS * BH_U) {
-          bool mine[BH_U];
-          int col[BH_U];
-          float val[BH_U];
-#pragma unroll
-          for (int u = 0; u < BH_U; ++u) {
-            col[u] = nxt[u].x;
-            val[u] = __int_as_float(nxt[u].y);
-            mine[u] = i0 + u * BIG_THREADS + tid < cnt;
-          }
-#pragma unroll
-          for (int u = 0; u < BH_U; ++u) {
-            const int idx = i0 + BIG_THREADS * BH_U + u * BIG_THREADS + tid;
-            nxt[u] = src[idx < cnt ? idx : 0];
-          }
-          hash_accum_multi<false>(sh.tab, size, shift, mine, col, val, &sh.st.dummy[lane_id()], err);
+        if (sh.full) {                                   // block-uniform (every insert of the pass is behind a barrier)
+          __syncthreads();                               // everyone has seen the flag before the next attempt resets it
+          full = true;
+          break;
         }
+        // compaction: wave w emits the slots [w*per, w*per+per); its share of the row's output range comes from one
+        // LDS atomic (the counter runs on across the passes of a row)
+        emit_claimed<BH_SLOTS / BIG_NW / WAVE>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
         __syncthreads();
-        STAMP(5)
+        STAMP(6)
+        ++pass;
       }
-      // compaction: wave w emits the slots [w*per, w*per+per); its share of the row's output range comes from one
-      // LDS atomic (the counter runs on across the passes of a row)
-      emit_claimed<BH_SLOTS / BIG_NW / WAVE>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
-      __syncthreads();
-      STAMP(6)
-      ++pass;
+      return full;
+    };
+    // The row as planned; if a class outgrew the table, again with twice the classes and the mixed class function, a few
+    // times at most.  The row's output range is its own, so what the passes of a failed attempt wrote is written again.
+    bool full = attempt_row(std::false_type{}, classes, 0);
+    for (int attempt = 1; full && attempt <= BH_RETRIES; ++attempt) {
+      classes *= 2;
+      full = attempt_row(std::true_type{}, classes, attempt);
     }
+    if (full && tid == 0) atomicOr(err, ERRF_TABLE_FULL);
     if (tid == 0 && sh.emitted != want) atomicOr(err, ERRF_COUNT_MISMATCH);
     __syncthreads();
     cur = nxt;

@@ -320,14 +320,18 @@ def test_big_rows_multi_window_and_rank_passes():
 
 def test_big_rows_wider_than_one_symbolic_window():
     """B with 2.5 M columns: the symbolic bitmap kernel covers 1 M columns per window, so rows above 4096 products
-    take three windows; the numeric side is the multi-pass LDS hash (one pass, parked passes, and the re-walk fallback
-    for a row with more hash classes than parking regions)."""
+    take three windows; the numeric side is the multi-pass LDS hash (one pass, parked passes, and the re-walk fallback).
+    The hash kernel takes BH_CAP = 11 264 distinct columns per pass and parks the later classes of up to BH_MAXCLS = 32
+    passes, BH_SPILL = 262 144 products in all: the 3900-entry row (some 230 000 products, 15 or more passes) reaches
+    the re-walk because its parked products outgrow that buffer, not for its number of classes (that edge, more than
+    32 * 11 264 columns, is pinned by tests/test_gpu_edges.py)."""
     rng = np.random.default_rng(17)
     k, n = 4000, 2500000
     B = _rows_csr([np.sort(rng.choice(n, size=int(rng.integers(30, 90)), replace=False)) for _ in range(k)], n, 5)
     A = _rows_csr([rng.choice(k, size=s, replace=False) for s in (120, 300, 0, 1100, 75, 3900)], k, 6)
     want = po.sequential_spmm(A, B)
-    assert np.diff(want.rowPtr).max() > 16 * 10240        # more classes than BH_MAXCLS regions -> fallback path
+    assert np.diff(want.rowPtr).max() > 16 * 10240        # 163 840 columns = 15 passes of BH_CAP or more: the parked
+                                                          # products outgrow BH_SPILL (16 * 10 240: the former constants)
     assert_parity(hip_mul(A, B), want, what="wide-B big rows")
 
 
