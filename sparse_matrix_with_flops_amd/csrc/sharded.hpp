@@ -82,11 +82,6 @@ __global__ void k_offset_copy(int n, const int* __restrict__ src, int off, int* 
   if (i < n) dst[i] = src[i] + off;
 }
 
-struct DevCSR {                                   // a device CSR owned by the pool of `device`
-  int* I = nullptr; int* J = nullptr; float* V = nullptr;
-  int rows = 0, cols = 0, nnz = 0;
-};
-
 }  // namespace
 
 struct spgemm_shard {
@@ -340,9 +335,8 @@ static int upload_csr(int device, const int* I, const int* J, const float* V, in
   const int rows = r1 - r0;
   const int base = I[r0], nnz = I[r1] - base;
   out->rows = rows; out->cols = cols; out->nnz = nnz;
-  HIPCHK(pool().alloc((void**)&out->I, sizeof(int) * ((size_t)rows + 1)));
-  HIPCHK(pool().alloc((void**)&out->J, sizeof(int) * (size_t)std::max(nnz, 1)));
-  HIPCHK(pool().alloc((void**)&out->V, sizeof(float) * (size_t)std::max(nnz, 1)));
+  HIPCHK(out->I.alloc((size_t)rows + 1));
+  HIPCHK(out->alloc_entries(nnz));
   std::vector<int> rp((size_t)rows + 1);
   for (int i = 0; i <= rows; ++i) rp[i] = I[r0 + i] - base;
   HIPCHK(hipMemcpy(out->I, rp.data(), sizeof(int) * ((size_t)rows + 1), hipMemcpyHostToDevice));
@@ -351,11 +345,6 @@ static int upload_csr(int device, const int* I, const int* J, const float* V, in
     HIPCHK(hipMemcpy(out->V, V + base, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
   }
   return SPGEMM_OK;
-}
-static void free_csr(int device, DevCSR* c) {
-  hipSetDevice(device);
-  pool().release(c->I); pool().release(c->J); pool().release(c->V);
-  c->I = c->J = nullptr; c->V = nullptr; c->nnz = 0;
 }
 
 // per-rank entry counts -> every rank knows all of them.  In-process: they are all in this process's memory.
@@ -540,9 +529,8 @@ extern "C" int hip_sharded_spmm_destroy(spgemm_sharded* job) {
   for (size_t i = 0; i < job->loc.size(); ++i) {
     const int dev = job->g->sh[i].device;
     auto& L = job->loc[i];
-    free_csr(dev, &L.A);
-    free_csr(dev, &L.B);
     hipSetDevice(dev);
+    L.A.reset(); L.B.reset();
     pool().release(L.lIC); pool().release(L.gI); pool().release(L.gJ); pool().release(L.gV);
   }
   delete job;
@@ -634,7 +622,7 @@ extern "C" int hip_sharded_spmm_step(spgemm_sharded* job, int gather, long long*
     HIPCHK(hipSetDevice(s.device));
     const long long off = doGather ? offs[(size_t)s.grank] : 0;
     CHK(ensure_cap(L, (size_t)std::max<long long>(doGather ? total : localNnz[i], 1)));
-    CHK(numeric_phase(s.h, L.A.I, L.A.J, L.A.V, L.B.I, L.B.J, L.B.V, L.A.rows, job->n, L.lIC, L.gJ + off, L.gV + off));
+    CHK(numeric_phase(s.h, L.A.I, L.A.J, L.A.V.p, L.B.I, L.B.J, L.B.V.p, L.A.rows, job->n, L.lIC, L.gJ + off, L.gV + off));
     const int r0 = doGather ? job->ends[s.grank] : 0;
     const int cnt = L.A.rows + ((!doGather || s.grank == G - 1) ? 1 : 0);
     clear_stale_hip_error();
@@ -717,37 +705,26 @@ struct spgemm_sharded_rmcl {
   spgemm_group* g = nullptr;
   int rows = 0, cols = 0;
   std::vector<int> ends;
-  struct MtBuf { int* I = nullptr; int* J = nullptr; float* V = nullptr; size_t cap = 0; int nnz = 0; };
+  struct MtBuf { DevBuf<int> I, J; DevBuf<float> V; size_t cap = 0; int nnz = 0;
+                 CsrView view() const { return {I, J, V, nnz}; } };
   struct Local {
     DevCSR Mg;                                    // this shard's row block of Mgt
     DevCSR Mt0;                                   // replica of the initial Mt (every run starts from it)
     MtBuf buf[2];                                 // the replicated Mt of the current / next iteration
-    // one iteration's block, between its two phases
-    int* sI = nullptr; int* sPtr = nullptr; int* sJ = nullptr; float* sV = nullptr;   // scratch rows + packed row pointer
-    bool packed = false;                          // the step gave up on the fused form: (sI, sJ, sV) is a packed block
-    int kept = 0;
-  };
+    DevCSR blk;                                   // one iteration's block between its two phases: block form (nnz = kept
+  };                                              // entries), or packed when the step gave up on the fused form
   std::vector<Local> loc;
   int cur = -1;                                   // buf index holding the result of the last run, -1 = the initial Mt
   std::vector<long long> iterNnz;                 // nnz(Mt) after every iteration of the last run
 };
 
-static void rmcl_release_block(spgemm_sharded_rmcl::Local& L) {
-  pool().release(L.sI); pool().release(L.sPtr); pool().release(L.sJ); pool().release(L.sV);
-  L.sI = L.sPtr = L.sJ = nullptr; L.sV = nullptr; L.packed = false; L.kept = 0;
-}
-
 extern "C" int hip_sharded_rmcl_destroy(spgemm_sharded_rmcl* job) {
   if (!job) return SPGEMM_OK;
   for (size_t i = 0; i < job->loc.size(); ++i) {
     const int dev = job->g->sh[i].device;
-    auto& L = job->loc[i];
-    free_csr(dev, &L.Mg);
-    free_csr(dev, &L.Mt0);
     hipSetDevice(dev);
     hipStreamSynchronize(job->g->sh[i].h->stream);
-    rmcl_release_block(L);
-    for (auto& b : L.buf) { pool().release(b.I); pool().release(b.J); pool().release(b.V); }
+    job->loc[i] = spgemm_sharded_rmcl::Local();   // every block of the shard goes back, behind the drained stream
   }
   delete job;
   return SPGEMM_OK;
@@ -783,13 +760,12 @@ extern "C" int hip_sharded_rmcl_create(spgemm_group* g, int rows, int cols, cons
 }
 
 static int rmcl_ensure_buf(spgemm_sharded_rmcl::MtBuf& b, int rows, size_t entries) {
-  if (!b.I) HIPCHK(pool().alloc((void**)&b.I, sizeof(int) * ((size_t)rows + 1)));
+  if (!b.I) HIPCHK(b.I.alloc((size_t)rows + 1));
   if (entries <= b.cap && b.J) return SPGEMM_OK;
-  pool().release(b.J); pool().release(b.V);
-  b.J = nullptr; b.V = nullptr; b.cap = 0;
+  b.J.reset(); b.V.reset(); b.cap = 0;
   const size_t cap = entries + entries / 8 + 1024;
-  HIPCHK(pool().alloc((void**)&b.J, sizeof(int) * cap));
-  HIPCHK(pool().alloc((void**)&b.V, sizeof(float) * cap));
+  HIPCHK(b.J.alloc(cap));
+  HIPCHK(b.V.alloc(cap));
   b.cap = cap;
   return SPGEMM_OK;
 }
@@ -808,7 +784,7 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
     for (size_t i = 0; i < job->loc.size(); ++i) {
       hipSetDevice(g->sh[i].device);
       hipStreamSynchronize(g->sh[i].h->stream);
-      rmcl_release_block(job->loc[i]);
+      job->loc[i].blk.reset();
     }
     job->cur = -1;
     return fail(rc, "%s", msg.c_str());
@@ -820,15 +796,10 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
       spgemm_shard& s = g->sh[i];
       auto& L = job->loc[i];
       HIPCHK(hipSetDevice(s.device));
-      const int* bI = cur < 0 ? L.Mt0.I : L.buf[cur].I;
-      const int* bJ = cur < 0 ? L.Mt0.J : L.buf[cur].J;
-      const float* bV = cur < 0 ? L.Mt0.V : L.buf[cur].V;
-      const int bn = cur < 0 ? L.Mt0.nnz : L.buf[cur].nnz;
-      int2* se = nullptr;
-      CHK(rmcl_expand_prune_core(s.h, L.Mg.I, L.Mg.J, L.Mg.V, L.Mg.nnz, bI, nullptr, nullptr, bJ, bV, bn, L.Mg.rows, cols, cols,
-                                 RMCL_BLOCK, &L.sI, &L.sPtr, &se, &L.sJ, &L.sV, &L.kept));
-      L.packed = L.sPtr == nullptr;               // (no rows / no products / product too large: a packed block came back)
-      localNnz[i] = L.kept;
+      const CsrView Mt = cur < 0 ? L.Mt0.view() : L.buf[cur].view();
+      // (no rows / no products / product too large: a packed block comes back, L.blk.packed())
+      CHK(rmcl_expand_prune_core(s.h, L.Mg.view(), Mt, L.Mg.rows, cols, cols, RMCL_BLOCK, &L.blk));
+      localNnz[i] = L.blk.nnz;
       return SPGEMM_OK;
     });
     const std::string msgA = rcA ? spgemm_hip_last_error() : "";
@@ -852,6 +823,7 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
     const int rcB = for_each_shard(g, [&](int i) -> int {
       spgemm_shard& s = g->sh[i];
       auto& L = job->loc[i];
+      const DevCSR& K = L.blk;
       HIPCHK(hipSetDevice(s.device));
       auto& N = L.buf[nxt];
       CHK(rmcl_ensure_buf(N, m, (size_t)std::max<long long>(total, 1)));
@@ -861,19 +833,14 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
       const int cnt = ml + (s.grank == G - 1 ? 1 : 0);
       hipStream_t st = s.h->stream;
       clear_stale_hip_error();
-      const int* ptr = L.packed ? L.sI : L.sPtr;      // row pointer of the packed block (ml + 1 entries)
-      if (cnt > 0) hipLaunchKernelGGL(k_offset_copy, dim3(cdiv(cnt, 256)), dim3(256), 0, st, cnt, ptr, (int)off, N.I + ends[s.grank]);
-      if (L.kept > 0) {
-        if (L.packed) {
-          HIPCHK(hipMemcpyAsync(N.J + off, L.sJ, sizeof(int) * (size_t)L.kept, hipMemcpyDeviceToDevice, st));
-          HIPCHK(hipMemcpyAsync(N.V + off, L.sV, sizeof(float) * (size_t)L.kept, hipMemcpyDeviceToDevice, st));
-        } else if ((long long)L.kept >= 96ll * ml) {
-          hipLaunchKernelGGL(k_rmcl_move<64>, dim3(clampi(cdiv(ml, 4), 1, s.h->numCU * 32)), dim3(256), 0, st, ml, L.sI, L.sPtr,
-                             L.sJ, L.sV, N.J + off, N.V + off);
-        } else {
-          hipLaunchKernelGGL(k_rmcl_move<16>, dim3(clampi(cdiv(ml, 16), 1, s.h->numCU * 16)), dim3(256), 0, st, ml, L.sI, L.sPtr,
-                             L.sJ, L.sV, N.J + off, N.V + off);
-        }
+      const int* ptr = K.packed() ? K.I : K.len;      // row pointer of the packed block (ml + 1 entries)
+      if (cnt > 0) hipLaunchKernelGGL(k_offset_copy, dim3(cdiv(cnt, 256)), dim3(256), 0, st, cnt, ptr, (int)off, N.I.p + ends[s.grank]);
+      if (K.nnz > 0 && K.packed()) {
+        HIPCHK(hipMemcpyAsync(N.J.p + off, K.J, sizeof(int) * (size_t)K.nnz, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(N.V.p + off, K.V, sizeof(float) * (size_t)K.nnz, hipMemcpyDeviceToDevice, st));
+      } else if (K.nnz > 0) {
+        const RowLanes rl = row_lanes(s.h, ml, K.nnz);
+        RMCL_ROWS(k_rmcl_move, rl, st, ml, K.I.p, K.len.p, K.J.p, K.V.p, N.J.p + off, N.V.p + off);
       }
       HIPCHK(hipGetLastError());
       // RCCL runs on this same stream, behind the move; the other transports read the slice from other streams
@@ -887,7 +854,7 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
     } else {
       for (auto& s : g->sh) { hipSetDevice(s.device); if (hipStreamSynchronize(s.h->stream) != hipSuccess) { fail(SPGEMM_ERR_HIP, "sharded R-MCL: iteration %d", it); return abandon(SPGEMM_ERR_HIP); } }
     }
-    for (auto& L : job->loc) rmcl_release_block(L);   // the streams are idle: the scratch blocks go back to the pool
+    for (auto& L : job->loc) L.blk.reset();           // the streams are idle: the scratch blocks go back to the pool
     cur = nxt;
     job->iterNnz.push_back(total);
   }
@@ -923,18 +890,16 @@ extern "C" int hip_sharded_rmcl_result(spgemm_sharded_rmcl* job, int local_shard
   if (local_shard < 0 || local_shard >= (int)job->loc.size()) return fail(SPGEMM_ERR_ARG, "local shard %d out of range", local_shard);
   auto& L = job->loc[(size_t)local_shard];
   HIPCHK(hipSetDevice(job->g->sh[(size_t)local_shard].device));
-  const int* dI = job->cur < 0 ? L.Mt0.I : L.buf[job->cur].I;
-  const int* dJ = job->cur < 0 ? L.Mt0.J : L.buf[job->cur].J;
-  const float* dV = job->cur < 0 ? L.Mt0.V : L.buf[job->cur].V;
-  const int nz = job->cur < 0 ? L.Mt0.nnz : L.buf[job->cur].nnz;
+  const CsrView Mt = job->cur < 0 ? L.Mt0.view() : L.buf[job->cur].view();
+  const int nz = Mt.nnz;
   const int rows = job->rows;
   int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
   int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(nz, 1));
   float* hA = (float*)malloc(sizeof(float) * (size_t)std::max(nz, 1));
   if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return fail(SPGEMM_ERR_NOMEM, "host malloc failed"); }
-  if (hipMemcpy(hI, dI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToHost) != hipSuccess ||
-      (nz && hipMemcpy(hJ, dJ, sizeof(int) * (size_t)nz, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (nz && hipMemcpy(hA, dV, sizeof(float) * (size_t)nz, hipMemcpyDeviceToHost) != hipSuccess)) {
+  if (hipMemcpy(hI, Mt.I, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToHost) != hipSuccess ||
+      (nz && hipMemcpy(hJ, Mt.J, sizeof(int) * (size_t)nz, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (nz && hipMemcpy(hA, Mt.V, sizeof(float) * (size_t)nz, hipMemcpyDeviceToHost) != hipSuccess)) {
     free(hI); free(hJ); free(hA);
     return fail(SPGEMM_ERR_HIP, "copy of Mt to the host failed: %s", hipGetErrorString(hipGetLastError()));
   }

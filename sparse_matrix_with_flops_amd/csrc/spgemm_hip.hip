@@ -148,6 +148,67 @@ struct DevPool {
   }
 };
 DevPool& pool() { static DevPool* p = new DevPool(); return *p; }
+
+// One pool block with one owner: released when the owner goes, or handed on with release().  Move-only: a block that
+// went back twice would be hipFree'd under whoever holds it by then.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+  ~DevBuf() { reset(); }
+  hipError_t alloc(size_t n) { reset(); return pool().alloc((void**)&p, sizeof(T) * n); }   // on the current device
+  void reset() { pool().release(p); p = nullptr; }
+  T* release() { T* q = p; p = nullptr; return q; }             // the caller owns the block now
+  operator T*() const { return p; }
+};
+
+// A CSR matrix as a kernel reads it; nothing is owned.  len == nullptr: packed, row r is [I[r], I[r + 1]).  Otherwise row r
+// is [I[r], I[r] + len[r]) of (J, V), se[r] is the same extent as one {start, end} pair (what the classification gathers)
+// and nnz is the extent of the arrays.
+struct CsrView {
+  const int* I; const int* J; const float* V; int nnz;
+  const int* len = nullptr; const int2* se = nullptr;
+};
+
+// A device matrix that owns its pool blocks, in one of the three forms R-MCL keeps:
+//   packed   (no len)      I = row pointer, nnz entries in (J, V);
+//   extents  (len and se)  the rows lie where the fused epilogues wrote them: I = scratch row starts, len = kept entries per
+//                          row, se = {start, end} per row, nnz = extent of (J, V).  The next iteration reads it as it is;
+//   block    (len, no se)  scratch rows too, but len = the SCANNED counts = the row pointer of the packed block (rows + 1
+//                          entries, len[rows] = nnz = kept entries): the sharded loop packs the rows into its slice of Mt.
+struct DevCSR {
+  DevBuf<int> I, J; DevBuf<float> V; DevBuf<int> len; DevBuf<int2> se;
+  int rows = 0, cols = 0, nnz = 0;                  // rows, cols: set by upload_csr; a step knows them from its arguments
+  bool packed() const { return !len; }
+  CsrView view() const { return {I, J, V, nnz, len, se}; }
+  hipError_t alloc_entries(long long n) {           // (J, V) for n entries; never a zero-sized block
+    const hipError_t e = J.alloc((size_t)std::max(n, 1ll));
+    return e != hipSuccess ? e : V.alloc((size_t)std::max(n, 1ll));
+  }
+  void reset() { *this = DevCSR(); }
+  void give(int** oI, int** oJ, float** oV, int* onnz) {   // a packed matrix leaves the library (spgemm_hip_free takes it back)
+    *oI = I.release(); *oJ = J.release(); *oV = V.release(); *onnz = nnz;
+    reset();
+  }
+};
+
+// The pool hands a released block to other handles and streams, so a block goes back only when no queued kernel can still
+// touch it.  The owners above release when they leave scope; two rules make that late enough.
+// Rule A: a failure may leave kernels queued that write the blocks of the failed step, so every error return of a function
+// that has queued work is `return drained(stream, rc)`: the stream is idle before the locals are destroyed.
+static int drained(hipStream_t s, int rc) {
+  if (rc) (void)hipStreamSynchronize(s);
+  return rc;
+}
+// Rule B: a step of the R-MCL loop that leaves its result as extents returns WITHOUT waiting for its numeric kernels, and
+// they read the step's operand.  The operand is parked here and released one step later, when a call has waited for an
+// event recorded behind those kernels (stream order alone does not protect a block once it is back in the pool).
+struct Retired {
+  DevCSR m;
+  void park(DevCSR&& operand) { m = std::move(operand); }   // call only after a step that waited: releases the one parked before
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1564,28 +1625,35 @@ extern "C" int spgemm_hip_host_api_stats(spgemm_host_api_stats* out) {
 // ------------------------------------------------------------------------------------------------
 // R-MCL
 // ------------------------------------------------------------------------------------------------
+// Lanes per row of the row-wise kernels (k_rmcl_stats / _compact / _move): 16 for short rows; a whole wave once rows
+// average ~100 entries.  nnz = 0 asks for the 16-lane form.
+struct RowLanes { bool wide; int grid; };
+static RowLanes row_lanes(const spgemm_handle* h, int m, long long nnz) {
+  const bool wide = m > 0 && nnz >= 96ll * m;
+  return {wide, wide ? clampi(cdiv(m, 4), 1, h->numCU * 32) : clampi(cdiv(m, 16), 1, h->numCU * 16)};
+}
+#define RMCL_ROWS(kern, rl, stream, ...)                                                              \
+  do {                                                                                                \
+    if ((rl).wide) hipLaunchKernelGGL(kern<64>, dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);  \
+    else hipLaunchKernelGGL(kern<16>, dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);            \
+  } while (0)
+
 // nnzIn >= 0: the caller knows nnz(C) (it is on the host after every SpGEMM of this library) and the choice of lanes per
 // row needs no device read; nnzIn < 0: one 4-byte copy fetches it.
-static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const float* dC,
-                           int** dIN, int** dJN, float** dCN, int* nnzN) {
-  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
+static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const float* dC, DevCSR* out) {
+  out->reset();
   if (m < 0 || !dIC) return fail(SPGEMM_ERR_ARG, "bad argument");
   if (!h) CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
   h->sym_m = -1;                                   // scan scratch and the small device block are shared with a pending phase
   clear_stale_hip_error();
   CHK(ws_ensure(h, m));
-  int* newPtr = nullptr; int* JN = nullptr; float* CN = nullptr; float* th = nullptr; float* ks = nullptr;
-  auto cleanup = [&](int rc) { pool().release(newPtr); pool().release(JN); pool().release(CN); pool().release(th); pool().release(ks); return rc; };
-  auto hipfail = [&](const char* what) { return cleanup(fail(SPGEMM_ERR_HIP, "rmcl prune: %s: %s", what, hipGetErrorString(hipGetLastError()))); };
-  if (hipSuccess != pool().alloc((void**)&newPtr, sizeof(int) * ((size_t)m + 1)) ||
-      hipSuccess != pool().alloc((void**)&th, sizeof(float) * (size_t)std::max(m, 1)) ||
-      hipSuccess != pool().alloc((void**)&ks, sizeof(float) * (size_t)std::max(m, 1)))
-    return hipfail("device allocation failed");
+  DevCSR N;
+  DevBuf<float> th, ks;
+  auto hipfail = [&](const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl prune: %s: %s", what, hipGetErrorString(hipGetLastError())); };
+  if (N.I.alloc((size_t)m + 1) || th.alloc((size_t)std::max(m, 1)) || ks.alloc((size_t)std::max(m, 1))) return hipfail("device allocation failed");
   hipStream_t s = h->stream;
   if (hipMemsetAsync(&h->dsmall->nnzC64, 0, sizeof(unsigned long long), s) != hipSuccess) return hipfail("memset");
-  // lanes per row: 16 for short rows; a whole wave once rows average ~100 entries
   if (m > 0 && nnzIn < 0) {
     int tmp = 0;
     if (hipMemcpyAsync(&tmp, dIC + m, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -1593,43 +1661,46 @@ static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* 
       return hipfail("reading nnz");
     nnzIn = tmp;
   }
-  const bool wide = m > 0 && nnzIn >= 96ll * m;
-  const int grid = wide ? clampi(cdiv(m, 4), 1, h->numCU * 32) : clampi(cdiv(m, 16), 1, h->numCU * 16);
+  const RowLanes rl = row_lanes(h, m, nnzIn);
   if (m > 0) {
-    if (wide) hipLaunchKernelGGL(k_rmcl_stats<64>, dim3(grid), dim3(256), 0, s, m, dIC, dC, newPtr, th, ks);
-    else hipLaunchKernelGGL(k_rmcl_stats<16>, dim3(grid), dim3(256), 0, s, m, dIC, dC, newPtr, th, ks);
-    int rc = launch_scan(h, newPtr, m, &h->dsmall->nnzC64);
-    if (rc) return cleanup(rc);
+    RMCL_ROWS(k_rmcl_stats, rl, s, m, dIC, dC, N.I.p, th.p, ks.p);
+    CHK(launch_scan(h, N.I, m, &h->dsmall->nnzC64));
   } else {
-    hipMemsetAsync(newPtr, 0, sizeof(int), s);
+    hipMemsetAsync(N.I, 0, sizeof(int), s);
   }
   if (hipMemcpyAsync(&h->hsmall->nnzC64, &h->dsmall->nnzC64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return hipfail("kept-entry count");
-  const int nz = (int)h->hsmall->nnzC64;
-  if (hipSuccess != pool().alloc((void**)&JN, sizeof(int) * (size_t)std::max(nz, 1)) ||
-      hipSuccess != pool().alloc((void**)&CN, sizeof(float) * (size_t)std::max(nz, 1)))
-    return hipfail("device allocation failed");
-  if (m > 0 && nz > 0) {
-    if (wide) hipLaunchKernelGGL(k_rmcl_compact<64>, dim3(grid), dim3(256), 0, s, m, dIC, dJC, dC, newPtr, th, ks, JN, CN);
-    else hipLaunchKernelGGL(k_rmcl_compact<16>, dim3(grid), dim3(256), 0, s, m, dIC, dJC, dC, newPtr, th, ks, JN, CN);
+  N.nnz = (int)h->hsmall->nnzC64;
+  if (N.alloc_entries(N.nnz)) return hipfail("device allocation failed");
+  if (m > 0 && N.nnz > 0) {
+    RMCL_ROWS(k_rmcl_compact, rl, s, m, dIC, dJC, dC, N.I.p, th.p, ks.p, N.J.p, N.V.p);
     if (hipGetLastError() != hipSuccess) return hipfail("compaction launch");
   }
   if (hipStreamSynchronize(s) != hipSuccess) return hipfail("compaction");
-  pool().release(th); pool().release(ks);
-  *dIN = newPtr; *dJN = JN; *dCN = CN; *nnzN = nz;
+  *out = std::move(N);
+  return SPGEMM_OK;
+}
+
+static int rmcl_prune_abi(spgemm_handle* h, int m, long long nnz, const int* dIC, const int* dJC, const float* dC, int** dIN,
+                          int** dJN, float** dCN, int* nnzN) {
+  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
+  DevCSR N;
+  CHK(rmcl_prune_impl(h, m, nnz, dIC, dJC, dC, &N));
+  N.give(dIN, dJN, dCN, nnzN);
   return SPGEMM_OK;
 }
 
 extern "C" int hip_rmcl_prune(spgemm_handle* h, int m, const int* dIC, const int* dJC, float* dC, int** dIN, int** dJN,
                               float** dCN, int* nnzN) {
-  return rmcl_prune_impl(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+  return rmcl_prune_abi(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
 }
 
 extern "C" int hip_rmcl_prune_n(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const float* dC,
                                 int** dIN, int** dJN, float** dCN, int* nnzN) {
   if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative nnz");
-  return rmcl_prune_impl(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+  return rmcl_prune_abi(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
 }
 
 // Expansion and prune of one R-MCL iteration as ONE operator: C = A*B is never materialised.  Every numeric kernel
@@ -1637,186 +1708,178 @@ extern "C" int hip_rmcl_prune_n(spgemm_handle* h, int m, int nnz, const int* dIC
 // (about a quarter of the product) to the front of the row's range of a scratch C; k_rmcl_move packs them.
 // What the reference's loop does in three steps (gpu SpGEMM, inflate+threshold kernels of dutil.cuh, thrust::remove;
 // gpu_csr_kernel.cu:218-270) and hip_gpuSpMM + hip_rmcl_prune do in two.
-// Rows that sit at [starts[r], starts[r] + len[r]) of (J, V) -- where the epilogues of the fused R-MCL step leave them --
-// packed into a CSR of their own: the scan of the lengths is the row pointer, k_rmcl_move copies the rows.
-static int rmcl_pack_rows(spgemm_handle* h, int m, const int* starts, const int* len, const int* J, const float* V,
-                          int** pI, int** pJ, float** pV, int* pn) {
-  *pI = nullptr; *pJ = nullptr; *pV = nullptr; *pn = 0;
+// The m rows of an unpacked R, packed into a CSR of their own: the scan of the lengths is the row pointer, k_rmcl_move
+// copies the rows.
+static int rmcl_pack_rows(spgemm_handle* h, int m, const CsrView& R, DevCSR* out) {
+  out->reset();
   hipStream_t s = h->stream;
-  int* I = nullptr; int* JN = nullptr; float* CN = nullptr;
-  auto bad = [&](int rc) { pool().release(I); pool().release(JN); pool().release(CN); return rc; };
-  if (hipSuccess != pool().alloc((void**)&I, sizeof(int) * ((size_t)m + 1))) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
-  unsigned long long total = 0;
-  int rc;
-  if (hipMemsetAsync(I, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess ||
-      hipMemcpyAsync(I, len, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return bad(fail(SPGEMM_ERR_HIP, "pack: copy of the row lengths"));
-  if ((rc = launch_scan(h, I, m, &h->dsmall->kept64))) return bad(rc);
-  if (hipMemcpyAsync(&h->hsmall->kept64, &h->dsmall->kept64, sizeof(total), hipMemcpyDeviceToHost, s) != hipSuccess ||
+  DevCSR N;
+  if (N.I.alloc((size_t)m + 1)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
+  if (hipMemsetAsync(N.I, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess ||
+      hipMemcpyAsync(N.I, R.len, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return fail(SPGEMM_ERR_HIP, "pack: copy of the row lengths");
+  CHK(launch_scan(h, N.I, m, &h->dsmall->kept64));
+  if (hipMemcpyAsync(&h->hsmall->kept64, &h->dsmall->kept64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return bad(fail(SPGEMM_ERR_HIP, "pack: scan of the row lengths"));
-  total = h->hsmall->kept64;
-  if (total > 0x7fffffffULL) return bad(fail(SPGEMM_ERR_OVERFLOW, "pack: %llu entries", total));
-  const int nz = (int)total;
-  if (hipSuccess != pool().alloc((void**)&JN, sizeof(int) * (size_t)std::max(nz, 1)) ||
-      hipSuccess != pool().alloc((void**)&CN, sizeof(float) * (size_t)std::max(nz, 1)))
-    return bad(fail(SPGEMM_ERR_NOMEM, "device allocation failed"));
-  if (nz > 0 && m > 0) {
-    hipLaunchKernelGGL(k_rmcl_move<16>, dim3(clampi(cdiv(m, 16), 1, h->numCU * 16)), dim3(256), 0, s, m, starts, I, J, V, JN, CN);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return bad(fail(SPGEMM_ERR_HIP, "pack: move"));
+    return fail(SPGEMM_ERR_HIP, "pack: scan of the row lengths");
+  const unsigned long long total = h->hsmall->kept64;
+  if (total > 0x7fffffffULL) return fail(SPGEMM_ERR_OVERFLOW, "pack: %llu entries", total);
+  N.nnz = (int)total;
+  if (N.alloc_entries(N.nnz)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
+  if (N.nnz > 0 && m > 0) {
+    const RowLanes rl = row_lanes(h, m, 0);          // always the 16-lane form
+    RMCL_ROWS(k_rmcl_move, rl, s, m, R.I, N.I.p, R.J, R.V, N.J.p, N.V.p);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail(SPGEMM_ERR_HIP, "pack: move");
   }
-  *pI = I; *pJ = JN; *pV = CN; *pn = nz;
+  *out = std::move(N);
   return SPGEMM_OK;
 }
 
-// One R-MCL iteration (expansion with the row rule fused into the numeric epilogues) on device arrays.
-//   dIBlen != nullptr   B is NOT packed: row j is [dIB[j], dIB[j] + dIBlen[j]) of (dJB, dB), dIBse[j] holds the same
-//                       extent as one {start, end} pair (what the classification gathers); nnzB = the arrays' extent
-//   mode RMCL_EXTENTS   the result is left where the epilogues wrote it: *dIN = the scratch row starts (m + 1 entries),
-//                       *dLenN = the kept entries per row, *dSEN = the {start, end} pairs, *dJN / *dCN = the scratch
-//                       arrays, *nnzN = their extent (P).
-//                       The next iteration reads it as its unpacked B: no scan, no copy, no allocation of packed arrays.
-//   mode RMCL_BLOCK     (sharded loop) the rows stay in the scratch arrays too, but their lengths are scanned: *dIN = the
-//                       scratch row starts, *dLenN = the row pointer of the PACKED block (m + 1 entries, [m] = *nnzN =
-//                       kept entries), *dJN / *dCN = the scratch arrays.  The caller packs the rows wherever the block
-//                       belongs (its slice of the next replicated Mt: k_rmcl_move), with no packed copy in between.
-//                       (The paths that give up on the fused step return a packed result and *dLenN = nullptr.)
+// ---- one fused R-MCL step (rmcl_expand_prune_core) and its phases ----
+// The form the step leaves its result in (DevCSR): extents for the next iteration of the loop, packed for a caller,
+// block for the sharded loop.  The give-up route returns a packed result whatever was asked for.
 enum { RMCL_EXTENTS = 0, RMCL_PACK = 1, RMCL_BLOCK = 2 };
-static int rmcl_expand_prune_core(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
-                                  const int* dIB, const int* dIBlen, const int2* dIBse, const int* dJB, const float* dB,
-                                  int nnzB, int m, int k, int n, int mode, int** dIN, int** dLenN, int2** dSEN,
-                                  int** dJN, float** dCN, int* nnzN, bool* errPending = nullptr) {
-  const bool pack = mode == RMCL_PACK;
-  *dIN = nullptr; *dLenN = nullptr; *dSEN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
-  if (h->failNext > 0) { --h->failNext; return fail(SPGEMM_ERR_INTERNAL, "forced failure (spgemm_hip_debug_fail_next)"); }
-  HIPCHK(hipSetDevice(h->device));
-  auto two_steps = [&]() {                           // no rows, no products, or a product too large for the scratch C
-    int *bI = nullptr, *bJ = nullptr, bn = nnzB;
-    float* bV = nullptr;
-    int rc = SPGEMM_OK;
-    if (dIBlen && (rc = rmcl_pack_rows(h, k, dIB, dIBlen, dJB, dB, &bI, &bJ, &bV, &bn))) return rc;
-    int *cI = nullptr, *cJ = nullptr, cn = 0;
-    float* cA = nullptr;
-    rc = spgemm_device(h, {dIA, dJA, dA, nnzA, dIBlen ? bI : dIB, dIBlen ? bJ : dJB, dIBlen ? bV : dB, m, k, n}, bn, nullptr,
-                       {&cI, &cJ, &cA, &cn});
-    if (!rc) rc = rmcl_prune_impl(h, m, cn, cI, cJ, cA, dIN, dJN, dCN, nnzN);
-    pool().release(cI); pool().release(cJ); pool().release(cA);
-    pool().release(bI); pool().release(bJ); pool().release(bV);
-    return rc;
-  };
-  if (m == 0) return two_steps();
-  CHK(ws_ensure(h, m));
-  int* dIC = nullptr; int* cnt = nullptr; int* dJC = nullptr; float* dC = nullptr; int* JN = nullptr; float* CN = nullptr;
-  auto cleanup = [&](int rc) {
-    // a failure may leave kernels queued that still write these blocks (and, in the loop form, the previous iteration's):
-    // the pool hands a released block to other handles and streams, so nothing goes back before the stream has drained
-    if (rc) (void)hipStreamSynchronize(h->stream);
-    for (void* q : {(void*)dIC, (void*)cnt, (void*)dJC, (void*)dC, (void*)JN, (void*)CN}) pool().release(q);
-    return rc;
-  };
-  auto hipfail = [&](const char* what) { return cleanup(fail(SPGEMM_ERR_HIP, "rmcl expand+prune: %s: %s", what, hipGetErrorString(hipGetLastError()))); };
-  if (hipSuccess != pool().alloc((void**)&dIC, sizeof(int) * ((size_t)m + 1)) ||
-      hipSuccess != pool().alloc((void**)&cnt, sizeof(int) * ((size_t)m + 1)))
-    return hipfail("device allocation failed");
+
+static int rmcl_hipfail(const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl expand+prune: %s: %s", what, hipGetErrorString(hipGetLastError())); }
+
+// Give-up route (no rows, no products, or a product too large for the scratch C): SpGEMM + prune, an unpacked B packed first.
+static int rmcl_two_steps(spgemm_handle* h, const CsrView& A, CsrView B, int m, int k, int n, DevCSR* out) {
+  DevCSR Bp, C;
+  if (B.len) { CHK(rmcl_pack_rows(h, k, B, &Bp)); B = Bp.view(); }
+  CHK(spgemm_device(h, {A.I, A.J, A.V, A.nnz, B.I, B.J, B.V, m, k, n}, B.nnz, nullptr, {&C.I.p, &C.J.p, &C.V.p, &C.nnz}));
+  return rmcl_prune_impl(h, m, C.nnz, C.I, C.J, C.V, out);
+}
+
+// Classification of the rows by their products into `mid`; C gets its row-start and kept-count arrays (m + 1 each).
+static int rmcl_classify(spgemm_handle* h, const CsrView& A, const CsrView& B, int m, DevCSR* C, HostMirror* mid, bool* errPending) {
+  if (C->I.alloc((size_t)m + 1) || C->len.alloc((size_t)m + 1)) return rmcl_hipfail("device allocation failed");
   hipStream_t s = h->stream;
   h->sym_m = -1;
   hipEventRecord(h->ev[0], s);
   h->cur_rowIds = h->rowIds;
-  int rc = launch_classify(h, dIA, dJA, dIB, m, nnzA, dIC, dIBse);
-  if (rc) return cleanup(rc);
+  CHK(launch_classify(h, A.I, A.J, B.I, m, A.nnz, C->I, B.se));
   hipEventRecord(h->ev[1], s);
   if (hipMemcpyAsync(h->hmid, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipEventRecord(h->evMid, s) != hipSuccess)
-    return hipfail("classification copy");
-  if (hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return hipfail("memset");
-  if (hipEventSynchronize(h->evMid) != hipSuccess) return hipfail("classification");
+    return rmcl_hipfail("classification copy");
+  if (hipMemsetAsync(C->len, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return rmcl_hipfail("memset");
+  if (hipEventSynchronize(h->evMid) != hipSuccess) return rmcl_hipfail("classification");
   if (errPending && *errPending) {                   // the previous iteration of the loop returned without waiting for its
     *errPending = false;                             // numeric kernels: their flags reached the host before this event
-    if (h->hsmall->err) return cleanup(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in the previous iteration (flags=%d)", h->hsmall->err));
+    if (h->hsmall->err) return fail(SPGEMM_ERR_INTERNAL, "device invariant broken in the previous iteration (flags=%d)", h->hsmall->err);
   }
-  const HostMirror mid = *h->hmid;
-  const unsigned long long P = mid.totalP;
+  *mid = *h->hmid;
+  return SPGEMM_OK;
+}
+
+// Row sizing WITHOUT the symbolic pass, for every row of at most 4096 products (all rows of an R-MCL iteration on a
+// sparse graph without hubs).  The pass's only product is the exact size of every row of C, and C is not kept: the
+// scratch rows are laid out by the rows' product counts (known from the classification), every such row is hashed in a
+// table sized by its products and the epilogue counts the distinct columns itself.  Rows of bin 8 pass through LDS in
+// pieces and need their exact counts: only they get a symbolic kernel (k_sym_big overwrites their entries of dIC).
+static int rmcl_size_rows_by_products(spgemm_handle* h, const CsrView& A, const CsrView& B, int m, int n, const HostMirror& mid, int* dIC) {
+  hipStream_t s = h->stream;
+  if (hipMemcpyAsync(dIC, h->rowFlops, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess) return rmcl_hipfail("copy");
+  const int nbig = mid.binPtr[NBINS] - mid.binPtr[NBINS - 1];
+  if (nbig > 0) {
+    KTimer t(h, SPGEMM_K_SYM_BIG, s);
+    hipLaunchKernelGGL(k_sym_big, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
+                       h->dsmall->binPtr, 8, h->cur_rowIds, A.I, h->sbl, B.J, n, dIC, h->bigBitmaps, h->bm_cap,
+                       h->dsmall->qctr + 0 * 32);
+    if (hipGetLastError() != hipSuccess) return rmcl_hipfail("symbolic launch");
+  }
+  return SPGEMM_OK;
+}
+
+// Scan of the row sizes, the scratch arrays (one slot per product) and the numeric kernels with the row rule in their
+// epilogues (pmode 2: rows laid out by products); scanKept: the kept counts are scanned behind them.
+static int rmcl_numeric(spgemm_handle* h, const CsrView& A, const CsrView& B, int m, int n, const HostMirror& mid, bool nosym,
+                        bool scanKept, DevCSR* C) {
+  hipStream_t s = h->stream;
+  hipEventRecord(h->ev[2], s);
+  CHK(launch_scan(h, C->I, m, &h->dsmall->nnzC64));
+  hipEventRecord(h->ev[3], s);
+  if (C->alloc_entries((long long)mid.totalP)) return rmcl_hipfail("device allocation of the scratch product failed");
+  hipEventRecord(h->ev[4], s);
+  h->mirror = mid;
+  CHK(launch_numeric(h, A.I, A.V, B.J, B.V, n, h->cur_rowIds, mid.binPtr, C->I, C->J, C->V, C->len, nosym ? 2 : 1));
+  hipEventRecord(h->ev[5], s);
+  return scanKept ? launch_scan(h, C->len, m, &h->dsmall->kept64) : SPGEMM_OK;
+}
+
+// Finish 1: the rows stay where the epilogues wrote them, as {start, end} pairs for the next classification (queued behind this).
+static int rmcl_leave_extents(spgemm_handle* h, int m, const HostMirror& mid, DevCSR* C) {
+  if (C->se.alloc((size_t)m)) return rmcl_hipfail("device allocation failed");
+  hipLaunchKernelGGL(k_zip_extents, dim3(cdiv(m, 256)), dim3(256), 0, h->stream, m, C->I.p, C->len.p, C->se.p);
+  if (hipGetLastError() != hipSuccess) return rmcl_hipfail("extent launch");
+  C->nnz = (int)mid.totalP;
+  return SPGEMM_OK;
+}
+
+// Finish 3 (finish 2, the block form, is the scratch C as it stands): the kept entries move into packed arrays, the
+// scanned counts become the row pointer and the scratch C goes back to the pool.
+static int rmcl_pack_result(spgemm_handle* h, int m, int nz, DevCSR* C) {
+  DevCSR N;
+  if (N.alloc_entries(nz)) return rmcl_hipfail("device allocation failed");
+  if (nz > 0) {
+    const RowLanes rl = row_lanes(h, m, nz);
+    RMCL_ROWS(k_rmcl_move, rl, h->stream, m, C->I.p, C->len.p, C->J.p, C->V.p, N.J.p, N.V.p);
+    if (hipGetLastError() != hipSuccess) return drained(h->stream, rmcl_hipfail("move launch"));   // N goes before the caller drains
+  }
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return drained(h->stream, rmcl_hipfail("move"));
+  N.I = std::move(C->len);
+  N.nnz = nz;
+  *C = std::move(N);
+  return SPGEMM_OK;
+}
+
+// One R-MCL iteration (expansion with the row rule fused into the numeric epilogues): *out = prune(A * B) in the form
+// `mode` names.  errPending != nullptr: the loop form, whose extents exit does not wait (below).
+static int rmcl_expand_prune_core(spgemm_handle* h, const CsrView& A, const CsrView& B, int m, int k, int n, int mode,
+                                  DevCSR* out, bool* errPending = nullptr) {
+  out->reset();
+  if (h->failNext > 0) { --h->failNext; return fail(SPGEMM_ERR_INTERNAL, "forced failure (spgemm_hip_debug_fail_next)"); }
+  HIPCHK(hipSetDevice(h->device));
+  if (m == 0) return rmcl_two_steps(h, A, B, m, k, n, out);
+  CHK(ws_ensure(h, m));
+  hipStream_t s = h->stream;
+  DevCSR C;                                          // the scratch product: row starts, kept counts, one slot per product
+  HostMirror mid;
+  int rc = rmcl_classify(h, A, B, m, &C, &mid, errPending);
+  if (rc) return drained(s, rc);
   // products beyond which the scratch C (8 bytes per product) is not made and the step runs as SpGEMM + prune.
   // SPGEMM_RMCL_MAXP lowers the bound (test hook: the give-up path behind an unpacked Mt on small inputs).
   unsigned long long maxP = 1ull << 30;
   if (const char* e = getenv("SPGEMM_RMCL_MAXP")) maxP = std::min<unsigned long long>(maxP, strtoull(e, nullptr, 10));
-  if (P == 0 || P > maxP) {
-    if (hipStreamSynchronize(s) != hipSuccess) return hipfail("classification");
-    cleanup(0);
-    dIC = cnt = dJC = JN = nullptr; dC = CN = nullptr;
-    return two_steps();
+  if (mid.totalP == 0 || mid.totalP > maxP) {
+    if (hipStreamSynchronize(s) != hipSuccess) return drained(s, rmcl_hipfail("classification"));
+    C.reset();
+    return rmcl_two_steps(h, A, B, m, k, n, out);
   }
-  // The symbolic pass is SKIPPED for every row of at most 4096 products (all rows of an R-MCL iteration on a sparse graph
-  // without hubs).  Its only product is the exact size of every row of C, and C is not kept: the scratch rows are laid
-  // out by the rows' product counts (known from the classification), every such row is hashed in a table sized by its
-  // products and the epilogue counts the distinct columns itself.  Rows of bin 8 pass through LDS in pieces and need
-  // their exact counts: only they get a symbolic kernel (k_sym_big overwrites their entries of dIC).
   const bool nosym = !getenv("SPGEMM_RMCL_SYMBOLIC");
-  if (nosym) {
-    if (hipMemcpyAsync(dIC, h->rowFlops, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess) return hipfail("copy");
-    const int nbig = mid.binPtr[NBINS] - mid.binPtr[NBINS - 1];
-    if (nbig > 0) {
-      KTimer t(h, SPGEMM_K_SYM_BIG, s);
-      hipLaunchKernelGGL(k_sym_big, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
-                         h->dsmall->binPtr, 8, h->cur_rowIds, dIA, h->sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap,
-                         h->dsmall->qctr + 0 * 32);
-      if (hipGetLastError() != hipSuccess) return hipfail("symbolic launch");
-    }
-  } else if ((rc = launch_symbolic(h, dIA, dJB, m, n, h->cur_rowIds, dIC))) return cleanup(rc);
-  hipEventRecord(h->ev[2], s);
-  if ((rc = launch_scan(h, dIC, m, &h->dsmall->nnzC64))) return cleanup(rc);
-  hipEventRecord(h->ev[3], s);
-  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * (size_t)P) ||
-      hipSuccess != pool().alloc((void**)&dC, sizeof(float) * (size_t)P))
-    return hipfail("device allocation of the scratch product failed");
-  hipEventRecord(h->ev[4], s);
-  h->mirror = mid;
-  if ((rc = launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, mid.binPtr, dIC, dJC, dC, cnt, nosym ? 2 : 1))) return cleanup(rc);
-  hipEventRecord(h->ev[5], s);
-  if ((pack || mode == RMCL_BLOCK) && (rc = launch_scan(h, cnt, m, &h->dsmall->kept64))) return cleanup(rc);
-  // the rows stay where the epilogues wrote them, as {start, end} pairs for the next classification (queued behind this kernel)
-  auto leave_extents = [&]() {
-    int2* se = nullptr;
-    if (hipSuccess != pool().alloc((void**)&se, sizeof(int2) * (size_t)m)) return hipfail("device allocation failed");
-    hipLaunchKernelGGL(k_zip_extents, dim3(cdiv(m, 256)), dim3(256), 0, s, m, dIC, cnt, se);
-    if (hipGetLastError() != hipSuccess) { pool().release(se); return hipfail("extent launch"); }
-    *dIN = dIC; *dLenN = cnt; *dSEN = se; *dJN = dJC; *dCN = dC; *nnzN = (int)P;
-    return SPGEMM_OK;
-  };
+  rc = nosym ? rmcl_size_rows_by_products(h, A, B, m, n, mid, C.I) : launch_symbolic(h, A.I, B.J, m, n, h->cur_rowIds, C.I);
+  if (!rc) rc = rmcl_numeric(h, A, B, m, n, mid, nosym, mode != RMCL_EXTENTS, &C);
+  if (rc) return drained(s, rc);
   if (mode == RMCL_EXTENTS && errPending && h->ktiming == 0) {
     // Loop form: nothing of this iteration is needed on the host before the next one starts -- its classification is
-    // queued behind the numeric kernels, and the error flags are looked at after that classification's event (above).
+    // queued behind the numeric kernels, and the error flags are looked at after that classification's event.
     // The host runs ahead and the GPU does not idle between iterations.  (With per-kernel timing on, the events have to
     // be read now: the call waits as before.)
     if (hipMemcpyAsync(h->hsmall, h->dsmall, sizeof(HostMirror), hipMemcpyDeviceToHost, s) != hipSuccess)
-      return hipfail("numeric phase");                 // (read_mirror's copy without its wait)
-    if ((rc = leave_extents())) return rc;
+      return drained(s, rmcl_hipfail("numeric phase"));   // (read_mirror's copy without its wait)
+    if ((rc = rmcl_leave_extents(h, m, mid, &C))) return drained(s, rc);
     publish_stats(h, mid, StatsForm::CountsOnly);
     *errPending = true;
+    *out = std::move(C);
     return SPGEMM_OK;
   }
-  if ((rc = read_mirror(h, "rmcl expand+prune"))) return cleanup(rc);
-  const HostMirror& hm = h->mirror;
-  publish_stats(h, hm, nosym ? StatsForm::OneShotNoNnz : StatsForm::OneShot);
+  if ((rc = read_mirror(h, "rmcl expand+prune"))) return drained(s, rc);
+  publish_stats(h, h->mirror, nosym ? StatsForm::OneShotNoNnz : StatsForm::OneShot);
   grow_bitmaps(h, n);
-  if (mode == RMCL_BLOCK) {                          // scratch rows + the row pointer of the packed block
-    *dIN = dIC; *dLenN = cnt; *dJN = dJC; *dCN = dC; *nnzN = (int)hm.kept64;
-    return SPGEMM_OK;
-  }
-  if (!pack) return leave_extents();
-  const int nz = (int)hm.kept64;                     // <= nnz(C) <= P <= 2^30
-  if (hipSuccess != pool().alloc((void**)&JN, sizeof(int) * (size_t)std::max(nz, 1)) ||
-      hipSuccess != pool().alloc((void**)&CN, sizeof(float) * (size_t)std::max(nz, 1)))
-    return hipfail("device allocation failed");
-  if (nz > 0) {
-    const bool wide = nz >= 96ll * m;
-    if (wide) hipLaunchKernelGGL(k_rmcl_move<64>, dim3(clampi(cdiv(m, 4), 1, h->numCU * 32)), dim3(256), 0, s, m, dIC, cnt, dJC, dC, JN, CN);
-    else hipLaunchKernelGGL(k_rmcl_move<16>, dim3(clampi(cdiv(m, 16), 1, h->numCU * 16)), dim3(256), 0, s, m, dIC, cnt, dJC, dC, JN, CN);
-    if (hipGetLastError() != hipSuccess) return hipfail("move launch");
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return hipfail("move");
-  pool().release(dIC); pool().release(dJC); pool().release(dC);
-  *dIN = cnt; *dJN = JN; *dCN = CN; *nnzN = nz;
+  const int kept = (int)h->mirror.kept64;            // <= nnz(C) <= P <= 2^30
+  if (mode == RMCL_BLOCK) C.nnz = kept;              // scratch rows + the row pointer of the packed block
+  else if ((rc = mode == RMCL_PACK ? rmcl_pack_result(h, m, kept, &C) : rmcl_leave_extents(h, m, mid, &C))) return drained(s, rc);
+  *out = std::move(C);
   return SPGEMM_OK;
 }
 
@@ -1829,10 +1892,10 @@ extern "C" int hip_rmcl_expand_prune(spgemm_handle* h, const int* dIA, const int
   CHK(check_common(dIA, dJA, dA, nnzA, "A"));
   CHK(check_common(dIB, dJB, dB, nnzB, "B"));
   if (!h) CHK(default_handle(&h));
-  int* len = nullptr;
-  int2* se = nullptr;
-  return rmcl_expand_prune_core(h, dIA, dJA, dA, nnzA, dIB, nullptr, nullptr, dJB, dB, nnzB, m, k, n, RMCL_PACK, dIN, &len, &se,
-                                dJN, dCN, nnzN);
+  DevCSR N;
+  CHK(rmcl_expand_prune_core(h, {dIA, dJA, dA, nnzA}, {dIB, dJB, dB, nnzB}, m, k, n, RMCL_PACK, &N));
+  N.give(dIN, dJN, dCN, nnzN);
+  return SPGEMM_OK;
 }
 
 // The R-MCL loop on device arrays (gpuRmclIter, gpus/gpu_csr_kernel.cu:15-40, without its two copies): maxIter iterations
@@ -1851,51 +1914,31 @@ extern "C" int hip_gpuRmclIter_device(spgemm_handle* h, int maxIter, int rows, i
   if (!h) CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
   const bool keep_packed = getenv("SPGEMM_RMCL_PACK") != nullptr;       // A/B switch: pack after every iteration
-  const int *bI = dtI, *bLen = nullptr, *bJ = dtJ;
-  const int2* bSE = nullptr;
-  const float* bV = dtA;
-  int bn = tnnz;
-  int *cI = nullptr, *cLen = nullptr, *cJ = nullptr;                    // the current Mt when the loop owns it
-  int2* cSE = nullptr;
-  float* cV = nullptr;
-  // An iteration that leaves Mt unpacked returns WITHOUT waiting for its numeric kernels (they read the previous Mt):
-  // that Mt goes to `old` and is released one iteration later, after a call that has waited for an event recorded behind
-  // those kernels -- the pool hands blocks to other handles and streams, so stream order alone does not protect them.
-  std::vector<void*> old;
-  auto flush_old = [&]() { for (void* q : old) pool().release(q); old.clear(); };
-  auto drop = [&]() {
-    for (void* q : {(void*)cI, (void*)cLen, (void*)cSE, (void*)cJ, (void*)cV}) if (q) old.push_back(q);
-    cI = cLen = cJ = nullptr; cSE = nullptr; cV = nullptr;
-  };
+  hipStream_t s = h->stream;
+  DevCSR cur;                                        // the current Mt once the loop owns one; until then the caller's
+  Retired old;                                       // rule B: the Mt the latest step read
   bool errPending = false;
-  auto bail = [&](int rc) { (void)hipStreamSynchronize(h->stream); drop(); flush_old(); return rc; };
   for (int it = 0; it < maxIter; ++it) {
-    int *nI = nullptr, *nLen = nullptr, *nJ = nullptr, nn = 0;
-    int2* nSE = nullptr;
-    float* nV = nullptr;
+    DevCSR next;
     const bool pack = keep_packed || it == maxIter - 1;
-    const int rc = rmcl_expand_prune_core(h, dgI, dgJ, dgA, gnnz, bI, bLen, bSE, bJ, bV, bn, rows, cols, cols,
-                                          pack ? RMCL_PACK : RMCL_EXTENTS, &nI, &nLen, &nSE, &nJ, &nV, &nn, &errPending);
-    if (rc) return bail(rc);
-    flush_old();                                     // the call above waited behind the kernels that read these
-    drop();                                          // the Mt it read itself: released after the next call
-    cI = nI; cLen = nLen; cSE = nSE; cJ = nJ; cV = nV;
-    bI = cI; bLen = cLen; bSE = cSE; bJ = cJ; bV = cV; bn = nn;
-  }
-  flush_old();                                       // the last iteration packs and waits for everything
+    const CsrView Mt = it ? cur.view() : CsrView{dtI, dtJ, dtA, tnnz};
+    if (int rc = rmcl_expand_prune_core(h, {dgI, dgJ, dgA, gnnz}, Mt, rows, cols, cols, pack ? RMCL_PACK : RMCL_EXTENTS, &next, &errPending))
+      return drained(s, rc);
+    old.park(std::move(cur));                        // that call waited behind the readers of the Mt parked before
+    cur = std::move(next);
+  }                                                  // (the last iteration packs and waits for everything)
   if (maxIter == 0) {                                // a copy of Mt
-    const size_t bi = sizeof(int) * ((size_t)rows + 1), bj = sizeof(int) * (size_t)std::max(tnnz, 1);
-    if (hipSuccess != pool().alloc((void**)&cI, bi) || hipSuccess != pool().alloc((void**)&cJ, bj) ||
-        hipSuccess != pool().alloc((void**)&cV, bj)) { return bail(fail(SPGEMM_ERR_NOMEM, "device allocation failed")); }
-    if (hipMemcpyAsync(cI, dtI, bi, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-        (tnnz > 0 && (hipMemcpyAsync(cJ, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, h->stream) != hipSuccess ||
-                      hipMemcpyAsync(cV, dtA, sizeof(float) * (size_t)tnnz, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)) ||
-        hipStreamSynchronize(h->stream) != hipSuccess) { return bail(fail(SPGEMM_ERR_HIP, "copy of Mt")); }
-    bn = tnnz;
-  } else if (bLen) {                                 // the last iteration gave up on the fused step?  it returns packed: not reached
-    return bail(fail(SPGEMM_ERR_INTERNAL, "the last iteration returned an unpacked matrix"));
+    if (cur.I.alloc((size_t)rows + 1) || cur.alloc_entries(tnnz)) return drained(s, fail(SPGEMM_ERR_NOMEM, "device allocation failed"));
+    if (hipMemcpyAsync(cur.I, dtI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        (tnnz > 0 && (hipMemcpyAsync(cur.J, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                      hipMemcpyAsync(cur.V, dtA, sizeof(float) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess)) ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return drained(s, fail(SPGEMM_ERR_HIP, "copy of Mt"));
+    cur.nnz = tnnz;
+  } else if (!cur.packed()) {                        // the last iteration gave up on the fused step?  it returns packed: not reached
+    return drained(s, fail(SPGEMM_ERR_INTERNAL, "the last iteration returned an unpacked matrix"));
   }
-  *oI = cI; *oJ = cJ; *oA = cV; *onnz = bn;
+  cur.give(oI, oJ, oA, onnz);
   return SPGEMM_OK;
 }
 
@@ -1957,32 +2000,26 @@ extern "C" int hip_gpuRmclIter(int maxIter, int rows, int cols, const int* gIA, 
   }
   spgemm_handle* h = nullptr;
   CHK(default_handle(&h));
-  int *dgI = nullptr, *dgJ = nullptr, *dtI = nullptr, *dtJ = nullptr;
-  float *dgA = nullptr, *dtA = nullptr;
-  auto cleanup = [&](int rc) { for (void* p : {(void*)dgI, (void*)dgJ, (void*)dgA, (void*)dtI, (void*)dtJ, (void*)dtA}) pool().release(p); return rc; };
+  DevCSR Mg, Mt, N;
+  auto up = [](auto& buf, const auto* src, size_t n) {
+    const int rc = spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * n);
+    return rc ? rc : spgemm_hip_memcpy_h2d(buf.p, src, sizeof(*src) * n);
+  };
   int rc;
-#define UP(dst, src, bytes) \
-  if ((rc = spgemm_hip_malloc((void**)&dst, (bytes))) || (rc = spgemm_hip_memcpy_h2d(dst, src, (bytes)))) return cleanup(rc);
-  UP(dgI, gIA, sizeof(int) * ((size_t)rows + 1)); UP(dgJ, gJA, sizeof(int) * (size_t)gnnz); UP(dgA, gA, sizeof(float) * (size_t)gnnz);
-  UP(dtI, tIA, sizeof(int) * ((size_t)rows + 1)); UP(dtJ, tJA, sizeof(int) * (size_t)tnnz); UP(dtA, tA, sizeof(float) * (size_t)tnnz);
-#undef UP
-  int curnnz = tnnz;
-  {
-    int *nI = nullptr, *nJ = nullptr, nn = 0;
-    float* nA = nullptr;
-    if ((rc = hip_gpuRmclIter_device(h, maxIter, rows, cols, dgI, dgJ, dgA, gnnz, dtI, dtJ, dtA, tnnz, &nI, &nJ, &nA, &nn))) return cleanup(rc);
-    pool().release(dtI); pool().release(dtJ); pool().release(dtA);
-    dtI = nI; dtJ = nJ; dtA = nA; curnnz = nn;
-  }
+  if ((rc = up(Mg.I, gIA, (size_t)rows + 1)) || (rc = up(Mg.J, gJA, (size_t)gnnz)) || (rc = up(Mg.V, gA, (size_t)gnnz)) ||
+      (rc = up(Mt.I, tIA, (size_t)rows + 1)) || (rc = up(Mt.J, tJA, (size_t)tnnz)) || (rc = up(Mt.V, tA, (size_t)tnnz)))
+    return rc;
+  CHK(hip_gpuRmclIter_device(h, maxIter, rows, cols, Mg.I, Mg.J, Mg.V, gnnz, Mt.I, Mt.J, Mt.V, tnnz, &N.I.p, &N.J.p, &N.V.p, &N.nnz));
+  Mt.reset();
   int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
-  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(curnnz, 1));
-  float* hA = (float*)malloc(sizeof(float) * (size_t)std::max(curnnz, 1));
-  if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return cleanup(fail(SPGEMM_ERR_NOMEM, "host malloc failed")); }
-  if ((rc = spgemm_hip_memcpy_d2h(hI, dtI, sizeof(int) * ((size_t)rows + 1))) ||
-      (rc = spgemm_hip_memcpy_d2h(hJ, dtJ, sizeof(int) * (size_t)curnnz)) ||
-      (rc = spgemm_hip_memcpy_d2h(hA, dtA, sizeof(float) * (size_t)curnnz))) { free(hI); free(hJ); free(hA); return cleanup(rc); }
-  *oIA = hI; *oJA = hJ; *oA = hA; *onnz = curnnz;
-  return cleanup(SPGEMM_OK);
+  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(N.nnz, 1));
+  float* hA = (float*)malloc(sizeof(float) * (size_t)std::max(N.nnz, 1));
+  if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return fail(SPGEMM_ERR_NOMEM, "host malloc failed"); }
+  if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) ||
+      (rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) ||
+      (rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(float) * (size_t)N.nnz))) { free(hI); free(hJ); free(hA); return rc; }
+  *oIA = hI; *oJA = hJ; *oA = hA; *onnz = N.nnz;
+  return SPGEMM_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1996,14 +2033,12 @@ static int sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, V* dC) {
   if (m == 0) return SPGEMM_OK;
   clear_stale_hip_error();
   hipStream_t s = h->stream;
-  int* dcnt = nullptr;
-  int* JS = nullptr;
-  V* CS = nullptr;
-  auto cleanup = [&](int rc) { pool().release(dcnt); pool().release(JS); pool().release(CS); return rc; };
-  auto hipfail = [&](const char* what) { return cleanup(fail(SPGEMM_ERR_HIP, "sort rows: %s: %s", what, hipGetErrorString(hipGetLastError()))); };
-  if (pool().alloc((void**)&dcnt, sizeof(int)) != hipSuccess) return hipfail("allocation");
+  DevBuf<int> dcnt, JS;
+  DevBuf<V> CS;
+  auto hipfail = [&](const char* what) { return fail(SPGEMM_ERR_HIP, "sort rows: %s: %s", what, hipGetErrorString(hipGetLastError())); };
+  if (dcnt.alloc(1) != hipSuccess) return hipfail("allocation");
   if (hipMemsetAsync(dcnt, 0, sizeof(int), s) != hipSuccess) return hipfail("memset");
-  hipLaunchKernelGGL(k_sort_rows<V>, dim3(clampi(m, 1, h->numCU * 8)), dim3(256), 0, s, m, dIC, dJC, dC, dcnt);
+  hipLaunchKernelGGL(k_sort_rows<V>, dim3(clampi(m, 1, h->numCU * 8)), dim3(256), 0, s, m, dIC, dJC, dC, dcnt.p);
   int info[2] = {0, 0};                                // unsorted rows longer than SORT_MAX, nnz
   if (hipMemcpyAsync(&info[0], dcnt, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipMemcpyAsync(&info[1], dIC + m, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -2011,15 +2046,13 @@ static int sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, V* dC) {
     return hipfail("short rows");
   if (info[0] > 0 && info[1] > 0) {
     // the long rows sort between their segment of (JC, C) and the same segment of a scratch copy
-    if (pool().alloc((void**)&JS, sizeof(int) * (size_t)info[1]) != hipSuccess ||
-        pool().alloc((void**)&CS, sizeof(V) * (size_t)info[1]) != hipSuccess)
-      return hipfail("scratch allocation");
+    if (JS.alloc((size_t)info[1]) != hipSuccess || CS.alloc((size_t)info[1]) != hipSuccess) return hipfail("scratch allocation");
     // column bits: the columns of a valid CSR are < 2^31; take the width from the largest possible key
     const int keyBits = 31;
-    hipLaunchKernelGGL(k_sort_long_rows<V>, dim3(clampi(info[0], 1, h->numCU * 4)), dim3(256), 0, s, m, dIC, dJC, dC, JS, CS, keyBits);
+    hipLaunchKernelGGL(k_sort_long_rows<V>, dim3(clampi(info[0], 1, h->numCU * 4)), dim3(256), 0, s, m, dIC, dJC, dC, JS.p, CS.p, keyBits);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return hipfail("long rows");
   }
-  return cleanup(SPGEMM_OK);
+  return SPGEMM_OK;
 }
 
 extern "C" int hip_csr_sort_rows(spgemm_handle* h, int m, const int* dIC, int* dJC, float* dC) {
