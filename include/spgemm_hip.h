@@ -389,6 +389,57 @@ int hip_csr_transpose(spgemm_handle* h, int m, int n, int nnz, const int* dIA, c
 int hip_csr_transpose_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
                           int** dIT, int** dJT, double** dAT);
 
+/* ---- comparing two device CSRs: diff report, differs, differsStats -------------------------------------------------------
+ * All CSR arrays are device pointers, reports and counts are host memory; h == NULL = the default handle; a call returns
+ * after the device work has completed.  Argument checks (null out / counts, negative size, null rowPtr, nnz > 0 with null
+ * arrays, npercents outside [0,64], npercents > 0 with null percents, a negative or NaN tolerance -> SPGEMM_ERR_ARG) run
+ * before any device is touched.  A and B are both m x n with every row strictly ascending by column (hip_csr_sort_rows
+ * gives that for a row without repeated columns).  Both rowPtr arrays are validated by a read-only pass that completes
+ * before a rowPtr value becomes an address; columns are only compared.  A bad rowPtr, or a row that is not strictly
+ * ascending -> SPGEMM_ERR_INPUT with a message, the report is left zeroed, the handle stays usable.  m == 0 or two empty
+ * matrices are valid: a zeroed report with the first_* fields at -1.
+ *
+ * One report serves the reference's comparisons (B is the reference side, as in CSR::isRelativeEqual):
+ *   CSR::differs          nlibs/CSR.cc:210-240    sum_sq
+ *   CSR::isEqual          nlibs/CSR.h:195-245     same shape and nnz, rows_len_differ == 0, max_abs_err <= 1e-7 and
+ *                                                 max_abs_only_b <= 1e-7
+ *   CSR::isRelativeEqual  nlibs/CSR.h:284-320     rel_tol = maxRelativeError, abs_tol = 1e-8: beyond == 0 and
+ *                                                 max_abs_only_b <= 1e-8
+ *   the parity rule       (the end-of-run check Mt.makeOrdered(); oMt.makeOrdered(); Mt.isEqual(oMt), nrmcl.cc:26-28, on
+ *                         device arrays)          rows_len_differ == only_a == only_b == beyond == 0 with abs_tol = 0
+ * Every term is computed in double from the stored values.  sum_sq is reduced in a fixed order without floating-point
+ * atomics: two calls on the same input return the same bits. */
+typedef struct spgemm_csr_diff {
+  int       rows_len_differ;   /* rows whose lengths differ                                  */
+  int       first_len_row;     /* lowest such row, -1 if none                                */
+  long long only_a, only_b;    /* entries whose column is absent from the same row of the other matrix */
+  int       first_only_row;    /* lowest row holding one, -1                                 */
+  long long beyond;            /* common columns with !(|a-b| <= abs_tol + rel_tol*|b|): a NaN on either side counts */
+  int       first_beyond_row;  /* lowest such row, -1                                        */
+  double    max_abs_err;       /* over common columns, |a-b| (NaN terms skipped)             */
+  double    max_rel_err;       /* over common columns with b != 0, |a-b|/|b| (NaN skipped)   */
+  double    max_abs_only_a, max_abs_only_b;  /* largest |value| among only_a / only_b entries, 0 if none */
+  double    sum_sq;            /* CSR::differs: sum (a-b)^2 over common + a^2 over only_a + b^2 over only_b */
+} spgemm_csr_diff;
+int hip_csr_diff(spgemm_handle* h, int m, int n,
+                 const int* dIA, const int* dJA, const float* dA, int nnzA,
+                 const int* dIB, const int* dJB, const float* dB, int nnzB,
+                 double rel_tol, double abs_tol, spgemm_csr_diff* out);
+int hip_csr_diff_f64(spgemm_handle* h, int m, int n,
+                     const int* dIA, const int* dJA, const double* dA, int nnzA,
+                     const int* dIB, const int* dJB, const double* dB, int nnzB,
+                     double rel_tol, double abs_tol, spgemm_csr_diff* out);
+
+/* CSR::differsStats (nlibs/CSR.cc:381-415) from the two device rowPtr arrays alone: counts[npercents + 4] (host).  Row by
+ * row with acount / bcount the lengths in A / B: acount == 0 && bcount > 0 -> slot n+1; both zero -> slot n+2; equal ->
+ * slot n+3; otherwise percent = (bcount - acount) / (QValue)acount goes to the first k with percent < percents[k], else
+ * to slot n (n = npercents <= 64; percents is a host array).  The division and the compare are done in float here and in
+ * double in the _f64 twin, as QValue is.  The rowPtr values are only subtracted. */
+int hip_csr_differsStats(spgemm_handle* h, int m, const int* dIA, const int* dIB,
+                         const float* percents, int npercents, int* counts);
+int hip_csr_differsStats_f64(spgemm_handle* h, int m, const int* dIA, const int* dIB,
+                             const double* percents, int npercents, int* counts);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

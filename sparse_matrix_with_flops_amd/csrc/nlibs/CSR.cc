@@ -300,6 +300,16 @@ void gpuRmclIter(const int maxIter, const CSR Mgt, CSR& Mt) {
   Mt.init(oA, oJ, oI, Mgt.rows, Mgt.cols, on);
 }
 
+CSR gpuRmclIterDevice(const int maxIter, const CSR& dMgt, const CSR& dMt) {
+  CSR dN;
+  hip_or_die(hip_gpuRmclIter_device(0, maxIter, dMt.rows, dMt.cols, dMgt.rowPtr, dMgt.colInd, dMgt.values, dMgt.nnz,
+                                    dMt.rowPtr, dMt.colInd, dMt.values, dMt.nnz, &dN.rowPtr, &dN.colInd, &dN.values, &dN.nnz),
+             "gpuRmclIterDevice");
+  dN.rows = dMt.rows;
+  dN.cols = dMt.cols;
+  return dN;
+}
+
 static spgemm_group* make_group(int shards) {
   int ndev = 0;
   hip_or_die(spgemm_hip_device_count(&ndev), "spgemm_hip_device_count");
@@ -376,6 +386,58 @@ std::vector<int> CSR::differsStats(const CSR& B, const std::vector<QValue>& perc
     ++counts[k];
   }
   return counts;
+}
+
+QValue CSR::differs(const CSR& B) const {         // nlibs/CSR.cc:210-240 (its last loop runs to B's row end here)
+  QValue sum = 0;
+  for (int i = 0; i < rows; ++i) {
+    int j = rowPtr[i], k = B.rowPtr[i];
+    const int je = rowPtr[i + 1], ke = B.rowPtr[i + 1];
+    while (j < je && k < ke) {
+      const QValue a = values[j], b = B.values[k];
+      if (colInd[j] == B.colInd[k]) { sum += (a - b) * (a - b); ++j; ++k; }
+      else if (colInd[j] < B.colInd[k]) { sum += a * a; ++j; }
+      else { sum += b * b; ++k; }
+    }
+    for (; j < je; ++j) sum += values[j] * values[j];
+    for (; k < ke; ++k) sum += B.values[k] * B.values[k];
+  }
+  return sum;
+}
+
+// one hip_csr_diff report of two device CSRs of the same shape (exits on error like the other device wrappers)
+static spgemm_csr_diff device_diff(const CSR& dA, const CSR& dB, double rel, double abs_tol, const char* what) {
+  if (dA.rows != dB.rows || dA.cols != dB.cols) {
+    printf("%s: A is %dx%d but B is %dx%d\n", what, dA.rows, dA.cols, dB.rows, dB.cols);
+    exit(EXIT_FAILURE);
+  }
+  spgemm_csr_diff d;
+  hip_or_die(hip_csr_diff(0, dA.rows, dA.cols, dA.rowPtr, dA.colInd, dA.values, dA.nnz, dB.rowPtr, dB.colInd, dB.values,
+                          dB.nnz, rel, abs_tol, &d), what);
+  return d;
+}
+
+QValue CSR::gpuDiffers(const CSR& dB) const { return (QValue)device_diff(*this, dB, 0.0, 0.0, "gpuDiffers").sum_sq; }
+
+std::vector<int> CSR::gpuDiffersStats(const CSR& dB, const std::vector<QValue>& percents) const {
+  if (rows != dB.rows) { printf("gpuDiffersStats: %d rows against %d\n", rows, dB.rows); exit(EXIT_FAILURE); }
+  std::vector<int> counts(percents.size() + 4, 0);
+  hip_or_die(hip_csr_differsStats(0, rows, rowPtr, dB.rowPtr, percents.data(), (int)percents.size(), counts.data()),
+             "gpuDiffersStats");
+  return counts;
+}
+
+bool CSR::gpuIsEqual(const CSR& dB) const {
+  bool same = true;
+  if (rows != dB.rows) { printf("rows = %d\tB_rows = %d\n", rows, dB.rows); same = false; }
+  if (cols != dB.cols) { printf("cols = %d\tB_cols = %d\n", cols, dB.cols); same = false; }
+  if (nnz != dB.nnz) { printf("nnz = %d\tB_nnz = %d\n", nnz, dB.nnz); same = false; }
+  if (!same) return false;
+  const spgemm_csr_diff d = device_diff(*this, dB, 0.0, 1e-7, "gpuIsEqual");
+  if (d.rows_len_differ) { printf("row %d: lengths differ (%d rows do)\n", d.first_len_row, d.rows_len_differ); return false; }
+  if (d.max_abs_err > 1e-7) { printf("row %d: values differ, max |dv| = %e\n", d.first_beyond_row, d.max_abs_err); return false; }
+  if (d.max_abs_only_b > 1e-7) { printf("row %d: a column of B is absent, |b| up to %e\n", d.first_only_row, d.max_abs_only_b); return false; }
+  return true;
 }
 
 std::vector<int> CSR::gpuNnzStats() const {

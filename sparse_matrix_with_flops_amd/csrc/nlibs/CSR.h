@@ -63,5 +63,15 @@ struct CSR {
   // counts[k] = rows whose relative change (len_B - len_A) / len_A is below percents[k] (first such k), counts[n] = the
   // rest, then three more: rows that appeared (0 -> >0), rows empty in both, rows unchanged.  n = percents.size().
   std::vector<int> differsStats(const CSR& B, const std::vector<QValue>& percents) const;
+  // the squared Frobenius norm of *this - B (nlibs/CSR.cc:210-240: how far an R-MCL iteration moved Mt); both operands
+  // ordered (makeOrdered), summed in QValue by the reference's two-pointer merge
+  QValue differs(const CSR& B) const;
+
+  // the same three on DEVICE CSRs (after toGpuCSR, rows ordered: hip_csr_sort_rows) through hip_csr_diff /
+  // hip_csr_differsStats, nothing downloaded.  gpuDiffers accumulates in double and rounds once to QValue.  gpuIsEqual is
+  // isEqual's rule (dims, nnz, row lengths, |dv| <= 1e-7) and prints the first offending row like isEqual does.
+  QValue gpuDiffers(const CSR& dB) const;
+  std::vector<int> gpuDiffersStats(const CSR& dB, const std::vector<QValue>& percents) const;
+  bool gpuIsEqual(const CSR& dB) const;
 };
 #endif

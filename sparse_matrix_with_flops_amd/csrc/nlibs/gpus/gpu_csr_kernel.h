@@ -15,6 +15,8 @@ std::vector<int> gpuFlopsClassify(const CSR& dA, const CSR& dB, int** drowIdsp, 
 CSR sgpuSpMMWrapper(const CSR& dA, const CSR& dB, int* drowIds, const std::vector<int>& hv, int* dflops);
 CSR scudaSpMM(const CSR& hA, const CSR& hB);
 void gpuRmclIter(const int maxIter, const CSR Mgt, CSR& Mt);
+// the same loop on DEVICE CSRs (hip_gpuRmclIter_device): returns the new Mt as a device CSR, the inputs are left alone
+CSR gpuRmclIterDevice(const int maxIter, const CSR& dMgt, const CSR& dMt);
 // Several GPUs (no counterpart in the reference, which is single-device: SURVEY.md section 2.4; the seam is the flops-balanced
 // row cut its CPU kernels make for their threads, nlibs/tools/util.cc:123-135).  HOST CSRs in, HOST CSR out: rows of A cut
 // into `shards` blocks of equal flops, one shard per device (shards > devices: logical shards share devices), B replicated,

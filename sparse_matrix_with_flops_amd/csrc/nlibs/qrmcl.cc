@@ -35,7 +35,10 @@ CSR RMCL(const char iname[], int maxIters, RunOptions runOptions) {
     // from Mt to the new Mt (CSR::differsStats).  The thresholds are the reference's -- its int array {-30, -20, -5, 0, 5,
     // 20, 30, 100} read as QValue and compared with the FRACTION (len' - len) / len, so in practice rows land in the
     // "< 0" bucket, the "< 5" bucket, or the three special buckets; kept as it is, the file format is the contract.
-    // The loop then runs one iteration per call (the matrix comes back to the host every time: this is a report mode).
+    // The loop runs one iteration per call.  On one device Mgt and Mt are uploaded once, every iteration is one
+    // hip_gpuRmclIter_device(1) on the device arrays followed by hip_csr_differsStats on the old and the new rowPtr, and Mt
+    // comes back once at the end.  With SPGEMM_RMCL_DEVICES / SPGEMM_RMCL_SHARDS set the sharded loop is asked for: that
+    // route stays one gpuRmclIter(1) per iteration through the host.
     static const int cpercents[] = {-30, -20, -5, 0, 5, 20, 30, 100};
     const std::vector<QValue> percents(cpercents, cpercents + sizeof(cpercents) / sizeof(int));
     FILE* fp = fopen("percent.stats", "w");
@@ -44,14 +47,30 @@ CSR RMCL(const char iname[], int maxIters, RunOptions runOptions) {
     fprintf(fp, "percent\t");
     for (size_t i = 0; i < percents.size(); ++i) fprintf(fp, "%lf ", (double)percents[i]);
     fprintf(fp, "\n");
-    for (int iter = 0; iter < maxIters; ++iter) {
-      CSR old = Mt.deepCopy();
-      gpuRmclIter(1, Mgt, Mt);
-      const std::vector<int> counts = old.differsStats(Mt, percents);
+    auto report = [&](int iter, const std::vector<int>& counts) {
       fprintf(fp, "%d :\t", iter);
       for (size_t i = 0; i < counts.size(); ++i) fprintf(fp, "%d ", counts[i]);
       fprintf(fp, "\n");
-      old.dispose();
+    };
+    if (getenv("SPGEMM_RMCL_DEVICES") || getenv("SPGEMM_RMCL_SHARDS")) {
+      for (int iter = 0; iter < maxIters; ++iter) {
+        CSR old = Mt.deepCopy();
+        gpuRmclIter(1, Mgt, Mt);
+        report(iter, old.differsStats(Mt, percents));
+        old.dispose();
+      }
+    } else {
+      CSR dMgt = Mgt.toGpuCSR(), dMt = Mt.toGpuCSR();
+      for (int iter = 0; iter < maxIters; ++iter) {
+        CSR dNew = gpuRmclIterDevice(1, dMgt, dMt);
+        report(iter, dMt.gpuDiffersStats(dNew, percents));
+        dMt.deviceDispose();
+        dMt = dNew;
+      }
+      Mt.dispose();
+      Mt = dMt.toCpuCSR();
+      dMt.deviceDispose();
+      dMgt.deviceDispose();
     }
     fclose(fp);
   } else {

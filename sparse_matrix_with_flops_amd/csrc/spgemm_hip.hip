@@ -2100,6 +2100,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 #include "reorder_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
+// comparing two device CSRs: diff report, differs, differsStats
+// ------------------------------------------------------------------------------------------------
+#include "compare_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL
 // ------------------------------------------------------------------------------------------------
 #include "sharded.hpp"

@@ -9,6 +9,8 @@ Mirrors (reference file:line):
   gpuFlopsClassify(dA, dB)    gpuFlopsClassify                 mindex2-cuda/flops.cu:110-185
   sgpuSpMMWrapper(...)        sgpuSpMMWrapper                  mindex2-cuda/kernel.cu:311-427
   scudaSpMM(hA, hB)           scudaSpMM                        mindex2-cuda/nGpuSpMM.cc:245-279
+  CSR.diff / differs / isEqual / isRelativeEqual / isParityEqual / differsStats
+                              CSR::differs, isEqual, ...       nlibs/CSR.cc:210-240, 381-415; nlibs/CSR.h:195-320
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -51,6 +53,7 @@ EXPORTS = [
     "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
     "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
     "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
+    "hip_csr_diff", "hip_csr_diff_f64", "hip_csr_differsStats", "hip_csr_differsStats_f64",
 ]
 VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
@@ -64,6 +67,17 @@ class SpgemmError(RuntimeError):
 
 class BinReport(C.Structure):
     _fields_ = [("rows", C.c_int), ("rows_differ", C.c_int), ("first_bad_row", C.c_int), ("max_rel_err", C.c_double)]
+
+
+class CsrDiff(C.Structure):
+    """spgemm_csr_diff: the report of hip_csr_diff (include/spgemm_hip.h)"""
+    _fields_ = [("rows_len_differ", C.c_int), ("first_len_row", C.c_int), ("only_a", C.c_longlong), ("only_b", C.c_longlong),
+                ("first_only_row", C.c_int), ("beyond", C.c_longlong), ("first_beyond_row", C.c_int),
+                ("max_abs_err", C.c_double), ("max_rel_err", C.c_double), ("max_abs_only_a", C.c_double),
+                ("max_abs_only_b", C.c_double), ("sum_sq", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class HostApiStats(C.Structure):
@@ -156,6 +170,11 @@ def lib():
         L.hip_csr_transpose.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + \
             [C.POINTER(C.c_void_p)] * 3
         L.hip_csr_transpose_f64.argtypes = L.hip_csr_transpose.argtypes
+        L.hip_csr_diff.argtypes = [C.c_void_p, C.c_int, C.c_int] + dev_in + dev_in + [C.c_double, C.c_double,
+                                                                                          C.POINTER(CsrDiff)]
+        L.hip_csr_diff_f64.argtypes = L.hip_csr_diff.argtypes
+        L.hip_csr_differsStats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _F, C.c_int, _I]
+        L.hip_csr_differsStats_f64.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _D, C.c_int, _I]
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -447,6 +466,75 @@ class CSR:
         finally:
             dev_free(dp)
 
+    # -- comparison (nlibs/CSR.cc:210-240, 381-415; nlibs/CSR.h:195-245, 284-320) through hip_csr_diff /
+    #    hip_csr_differsStats: a host CSR is uploaded for the call and the copy released, a device CSR is used in place.
+    #    Rows of both operands must be strictly ascending by column (makeOrdered / sort_rows_device). ------------------
+    def _with_device_pair(self, B, fn):
+        """fn(device self, device B); shape / dtype mismatch raises before any device work"""
+        if (self.rows, self.cols) != (B.rows, B.cols):
+            raise SpgemmError(f"shape mismatch: A is {self.rows}x{self.cols}, B is {B.rows}x{B.cols}")
+        _common_dtype(self, B)
+        made = []
+        try:
+            pair = []
+            for M in (self, B):
+                if M.on_device:
+                    pair.append(M)
+                elif M is self and pair:                    # A.diff(A): one upload
+                    pair.append(pair[0])
+                else:
+                    made.append(M.toGpuCSR())
+                    pair.append(made[-1])
+            return fn(pair[0], pair[1])
+        finally:
+            for d in made:
+                d.deviceDispose()
+
+    def diff(self, B, rel=1e-6, abs=0.0, handle=None):
+        """hip_csr_diff of self against B (B is the reference side) -> CsrDiff"""
+        raw = csr_diff_raw_f64 if _value_dtype(self.dtype) == np.float64 else csr_diff_raw
+        return self._with_device_pair(B, lambda a, b: raw(handle, a.rows, a.cols, a.rowPtr, a.colInd, a.values, a.nnz,
+                                                          b.rowPtr, b.colInd, b.values, b.nnz, rel, abs))
+
+    def differs(self, B, handle=None):
+        """CSR::differs (nlibs/CSR.cc:210-240): the squared Frobenius norm of self - B, accumulated in double"""
+        return float(self.diff(B, handle=handle).sum_sq)
+
+    def differsStats(self, B, percents, handle=None):
+        """CSR::differsStats (nlibs/CSR.cc:381-415) -> list of len(percents) + 4 counts; only the row pointers are read"""
+        if self.rows != B.rows:
+            raise SpgemmError(f"shape mismatch: A has {self.rows} rows, B has {B.rows}")
+        dt = _common_dtype(self, B)
+        ups = [None if M.on_device else h2d(M.rowPtr) for M in (self, B)]
+        try:
+            ia, ib = [M.rowPtr if u is None else u for M, u in zip((self, B), ups)]
+            return csr_differs_stats_raw(handle, self.rows, ia, ib, percents, dtype=dt)
+        finally:
+            for u in ups:
+                dev_free(u)
+
+    def isEqual(self, B, handle=None):
+        """CSR::isEqual (nlibs/CSR.h:195-245): same rows / cols / nnz and row lengths, values within 1e-7 absolute (an
+        entry only B holds is compared with 0, as the reference's dense row does)"""
+        if (self.rows, self.cols, self.nnz) != (B.rows, B.cols, B.nnz):
+            return False
+        d = self.diff(B, handle=handle)
+        return d.rows_len_differ == 0 and d.max_abs_err <= 1e-7 and d.max_abs_only_b <= 1e-7
+
+    def isRelativeEqual(self, B, maxRelativeError, handle=None):
+        """CSR::isRelativeEqual (nlibs/CSR.h:284-320): every entry of B with |b| > 1e-8 is met within maxRelativeError"""
+        if (self.rows, self.cols) != (B.rows, B.cols):
+            return False
+        d = self.diff(B, rel=float(maxRelativeError), abs=1e-8, handle=handle)
+        return d.beyond == 0 and d.max_abs_only_b <= 1e-8
+
+    def isParityEqual(self, B, rel=1e-6, handle=None):
+        """the parity rule: identical structure, values within `rel` relative"""
+        if (self.rows, self.cols, self.nnz) != (B.rows, B.cols, B.nnz):
+            return False
+        d = self.diff(B, rel=rel, abs=0.0, handle=handle)
+        return d.rows_len_differ == 0 and d.only_a == 0 and d.only_b == 0 and d.beyond == 0
+
 
 def _need_square(M, what):
     if M.rows != M.cols:
@@ -697,6 +785,39 @@ def csr_transpose_raw(handle, m, n, nnz, IA, JA, VA):
 def csr_transpose_raw_f64(handle, m, n, nnz, IA, JA, VA):
     """csr_transpose_raw with float64 values (hip_csr_transpose_f64)."""
     return _csr_transpose(lib().hip_csr_transpose_f64, "hip_csr_transpose_f64", handle, m, n, nnz, IA, JA, VA)
+
+
+def _csr_diff(fn, name, handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol):
+    out = CsrDiff()
+    _check(fn(handle.ptr if handle else None, int(m), int(n), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
+              C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), float(rel), float(abs_tol), C.byref(out)), name)
+    return out
+
+
+def csr_diff_raw(handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel=1e-6, abs_tol=0.0):
+    """hip_csr_diff on raw device pointers (float32 values) -> CsrDiff"""
+    return _csr_diff(lib().hip_csr_diff, "hip_csr_diff", handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol)
+
+
+def csr_diff_raw_f64(handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel=1e-6, abs_tol=0.0):
+    """csr_diff_raw with float64 values (hip_csr_diff_f64)"""
+    return _csr_diff(lib().hip_csr_diff_f64, "hip_csr_diff_f64", handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel,
+                     abs_tol)
+
+
+def csr_differs_stats_raw(handle, m, IA, IB, percents, dtype=np.float32):
+    """hip_csr_differsStats (dtype float32) / _f64 (float64) on two raw device rowPtr arrays; percents: host sequence.
+    -> list of len(percents) + 4 counts"""
+    f64 = _value_dtype(dtype) == np.float64
+    pc = np.ascontiguousarray(percents, dtype=np.float64 if f64 else np.float32)
+    if pc.ndim != 1:
+        raise SpgemmError("differsStats: percents must be one-dimensional")
+    counts = (C.c_int * (len(pc) + 4))()
+    fn, name = (lib().hip_csr_differsStats_f64, "hip_csr_differsStats_f64") if f64 else \
+        (lib().hip_csr_differsStats, "hip_csr_differsStats")
+    _check(fn(handle.ptr if handle else None, int(m), C.c_void_p(IA), C.c_void_p(IB),
+              pc.ctypes.data_as(_D if f64 else _F) if len(pc) else None, len(pc), counts), name)
+    return [int(x) for x in counts]
 
 
 def permutation_transpose_raw(handle, length, dP, dPt):
