@@ -440,6 +440,58 @@ int hip_csr_differsStats(spgemm_handle* h, int m, const int* dIA, const int* dIB
 int hip_csr_differsStats_f64(spgemm_handle* h, int m, const int* dIA, const int* dIB,
                              const double* percents, int npercents, int* counts);
 
+/* ---- column-partitioned CSR (PCSR): split into column blocks, blockwise product, join ---------------------------------
+ * All CSR arrays are device pointers; blockPtr, the block tables (arrays of c device pointers / c counts) and the result
+ * counts are host memory; h == NULL = the default handle; a call returns after the device work has completed; outputs
+ * come from the library pool (release with spgemm_hip_free).  Argument checks (c outside [1, SPGEMM_PCSR_MAX_BLOCKS], a
+ * null output or table, a negative size, nnz > 0 with null arrays -> SPGEMM_ERR_ARG; c * (m + 1) or a total nnz beyond
+ * int32 -> SPGEMM_ERR_OVERFLOW) run before any device is touched.  Every value that becomes an address (rowPtr, the
+ * column that selects a block) is validated by a read-only pass whose flag the host reads before it is used: bad input
+ * -> SPGEMM_ERR_INPUT with a message.  On any error the outputs are NULL, nothing stays allocated, the handle stays usable.
+ *
+ * The layout is the reference's PCSR (nlibs/PCSR.h:5-10): stride = (n + c - 1) / c (1 when n == 0); an entry with column
+ * col belongs to block b = col / stride, its block-local column is col - b * stride; every block is an m x stride CSR. */
+#define SPGEMM_PCSR_MAX_BLOCKS 64
+
+/* PCSR::PCSR(const CSR& csr, const int c) (nlibs/PCSR.cc:3-56), the same packed arrays:
+ *   *dIP       device int[c * (m + 1)]: block b's rowPtr at b * (m + 1); it starts at 0 and ends at the block's nnz
+ *   *dJP, *dP  device, nnz entries each: block b's at blockPtr[b] (local columns)
+ *   blockPtr   host int[c + 1]
+ * Inside a block the entries are in row order, inside a row in A's storage order (the split is stable); A's rows need
+ * not be sorted and may repeat a column.  Block b is formed by pointer arithmetic (dIP + b * (m + 1), dJP + blockPtr[b],
+ * dP + blockPtr[b], nnz = blockPtr[b + 1] - blockPtr[b]); as PCSR::dispose (nlibs/PCSR.h:39-50) frees the base arrays
+ * only, a caller releases only the three base pointers.  m == 0 or nnz == 0: every rowPtr zero; c > n: the trailing
+ * blocks are empty.  A bad rowPtr or a column outside [0, n) -> SPGEMM_ERR_INPUT. */
+int hip_csr_split_columns(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                          int c, int** dIP, int** dJP, float** dP, int* blockPtr);
+int hip_csr_split_columns_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                              int c, int** dIP, int** dJP, double** dP, int* blockPtr);
+
+/* The inverse view, the row walk of PCSR::isEqual (nlibs/PCSR.h:69-86) written out as a CSR: c device CSRs of shape
+ * m x stride (dIB[b], dJB[b], dB[b], nnzB[b]; separate allocations, as a product loop leaves them, or views into a
+ * packed split) become one m x n CSR.  Row i of the result is block 0's row i, then block 1's, and so on; each block's
+ * in-row order is kept; block b's columns gain b * stride.  join(split(A)) is therefore A with every row stably
+ * partitioned by block: A itself, bit for bit, whenever A's rows are column-sorted.  Every block's rowPtr is validated
+ * against its count; a local column outside [0, stride) or a global column >= n -> SPGEMM_ERR_INPUT (the result would
+ * not be a valid CSR). */
+int hip_pcsr_join(spgemm_handle* h, int m, int n, int c, const int* const* dIB, const int* const* dJB,
+                  const float* const* dB, const int* nnzB, int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_pcsr_join_f64(spgemm_handle* h, int m, int n, int c, const int* const* dIB, const int* const* dJB,
+                      const double* const* dB, const int* nnzB, int** dIC, int** dJC, double** dC, int* nnzC);
+
+/* PCSR spmm(const CSR& A, const PCSR& pB, stride) (correctTests/pcsrTest.cc:7-19): C_b = A * B_b for the c blocks of a
+ * k x n matrix B (each k x stride, given as for hip_pcsr_join); A is m x k.  dIC, dJC, dC, nnzC are host arrays of
+ * length c; every C_b (m x stride, local columns, rows unsorted) is its own allocation.  It is a host loop of c calls of
+ * hip_gpuSpMM / hip_gpuSpMM_f64 on the same handle, no product kernel of its own.  If block b fails, the earlier
+ * results are freed, every output slot is NULL and the failing block's status is returned.  spgemm_hip_get_stats
+ * afterwards describes the LAST block's product only. */
+int hip_pcsr_spmm(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA, int m, int k, int n, int c,
+                  const int* const* dIB, const int* const* dJB, const float* const* dB, const int* nnzB,
+                  int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_pcsr_spmm_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA, int m, int k, int n, int c,
+                      const int* const* dIB, const int* const* dJB, const double* const* dB, const int* nnzB,
+                      int** dIC, int** dJC, double** dC, int* nnzC);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

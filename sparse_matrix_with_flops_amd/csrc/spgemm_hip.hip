@@ -2105,6 +2105,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 #include "compare_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
+// column-partitioned CSR: split into column blocks, blockwise product, join
+// ------------------------------------------------------------------------------------------------
+#include "pcsr_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL
 // ------------------------------------------------------------------------------------------------
 #include "sharded.hpp"

@@ -11,6 +11,8 @@ Mirrors (reference file:line):
   scudaSpMM(hA, hB)           scudaSpMM                        mindex2-cuda/nGpuSpMM.cc:245-279
   CSR.diff / differs / isEqual / isRelativeEqual / isParityEqual / differsStats
                               CSR::differs, isEqual, ...       nlibs/CSR.cc:210-240, 381-415; nlibs/CSR.h:195-320
+  PCSR(dM, c) / join / spmm_left / isEqual
+                              struct PCSR, spmm(A, pB)         nlibs/PCSR.h:5-100, nlibs/PCSR.cc:3-56, correctTests/pcsrTest.cc:7-19
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -54,7 +56,10 @@ EXPORTS = [
     "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
     "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
     "hip_csr_diff", "hip_csr_diff_f64", "hip_csr_differsStats", "hip_csr_differsStats_f64",
+    "hip_csr_split_columns", "hip_csr_split_columns_f64", "hip_pcsr_join", "hip_pcsr_join_f64",
+    "hip_pcsr_spmm", "hip_pcsr_spmm_f64",
 ]
+PCSR_MAX_BLOCKS = 64
 VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
 XCHG_NAMES = {0: "auto", 1: "rccl", 2: "peer", 3: "host"}
@@ -175,6 +180,14 @@ def lib():
         L.hip_csr_diff_f64.argtypes = L.hip_csr_diff.argtypes
         L.hip_csr_differsStats.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _F, C.c_int, _I]
         L.hip_csr_differsStats_f64.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, _D, C.c_int, _I]
+        table = [C.POINTER(C.c_void_p)] * 3 + [_I]         # host arrays: c rowPtr / colInd / values pointers, c counts
+        L.hip_csr_split_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_csr_split_columns_f64.argtypes = L.hip_csr_split_columns.argtypes
+        L.hip_pcsr_join.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + table + [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_pcsr_join_f64.argtypes = L.hip_pcsr_join.argtypes
+        L.hip_pcsr_spmm.argtypes = [C.c_void_p] + dev_in + [C.c_int, C.c_int, C.c_int, C.c_int] + table + table
+        L.hip_pcsr_spmm_f64.argtypes = L.hip_pcsr_spmm.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1143,3 +1156,148 @@ def sort_rows_device(dC, handle=None):
     fn, name = (lib().hip_csr_sort_rows_f64, "hip_csr_sort_rows_f64") if f64 else (lib().hip_csr_sort_rows, "hip_csr_sort_rows")
     _check(fn(handle.ptr if handle else None, dC.rows, C.c_void_p(dC.rowPtr), C.c_void_p(dC.colInd),
               C.c_void_p(dC.values)), name)
+
+
+# ---------------------------------------------------------------------------------------------
+# column-partitioned CSR (include/spgemm_hip.h "column-partitioned CSR"): split, blockwise product, join
+# ---------------------------------------------------------------------------------------------
+def _pcsr_fn(name, dtype):
+    f64 = _value_dtype(dtype) == np.float64
+    name = name + "_f64" if f64 else name
+    return getattr(lib(), name), name
+
+
+def _block_table(blocks):
+    """blocks: sequence of (rowPtr, colInd, values, nnz) device pointers -> the four host arrays the C side takes"""
+    c = len(blocks)
+    cols = [(C.c_void_p * c)(*[b[i] for b in blocks]) for i in range(3)]
+    return cols + [(C.c_int * c)(*[int(b[3]) for b in blocks])]
+
+
+def csr_split_columns_raw(handle, m, n, nnz, IA, JA, VA, c, dtype=np.float32):
+    """hip_csr_split_columns (float32) / _f64 on raw device pointers -> (dIP, dJP, dP, blockPtr): the packed arrays from
+    the library pool (release the three with dev_free) and the host list of c + 1 block starts."""
+    fn, name = _pcsr_fn("hip_csr_split_columns", dtype)
+    ip, jp, vp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    bp = (C.c_int * (max(int(c), 0) + 1))()
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(c),
+              C.byref(ip), C.byref(jp), C.byref(vp), bp), name)
+    return ip.value, jp.value, vp.value, [int(x) for x in bp]
+
+
+def pcsr_join_raw(handle, m, n, blocks, dtype=np.float32):
+    """hip_pcsr_join / _f64: blocks = c tuples (rowPtr, colInd, values, nnz) of device pointers, each an m x stride CSR
+    -> (dIC, dJC, dC, nnz) from the library pool (release with dev_free)."""
+    fn, name = _pcsr_fn("hip_pcsr_join", dtype)
+    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    _check(fn(handle.ptr if handle else None, int(m), int(n), len(blocks), *_block_table(blocks),
+              C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
+    return ic.value, jc.value, cv.value, nnz.value
+
+
+def pcsr_spmm_raw(handle, IA, JA, VA, nnzA, m, k, n, blocks, dtype=np.float32):
+    """hip_pcsr_spmm / _f64: A (m x k) times the c blocks of a k x n matrix -> list of c tuples (dIC, dJC, dC, nnz), each
+    its own allocation (release with dev_free).  handle.stats() afterwards describes the last block's product."""
+    fn, name = _pcsr_fn("hip_pcsr_spmm", dtype)
+    c = len(blocks)
+    ic, jc, cv, nnz = (C.c_void_p * c)(), (C.c_void_p * c)(), (C.c_void_p * c)(), (C.c_int * c)()
+    _check(fn(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA), int(m), int(k),
+              int(n), c, *_block_table(blocks), ic, jc, cv, nnz), name)
+    return [(ic[b], jc[b], cv[b], int(nnz[b])) for b in range(c)]
+
+
+class PCSR:
+    """Mirror of the reference's `struct PCSR` (nlibs/PCSR.h:5-10) on device arrays: rows, cols, c and c blocks, each a
+    device CSR of shape rows x stride with block-local columns.
+
+    PCSR(dM, c) splits a device CSR (hip_csr_split_columns): the blocks are views into three packed arrays, which
+    deviceDispose() releases (PCSR::dispose frees the base arrays only).  spmm_left(A) returns a PCSR whose blocks are
+    separate allocations (spmm(A, pB), correctTests/pcsrTest.cc:7-19)."""
+
+    def __init__(self, dM, c, handle=None):
+        assert dM.on_device
+        ip, jp, vp, bp = csr_split_columns_raw(handle, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, dM.values, c, dM.dtype)
+        self.rows, self.cols, self.c, self.dtype = dM.rows, dM.cols, int(c), dM.dtype
+        self.blockPtr = bp
+        self._base = (ip, jp, vp)
+        isz = self.dtype.itemsize
+        self.blocks = [CSR(vp + isz * bp[b], jp + 4 * bp[b], ip + 4 * b * (self.rows + 1), self.rows, self.stride,
+                           bp[b + 1] - bp[b], True, dtype=self.dtype) for b in range(self.c)]
+
+    @staticmethod
+    def from_csr(dM, c, handle=None):
+        return PCSR(dM, c, handle)
+
+    @staticmethod
+    def _of_blocks(blocks, rows, cols, dtype):
+        p = PCSR.__new__(PCSR)
+        p.rows, p.cols, p.c, p.dtype = rows, cols, len(blocks), np.dtype(dtype)
+        p.blocks, p._base = blocks, None
+        p.blockPtr = [0]
+        for b in blocks:
+            p.blockPtr.append(p.blockPtr[-1] + b.nnz)
+        return p
+
+    @property
+    def stride(self):
+        return max(1, (self.cols + self.c - 1) // self.c)
+
+    def nnz(self):
+        return sum(b.nnz for b in self.blocks)
+
+    def block(self, b):
+        """block b as a device CSR; a view: it is released with the PCSR, never on its own"""
+        return self.blocks[b]
+
+    def _table(self):
+        return [(b.rowPtr, b.colInd, b.values, b.nnz) for b in self.blocks]
+
+    def join(self, handle=None):
+        """hip_pcsr_join -> device CSR rows x cols: row i = block 0's row i, block 1's row i, ... with global columns"""
+        ic, jc, cv, nnz = pcsr_join_raw(handle, self.rows, self.cols, self._table(), self.dtype)
+        return CSR(cv, jc, ic, self.rows, self.cols, nnz, True, dtype=self.dtype)
+
+    def spmm_left(self, dA, handle=None):
+        """A * self block by block (hip_pcsr_spmm) -> PCSR of shape A.rows x cols, every block its own allocation"""
+        assert dA.on_device
+        if dA.cols != self.rows:
+            raise SpgemmError(f"shape mismatch: A is {dA.rows}x{dA.cols}, the partitioned matrix is {self.rows}x{self.cols}")
+        if _value_dtype(dA.dtype) != self.dtype:
+            raise SpgemmError(f"mixed value types: A is {dA.dtype}, the partitioned matrix is {self.dtype}")
+        outs = pcsr_spmm_raw(handle, dA.rowPtr, dA.colInd, dA.values, dA.nnz, dA.rows, dA.cols, self.cols, self._table(),
+                             self.dtype)
+        blocks = [CSR(cv, jc, ic, dA.rows, self.stride, nnz, True, dtype=self.dtype) for ic, jc, cv, nnz in outs]
+        return PCSR._of_blocks(blocks, dA.rows, self.cols, self.dtype)
+
+    def isEqual(self, dB, handle=None):
+        """PCSR::isEqual (nlibs/PCSR.h:52-100): the joined blocks against the device CSR dB by CSR.isEqual's rule, both
+        sides row-sorted on the device first (dB itself is left alone: a copy is sorted).  Another shape or nnz: False
+        before any device work."""
+        assert dB.on_device
+        if (self.rows, self.cols, self.nnz()) != (dB.rows, dB.cols, dB.nnz):
+            return False
+        if _value_dtype(dB.dtype) != self.dtype:
+            raise SpgemmError(f"mixed value types: the partitioned matrix is {self.dtype}, B is {dB.dtype}")
+        raw = csr_permute_raw_f64 if self.dtype == np.float64 else csr_permute_raw
+        mine = self.join(handle)
+        try:
+            ib, jb, vb = raw(handle, dB.rows, dB.cols, dB.nnz, dB.rowPtr, dB.colInd, dB.values)       # a deep copy
+            theirs = CSR(vb, jb, ib, dB.rows, dB.cols, dB.nnz, True, dtype=dB.dtype)
+            try:
+                sort_rows_device(mine, handle)
+                sort_rows_device(theirs, handle)
+                return mine.isEqual(theirs, handle)
+            finally:
+                theirs.deviceDispose()
+        finally:
+            mine.deviceDispose()
+
+    def deviceDispose(self):
+        if self._base is not None:
+            for p in self._base:
+                dev_free(p)
+            self._base = None
+        else:
+            for b in self.blocks:
+                b.deviceDispose()
+        self.blocks = []

@@ -1,0 +1,211 @@
+"""CPU: the column-partition entry points (hip_csr_split_columns, hip_pcsr_join, hip_pcsr_spmm and their _f64 twins) check
+their arguments without a GPU, the mirrors refuse a shape mismatch before any device work, and the numpy restatement the
+GPU tests compare against (tests/pcsr_ref.py) is pinned on a hand-worked 3 x 5 matrix whose expected split and join are
+written out below."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import pcsr_ref as pr
+import reorder_ref as rr
+from helpers import ROOT, po, random_csr
+from sparse_matrix_with_flops_amd import hipspgemm as hs
+
+ERR_ARG, ERR_OVERFLOW = 2, 3
+TWINS = ["", "_f64"]
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    import __graft_entry__ as ge
+    ge.build()
+
+
+# ---- the hand-worked pair --------------------------------------------------------------------------------------------
+def _hand():
+    """A is 3 x 5, c = 2, stride = 3:
+    row 0    (4, 1.0) (0, 2.0) (3, 3.0)      unsorted
+    row 1    --
+    row 2    (2, 4.0) (3, 5.0)"""
+    return rr.Host([0, 3, 3, 5], [4, 0, 3, 2, 3], np.array([1.0, 2.0, 3.0, 4.0, 5.0], np.float32), 3, 5)
+
+
+def test_restatement_on_the_hand_worked_pair():
+    A = _hand()
+    S = pr.split(A, 2)
+    assert S.stride == 3 and S.blockPtr.tolist() == [0, 2, 5]
+    b0, b1 = S.block(0), S.block(1)
+    assert (b0.rows, b0.cols, b1.rows, b1.cols) == (3, 3, 3, 3)
+    assert b0.rowPtr.tolist() == [0, 1, 1, 2] and b0.colInd.tolist() == [0, 2] and b0.values.tolist() == [2.0, 4.0]
+    assert b1.rowPtr.tolist() == [0, 2, 2, 3] and b1.colInd.tolist() == [1, 0, 0] and b1.values.tolist() == [1.0, 3.0, 5.0]
+    assert S.rowPtrs.tolist() == [0, 1, 1, 2, 0, 2, 2, 3]
+    J = pr.join(S.blocks(), 5)
+    assert J.rowPtr.tolist() == [0, 3, 3, 5]
+    # row 0 becomes (0, 2) (4, 1) (3, 3): block 0's entry first, block 1's in A's order; row 2 is unchanged
+    assert J.colInd.tolist() == [0, 4, 3, 2, 3] and J.values.tolist() == [2.0, 1.0, 3.0, 4.0, 5.0]
+    assert rr.same_bits(J, pr.stable_partition(A, 2)) and J.values.dtype == np.float32
+    # a column-sorted A comes back as it was
+    assert rr.same_bits(pr.stable_partition(rr.sort_rows(A), 2), rr.sort_rows(A))
+    # c = 1 is the matrix itself, c > n leaves the trailing blocks empty (stride 1)
+    one = pr.split(A, 1)
+    assert one.blockPtr.tolist() == [0, 5] and rr.same_bits(one.block(0), A)
+    seven = pr.split(A, 7)
+    assert seven.stride == 1 and seven.blockPtr.tolist() == [0, 1, 1, 2, 4, 5, 5, 5] and not seven.colInd.any()
+    assert rr.same_bits(pr.join(seven.blocks(), 5), rr.sort_rows(A))        # stride 1: partitioned by block = sorted
+    # float64 values keep their bits
+    A64 = rr.Host(A.rowPtr, A.colInd, A.values.astype(np.float64) + 2.0 ** -40, 3, 5)
+    assert pr.split(A64, 2).values.tolist() == [2.0 + 2.0 ** -40, 4.0 + 2.0 ** -40, 1.0 + 2.0 ** -40, 3.0 + 2.0 ** -40,
+                                                5.0 + 2.0 ** -40]
+
+
+def test_restatement_blockwise_product_is_the_whole_product():
+    """spmm through the oracle: the joined blockwise product has the whole product's structure, and with values from
+    {1, 2, 3} (every sum exact) its values"""
+    rng = np.random.default_rng(3)
+    A = random_csr(40, 30, 0.2, 1)
+    B = random_csr(30, 50, 0.2, 2, sorted_rows=False)
+    for M in (A, B):
+        M.values[:] = rng.integers(1, 4, size=M.nnz).astype(np.float32)
+    want = po.omp_spmm(A, B).canonical()
+    for c in (1, 2, 3, 7):
+        parts = pr.spmm(A, pr.split(B, c), po.omp_spmm)
+        assert all((P.rows, P.cols) == (40, pr.stride_of(50, c)) for P in parts)
+        got = rr.sort_rows(pr.join(parts, 50))
+        assert rr.same_bits(got, rr.Host(want.rowPtr, want.colInd, want.values, 40, 50)), c
+
+
+# ---- argument errors: no device is touched (the "device pointers" are never dereferenced) ----------------------------
+ONE = C.c_void_p(8)
+
+
+def _outs(n=3):
+    return [C.c_void_p(1) for _ in range(n)]
+
+
+def _table(c, ptr=8, nnz=0):
+    c = max(c, 1)
+    return [(C.c_void_p * c)(*[ptr] * c) for _ in range(3)] + [(C.c_int * c)(*[nnz] * c)]
+
+
+@pytest.mark.parametrize("twin", TWINS)
+def test_split_argument_errors_do_not_need_a_gpu(twin):
+    fn = getattr(hs.lib(), "hip_csr_split_columns" + twin)
+    bp = (C.c_int * 66)()
+
+    def call(m=4, n=4, nnz=0, IA=ONE, JA=None, A=None, c=2, outs=None, blockPtr=bp):
+        o = outs if outs is not None else [C.byref(x) for x in _outs()]
+        return fn(None, m, n, nnz, IA, JA, A, c, *o, blockPtr)
+
+    assert call(c=0) == ERR_ARG and call(c=-3) == ERR_ARG and call(c=65) == ERR_ARG
+    for k in range(3):
+        o = [C.byref(x) for x in _outs()]
+        o[k] = None
+        assert call(outs=o) == ERR_ARG                      # a null output
+    assert call(blockPtr=None) == ERR_ARG
+    assert call(m=-1) == ERR_ARG and call(n=-1) == ERR_ARG and call(nnz=-1) == ERR_ARG
+    assert call(IA=None) == ERR_ARG
+    assert call(nnz=3, JA=None, A=ONE) == ERR_ARG and call(nnz=3, JA=ONE, A=None) == ERR_ARG
+    assert call(m=0, nnz=3, JA=ONE, A=ONE) == ERR_ARG       # entries in a matrix without rows
+    assert call(m=2 ** 31 - 2, c=2) == ERR_OVERFLOW         # c * (m + 1) beyond int32
+    assert hs.lib().spgemm_hip_last_error()
+    outs = _outs()
+    assert call(c=65, outs=[C.byref(x) for x in outs]) == ERR_ARG and [x.value for x in outs] == [None, None, None]
+
+
+@pytest.mark.parametrize("twin", TWINS)
+def test_join_argument_errors_do_not_need_a_gpu(twin):
+    fn = getattr(hs.lib(), "hip_pcsr_join" + twin)
+    nnzC = C.c_int(7)
+
+    def call(m=4, n=4, c=2, table=None, outs=None, nnz=C.byref(nnzC)):
+        t = table if table is not None else _table(c)
+        o = outs if outs is not None else [C.byref(x) for x in _outs()]
+        return fn(None, m, n, c, *t, *o, nnz)
+
+    assert call(c=0) == ERR_ARG and call(c=65) == ERR_ARG
+    for k in range(3):
+        o = [C.byref(x) for x in _outs()]
+        o[k] = None
+        assert call(outs=o) == ERR_ARG
+    assert call(nnz=None) == ERR_ARG
+    assert call(m=-1) == ERR_ARG and call(n=-1) == ERR_ARG
+    for k in range(4):                                      # a null table
+        t = _table(2)
+        t[k] = None
+        assert call(table=t) == ERR_ARG
+    assert call(table=_table(2, nnz=-1)) == ERR_ARG         # a negative count
+    t = _table(2)
+    t[0][1] = None
+    assert call(table=t) == ERR_ARG                         # a null rowPtr
+    for k in (1, 2):                                        # nnz > 0 with null colInd / values
+        t = _table(2, nnz=3)
+        t[k][0] = None
+        assert call(table=t) == ERR_ARG
+    assert call(m=0, table=_table(2, nnz=3)) == ERR_ARG
+    assert call(table=_table(2, nnz=2 ** 31 - 1)) == ERR_OVERFLOW           # the total beyond int32
+    outs = _outs()
+    assert call(c=0, outs=[C.byref(x) for x in outs]) == ERR_ARG
+    assert [x.value for x in outs] == [None, None, None] and nnzC.value == 0
+
+
+@pytest.mark.parametrize("twin", TWINS)
+def test_spmm_argument_errors_do_not_need_a_gpu(twin):
+    fn = getattr(hs.lib(), "hip_pcsr_spmm" + twin)
+
+    def res(c=2):
+        c = max(c, 1)
+        return [(C.c_void_p * c)(*[1] * c) for _ in range(3)] + [(C.c_int * c)(*[7] * c)]
+
+    def call(IA=ONE, JA=None, A=None, nnzA=0, m=4, k=4, n=4, c=2, table=None, outs=None):
+        t = table if table is not None else _table(c)
+        o = outs if outs is not None else res(c)
+        return fn(None, IA, JA, A, nnzA, m, k, n, c, *t, *o)
+
+    assert call(c=0) == ERR_ARG and call(c=65) == ERR_ARG
+    for q in range(4):
+        o = res()
+        o[q] = None
+        assert call(outs=o) == ERR_ARG                      # a null output array
+    assert call(m=-1) == ERR_ARG and call(k=-1) == ERR_ARG and call(n=-1) == ERR_ARG and call(nnzA=-1) == ERR_ARG
+    assert call(IA=None) == ERR_ARG
+    assert call(nnzA=3, JA=None, A=ONE) == ERR_ARG and call(nnzA=3, JA=ONE, A=None) == ERR_ARG
+    for q in range(4):
+        t = _table(2)
+        t[q] = None
+        assert call(table=t) == ERR_ARG
+    assert call(table=_table(2, nnz=-1)) == ERR_ARG
+    t = _table(2, nnz=3)
+    t[1][1] = None
+    assert call(table=t) == ERR_ARG
+    o = res()
+    assert call(m=-1, outs=o) == ERR_ARG                    # every output slot is cleared on an error
+    assert [list(a) for a in o[:3]] == [[None, None]] * 3 and list(o[3]) == [0, 0]
+    assert hs.lib().spgemm_hip_last_error()
+
+
+# ---- the mirrors refuse before device work ---------------------------------------------------------------------------
+def test_python_mirror_refuses_mismatches_before_device_work():
+    # device CSRs with no memory behind them: anything that reached the device would fail differently
+    blocks = [hs.CSR(None, None, None, 3, 3, 2, on_device=True), hs.CSR(None, None, None, 3, 3, 3, on_device=True)]
+    p = hs.PCSR._of_blocks(blocks, 3, 5, np.float32)
+    assert (p.stride, p.nnz(), p.blockPtr) == (3, 5, [0, 2, 5]) and p.block(1) is blocks[1]
+    for rows, cols, nnz in ((4, 5, 5), (3, 6, 5), (3, 5, 6)):
+        assert not p.isEqual(hs.CSR(None, None, None, rows, cols, nnz, on_device=True))
+    with pytest.raises(hs.SpgemmError, match="mixed"):
+        p.isEqual(hs.CSR(None, None, None, 3, 5, 5, on_device=True, dtype=np.float64))
+    with pytest.raises(hs.SpgemmError, match="shape"):
+        p.spmm_left(hs.CSR(None, None, None, 4, 4, 0, on_device=True))
+    with pytest.raises(hs.SpgemmError, match="mixed"):
+        p.spmm_left(hs.CSR(None, None, None, 4, 3, 0, on_device=True, dtype=np.float64))
+
+
+def test_cpp_mirror_refuses_a_shape_mismatch_before_device_work():
+    """tests/cpp/pcsr_check.cc --shape-check: PCSR::isEqual against another row count, column count and nnz"""
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "Makefile.pcsr"])
+    out = subprocess.run([os.path.join(cpp, "pcsr_check.x"), "--shape-check"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "refused" in out.stdout and "B_rows = 4" in out.stdout and "B_cols = 6" in out.stdout and "B_nnz = 6" in out.stdout
