@@ -492,6 +492,51 @@ int hip_pcsr_spmm_f64(spgemm_handle* h, const int* dIA, const int* dJA, const do
                       const int* const* dIB, const int* const* dJB, const double* const* dB, const int* nnzB,
                       int** dIC, int** dJC, double** dC, int* nnzC);
 
+/* ---- blocked CSR (BCSR): a CSR as r x c dense tiles, and back ------------------------------------------------------------
+ * All CSR / BCSR arrays are device pointers, the counts are host memory; h == NULL = the default handle; a call returns
+ * after the device work has completed; outputs come from the library pool (release with spgemm_hip_free).  Argument
+ * checks (r < 1, c < 1, r * c > SPGEMM_BCSR_MAX_TILE, a null output, a negative size, a count > 0 with null arrays, a
+ * negative or NaN drop_tol -> SPGEMM_ERR_ARG) run before any device is touched.  Every value that becomes an address
+ * (rowPtr, the columns, the block columns) is validated by a read-only pass whose flag the host reads before it is used:
+ * bad input -> SPGEMM_ERR_INPUT with a message.  On any error the outputs are NULL, nothing stays allocated, the handle
+ * stays usable.
+ *
+ * r (tile rows) comes before c (tile columns), as in the reference's definition BCSR::BCSR(csr, r, c) (nlibs/BCSR.cc:3);
+ * its header declares the two the other way round (nlibs/BCSR.h:15), the definition is what runs.
+ * bm = ceil(m / r) block rows, bn = ceil(n / c) block columns; r > m and c > n are valid (one block row / column). */
+#define SPGEMM_BCSR_MAX_TILE 4096      /* r >= 1, c >= 1, r * c <= 4096 */
+
+/* BCSR::BCSR(const CSR&, r, c) (nlibs/BCSR.cc:3-65), the same three arrays:
+ *   *dIB   device int[bm + 1]: starts at 0, ends at *nnzb
+ *   *dJB   device int[nnzb]: block columns
+ *   *dB    device, nnzb * r * c values: tile k at k * r * c, entry (i, col) in cell (i % r) * c + col % c; every cell no
+ *          entry lands in is +0.0, the cells of a ragged last block row / block column included
+ * The tiles of a block row are in first-occurrence order: the reference walks the block row's rows in ascending order,
+ * each in A's storage order, and appends a block column when it first meets it -- ascending only when A's rows are
+ * column-sorted and r == 1.  Of a repeated (row, col) the last in storage order stays, as the sequential loop leaves it
+ * (deterministic: no two stores aim at one cell).  Values are moved, not computed: NaN payloads, -0.0 and denormals keep
+ * their bits.  A's rows need not be sorted.  m == 0 or nnz == 0: rowPtr all zero, *nnzb = 0.  A bad rowPtr or a column
+ * outside [0, n) -> SPGEMM_ERR_INPUT.  nnzb * r * c > INT32_MAX -> SPGEMM_ERR_OVERFLOW (known only after the count
+ * pass; everything is released). */
+int hip_csr_to_bcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                    int r, int c, int** dIB, int** dJB, float** dB, int* nnzb);
+int hip_csr_to_bcsr_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                        int r, int c, int** dIB, int** dJB, double** dB, int* nnzb);
+
+/* The row walk of BCSR::isEqual (nlibs/BCSR.cc:67-116) written out as a CSR.  Row i (bi = i / r, ei = i % r) is: the
+ * tiles of block row bi in storage order, in each tile ej = 0 .. c-1, every cell whose global column bcol * c + ej is
+ * below n and whose value has fabs((double)v) > drop_tol.  NaN, +-0 and anything at or below the tolerance are dropped
+ * (isEqual's `> 1e-9`); drop_tol = 0 keeps every nonzero non-NaN cell; kept values keep their bits.  The BCSR rowPtr is
+ * validated against nnzb and every block column against [0, bn): a violation -> SPGEMM_ERR_INPUT.  A block column
+ * repeated inside a block row is no error: the row then repeats columns.  More than INT32_MAX kept cells ->
+ * SPGEMM_ERR_OVERFLOW.  For a column-sorted A without repeated columns and no |value| <= drop_tol,
+ * hip_csr_sort_rows(hip_bcsr_to_csr(hip_csr_to_bcsr(A))) is A bit for bit; unsorted it is A with every row stably
+ * grouped by tile in first-occurrence order, ascending inside a tile. */
+int hip_bcsr_to_csr(spgemm_handle* h, int m, int n, int r, int c, int nnzb, const int* dIB, const int* dJB,
+                    const float* dB, double drop_tol, int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_bcsr_to_csr_f64(spgemm_handle* h, int m, int n, int r, int c, int nnzb, const int* dIB, const int* dJB,
+                        const double* dB, double drop_tol, int** dIC, int** dJC, double** dC, int* nnzC);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

@@ -2110,6 +2110,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 #include "pcsr_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
+// blocked CSR (BCSR): CSR -> r x c dense tiles and back
+// ------------------------------------------------------------------------------------------------
+#include "bcsr_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL
 // ------------------------------------------------------------------------------------------------
 #include "sharded.hpp"

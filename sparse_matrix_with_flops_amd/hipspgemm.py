@@ -13,6 +13,8 @@ Mirrors (reference file:line):
                               CSR::differs, isEqual, ...       nlibs/CSR.cc:210-240, 381-415; nlibs/CSR.h:195-320
   PCSR(dM, c) / join / spmm_left / isEqual
                               struct PCSR, spmm(A, pB)         nlibs/PCSR.h:5-100, nlibs/PCSR.cc:3-56, correctTests/pcsrTest.cc:7-19
+  BCSR.from_csr(dM, r, c) / to_csr / nonzero_density / is_equal
+                              struct BCSR                      nlibs/BCSR.h:6-64, nlibs/BCSR.cc:3-116
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -58,8 +60,10 @@ EXPORTS = [
     "hip_csr_diff", "hip_csr_diff_f64", "hip_csr_differsStats", "hip_csr_differsStats_f64",
     "hip_csr_split_columns", "hip_csr_split_columns_f64", "hip_pcsr_join", "hip_pcsr_join_f64",
     "hip_pcsr_spmm", "hip_pcsr_spmm_f64",
+    "hip_csr_to_bcsr", "hip_csr_to_bcsr_f64", "hip_bcsr_to_csr", "hip_bcsr_to_csr_f64",
 ]
 PCSR_MAX_BLOCKS = 64
+BCSR_MAX_TILE = 4096
 VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
 XCHG_NAMES = {0: "auto", 1: "rccl", 2: "peer", 3: "host"}
@@ -188,6 +192,12 @@ def lib():
         L.hip_pcsr_join_f64.argtypes = L.hip_pcsr_join.argtypes
         L.hip_pcsr_spmm.argtypes = [C.c_void_p] + dev_in + [C.c_int, C.c_int, C.c_int, C.c_int] + table + table
         L.hip_pcsr_spmm_f64.argtypes = L.hip_pcsr_spmm.argtypes
+        L.hip_csr_to_bcsr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_csr_to_bcsr_f64.argtypes = L.hip_csr_to_bcsr.argtypes
+        L.hip_bcsr_to_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_double] + [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_bcsr_to_csr_f64.argtypes = L.hip_bcsr_to_csr.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1301,3 +1311,93 @@ class PCSR:
             for b in self.blocks:
                 b.deviceDispose()
         self.blocks = []
+
+
+# ---------------------------------------------------------------------------------------------
+# blocked CSR (include/spgemm_hip.h "blocked CSR"): a CSR as r x c dense tiles, and back
+# ---------------------------------------------------------------------------------------------
+def csr_to_bcsr_raw(handle, m, n, nnz, IA, JA, VA, r, c, dtype=np.float32):
+    """hip_csr_to_bcsr (float32) / _f64 on raw device pointers -> (dIB, dJB, dB, nnzb): block rowPtr int[bm + 1], block
+    columns int[nnzb], nnzb * r * c values, all from the library pool (release with dev_free)."""
+    fn, name = _pcsr_fn("hip_csr_to_bcsr", dtype)
+    ib, jb, vb, nnzb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(r),
+              int(c), C.byref(ib), C.byref(jb), C.byref(vb), C.byref(nnzb)), name)
+    return ib.value, jb.value, vb.value, nnzb.value
+
+
+def bcsr_to_csr_raw(handle, m, n, r, c, nnzb, IB, JB, VB, drop_tol=1e-9, dtype=np.float32):
+    """hip_bcsr_to_csr / _f64: the tiles written out row by row -> (dIC, dJC, dC, nnz) from the library pool; a cell is kept
+    when its column is below n and fabs(value) > drop_tol (compared in double)."""
+    fn, name = _pcsr_fn("hip_bcsr_to_csr", dtype)
+    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(r), int(c), int(nnzb), C.c_void_p(IB), C.c_void_p(JB),
+              C.c_void_p(VB), float(drop_tol), C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
+    return ic.value, jc.value, cv.value, nnz.value
+
+
+class BCSR:
+    """Mirror of the reference's `struct BCSR` (nlibs/BCSR.h:6-64) on device arrays: an m x n matrix as r x c dense tiles.
+    Fields m, n, r, c, bm, bn, nnzb, nnz (the source CSR's, as the reference keeps it) and the three device arrays rowPtr
+    (int[bm + 1]), colInd (int[nnzb] block columns), values (nnzb * r * c).  r comes before c, as in the reference's
+    definition (its header declares them the other way round)."""
+
+    def __init__(self, dM, r, c, handle=None):
+        assert dM.on_device
+        r, c = int(r), int(c)
+        if r < 1 or c < 1 or r * c > BCSR_MAX_TILE:
+            raise SpgemmError(f"tile r={r} c={c}: need r >= 1, c >= 1, r * c <= {BCSR_MAX_TILE}")
+        self.dtype = _value_dtype(dM.dtype)
+        self.m, self.n, self.r, self.c, self.nnz = dM.rows, dM.cols, r, c, dM.nnz
+        self.bm, self.bn = (self.m + r - 1) // r, (self.n + c - 1) // c
+        self.rowPtr, self.colInd, self.values, self.nnzb = csr_to_bcsr_raw(
+            handle, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, dM.values, r, c, self.dtype)
+
+    @staticmethod
+    def from_csr(dM, r, c, handle=None):
+        return BCSR(dM, r, c, handle)
+
+    def to_csr(self, drop_tol=1e-9, handle=None):
+        """hip_bcsr_to_csr -> device CSR m x n: row i = the tiles of its block row in storage order, ascending inside a tile"""
+        ic, jc, cv, nnz = bcsr_to_csr_raw(handle, self.m, self.n, self.r, self.c, self.nnzb, self.rowPtr, self.colInd,
+                                          self.values, drop_tol, self.dtype)
+        return CSR(cv, jc, ic, self.m, self.n, nnz, True, dtype=self.dtype)
+
+    def nonzero_density(self):
+        """BCSR::nonzeroDensity (nlibs/BCSR.h:61-63): nnz / (nnzb * r * c) * 100; 0.0 without tiles (the reference
+        divides by zero there)"""
+        cells = self.nnzb * self.r * self.c
+        return float(self.nnz) / cells * 100.0 if cells else 0.0
+
+    def is_equal(self, dB, handle=None):
+        """BCSR::isEqual (nlibs/BCSR.cc:67-116) against a device CSR: the tiles written out with drop_tol = 1e-9 and a
+        copy of dB, both row-sorted on the device, then one hip_csr_diff report with abs_tol = 1e-9: true iff the row
+        lengths agree, no common column is further than 1e-9 apart and no entry only dB holds exceeds 1e-9.  dB itself
+        is left alone.  Another shape or value type raises before any device work."""
+        assert dB.on_device
+        if (self.m, self.n) != (dB.rows, dB.cols):
+            raise SpgemmError(f"shape mismatch: the blocked matrix is {self.m}x{self.n}, B is {dB.rows}x{dB.cols}")
+        if _value_dtype(dB.dtype) != self.dtype:
+            raise SpgemmError(f"mixed value types: the blocked matrix is {self.dtype}, B is {dB.dtype}")
+        f64 = self.dtype == np.float64
+        copy, diff = (csr_permute_raw_f64, csr_diff_raw_f64) if f64 else (csr_permute_raw, csr_diff_raw)
+        mine = self.to_csr(1e-9, handle)
+        try:
+            ib, jb, vb = copy(handle, dB.rows, dB.cols, dB.nnz, dB.rowPtr, dB.colInd, dB.values)       # a deep copy
+            theirs = CSR(vb, jb, ib, dB.rows, dB.cols, dB.nnz, True, dtype=dB.dtype)
+            try:
+                sort_rows_device(mine, handle)
+                sort_rows_device(theirs, handle)
+                d = diff(handle, self.m, self.n, mine.rowPtr, mine.colInd, mine.values, mine.nnz, theirs.rowPtr,
+                         theirs.colInd, theirs.values, theirs.nnz, 0.0, 1e-9)
+                return d.rows_len_differ == 0 and d.beyond == 0 and d.max_abs_only_b <= 1e-9
+            finally:
+                theirs.deviceDispose()
+        finally:
+            mine.deviceDispose()
+
+    def dispose(self):
+        for p in (self.rowPtr, self.colInd, self.values):
+            dev_free(p)
+        self.rowPtr = self.colInd = self.values = None
+        self.nnzb = 0
