@@ -537,6 +537,63 @@ int hip_bcsr_to_csr(spgemm_handle* h, int m, int n, int r, int c, int nnzb, cons
 int hip_bcsr_to_csr_f64(spgemm_handle* h, int m, int n, int r, int c, int nnzb, const int* dIB, const int* dJB,
                         const double* dB, double drop_tol, int** dIC, int** dJC, double** dC, int* nnzC);
 
+/* ---- mixed CSR (MCSR): the top-left corner as r x c dense tiles, the rest as a CSR, and back -----------------------------
+ * All arrays are device pointers, the counts are host memory; h == NULL = the default handle; a call returns after the
+ * device work has completed; outputs come from the library pool (release with spgemm_hip_free).  Argument checks (the
+ * tile rules of hip_csr_to_bcsr; blockRows outside [0, m]; blockCols outside [0, n]; blockRows % r != 0, the reference's
+ * assert at nlibs/MCSR.cc:15; a null output, a negative size, a count > 0 with null arrays, a negative or NaN drop_tol
+ * -> SPGEMM_ERR_ARG) run before any device is touched.  Every value that becomes an address is validated by a read-only
+ * pass whose flag the host reads before it is used: bad input -> SPGEMM_ERR_INPUT with a message.  On any error every
+ * output is NULL, the counts are 0, nothing stays allocated, the handle stays usable.
+ *
+ * r comes before c as in the definition MCSR::MCSR(csr, r, c, blockRows, blockCols) (nlibs/MCSR.cc:3); the header
+ * (nlibs/MCSR.h:7) declares the two the other way round.  blockCols need not be a multiple of c.
+ * bm = blockRows / r block rows, bn = ceil(blockCols / c) block columns. */
+
+/* The FILL pass of MCSR::MCSR (nlibs/MCSR.cc:58-92).  An entry (i, col) with i < blockRows and col < blockCols goes into
+ * tile (i / r, col / c), cell (i % r) * c + col % c; every other entry stays in the remainder.
+ *   *dIB, *dJB, *dB, *nnzb   exactly what hip_csr_to_bcsr returns for the blockRows x blockCols CSR made of the corner's
+ *                            entries in A's storage order: int[bm + 1], int[nnzb] block columns, nnzb * r * c values; the
+ *                            tiles of a block row in first-occurrence order; of a repeated (row, col) the last in storage
+ *                            order stays; every other cell +0.0, the cells of a ragged last block column included (their
+ *                            columns >= blockCols belong to the remainder); values keep their bits
+ *   *dIR, *dJR, *dR, *nnzR   the remainder, an m x n CSR with global columns: row i < blockRows holds A's entries of row i
+ *                            with col >= blockCols in storage order, row i >= blockRows is A's row unchanged
+ * The number of entries that went to the corner, repeats counted, is nnz - *nnzR (the reference leaves BCSR::nnz at 0).
+ * A's rows need not be sorted and may repeat a column.  m == 0, nnz == 0, blockRows == 0 or blockCols == 0 (no tiles, the
+ * remainder is A) and a corner that covers the whole matrix (an empty remainder) are valid; the arrays of an empty part
+ * follow hip_csr_to_bcsr (rowPtr all zero, the other two non-null placeholders).  A bad rowPtr or a column outside
+ * [0, n) -> SPGEMM_ERR_INPUT.  nnzb * r * c > INT32_MAX -> SPGEMM_ERR_OVERFLOW.
+ * Not reproduced: the reference's COUNT pass (nlibs/MCSR.cc:16-40) resets `top` per block row instead of per row, so for
+ * r > 1 its remainder rowPtr over-counts whenever a row other than the last of its block row has remainder entries, and
+ * its assert(nnz == top) fails; for r == 1 (its known-answer vectors, tests/MCSR_test.cc) the two passes agree. */
+int hip_csr_to_mcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                    int r, int c, int blockRows, int blockCols,
+                    int** dIB, int** dJB, float** dB, int* nnzb,
+                    int** dIR, int** dJR, float** dR, int* nnzR);
+int hip_csr_to_mcsr_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                        int r, int c, int blockRows, int blockCols,
+                        int** dIB, int** dJB, double** dB, int* nnzb,
+                        int** dIR, int** dJR, double** dR, int* nnzR);
+
+/* The inverse (the reference has no MCSR::isEqual; this is the definition).  Row i < blockRows of the result is the
+ * corner's row i followed by the remainder's row i; row i >= blockRows is the remainder's row.  The corner's row is
+ * written out as hip_bcsr_to_csr does for a blockRows x blockCols BCSR: tiles in storage order, ej = 0 .. c-1, a cell kept
+ * when its global column is below blockCols and fabs((double)v) > drop_tol; kept values keep their bits.  Validated, each
+ * -> SPGEMM_ERR_INPUT: the block rowPtr against nnzb, every block column against [0, bn), the remainder's rowPtr against
+ * nnzR, every remainder column against [0, n).  A remainder entry inside the corner's range is no error: the row then may
+ * repeat a column.  More than INT32_MAX kept entries -> SPGEMM_ERR_OVERFLOW.  For a column-sorted A without repeated
+ * columns and no |value| <= drop_tol the round trip is A bit for bit when r == 1, and A after hip_csr_sort_rows when
+ * r > 1 (the tiles of a block row are in first-occurrence order over its r rows). */
+int hip_mcsr_to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols,
+                    int nnzb, const int* dIB, const int* dJB, const float* dB,
+                    int nnzR, const int* dIR, const int* dJR, const float* dR, double drop_tol,
+                    int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_mcsr_to_csr_f64(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols,
+                        int nnzb, const int* dIB, const int* dJB, const double* dB,
+                        int nnzR, const int* dIR, const int* dJR, const double* dR, double drop_tol,
+                        int** dIC, int** dJC, double** dC, int* nnzC);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

@@ -1,0 +1,318 @@
+// Mixed CSR (MCSR) on the device: the top-left blockRows x blockCols corner as r x c dense tiles, the rest as a CSR; and
+// the two parts written back out as one CSR.
+//
+// Replaces, on device arrays,
+//   MCSR::MCSR(const CSR&, r, c, blockRows, blockCols)   nlibs/MCSR.cc:3-97   (the FILL pass, lines 58-92, is the
+//                                                                              definition; see below for the count pass)
+// and defines the inverse, which the reference lacks (there is no MCSR::isEqual).
+//
+// Layout.  An entry (i, col) with i < blockRows and col < blockCols belongs to the corner: tile (i / r, col / c), cell
+// (i % r) * c + col % c of a BCSR with bm = blockRows / r block rows and bn = ceil(blockCols / c) block columns -- exactly
+// what bcsr::to_bcsr makes of the blockRows x blockCols CSR of those entries in A's storage order.  Everything else is the
+// remainder, an m x n CSR with global columns: row i < blockRows keeps its entries with col >= blockCols in storage order,
+// row i >= blockRows is A's row.
+//
+// The reference's COUNT pass (nlibs/MCSR.cc:16-40) resets `top` per block row, not per row, so for r > 1 its remainder
+// rowPtr over-counts whenever a row other than the last of its block row has remainder entries, and assert(nnz == top)
+// fails.  That defect is not reproduced: the remainder rowPtr here is the one the fill pass implies.
+//
+// Forward.  A CSR is in row order, so ONE stable two-way partition of the first nTop = IA[blockRows] entries by the flag
+// col < blockCols yields both parts in CSR order; no sort, no per-row work:
+//   * k_flags, dealt by entries, then the library's scan: scan[o] = corner entries before o, scan[nTop] = nCorner;
+//   * k_scatter, dealt by entries (coalesced reads): a corner entry goes to scan[o] of the temporary corner CSR (its column
+//     is local already), a remainder entry to o - scan[o];
+//   * entries nTop..nnz are copied in bulk behind the remainder's top part;
+//   * k_rowptrs: corner rowPtr[i] = scan[IA[i]], remainder rowPtr[i] = IA[i] - scan[IA[i]] up to blockRows, IA[i] - nCorner
+//     above;
+//   * bcsr::to_bcsr on the temporary corner CSR, which goes back to the pool before the call returns.
+// A 20 000-entry row is spread over blocks like any other 20 000 entries.  No atomics on values; every position is a
+// function of the input alone, so the result is the same bytes every time.
+//
+// Inverse.  bcsr::to_csr on the corner (m = blockRows, n = blockCols: a temporary CSR), then a row-wise concatenation with
+// the remainder: row lengths added, the library's scan (its 64-bit total decides the overflow), one copy kernel dealt by
+// OUTPUT entries as pcsr::k_join_copy.
+//
+// Every value that becomes an address (rowPtr, the columns, the block rowPtr and columns) is checked first by
+// reorder::k_check_rowptr / k_check_cols (here or inside the bcsr:: calls); the host reads the flag before anything is
+// queued that indexes with them.  Included at the end of spgemm_hip.hip behind bcsr_device.hpp.
+#pragma once
+
+namespace mcsr {
+
+using reorder::CP_THREADS;
+using reorder::CP_ITEMS;
+using reorder::CP_TILE;
+
+// flag[o] = 1 where entry o < nTop lies left of blockCols (its row is above blockRows by the choice of nTop)
+__global__ __launch_bounds__(CP_THREADS) void k_flags(int nTop, int blockCols, const int* __restrict__ JA,
+                                                      int* __restrict__ flag) {
+  const long long base = (long long)blockIdx.x * CP_TILE;
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS; ++k) {
+    const long long o = base + k * CP_THREADS + threadIdx.x;
+    if (o >= nTop) break;
+    flag[o] = JA[o] < blockCols ? 1 : 0;
+  }
+}
+
+// the stable partition: scan[o] corner entries precede entry o, so o - scan[o] remainder entries do
+template <class V>
+__global__ __launch_bounds__(CP_THREADS) void k_scatter(int nTop, int blockCols, const int* __restrict__ JA,
+                                                        const V* __restrict__ A, const int* __restrict__ scan,
+                                                        int* __restrict__ JK, V* __restrict__ K, int* __restrict__ JR,
+                                                        V* __restrict__ R) {
+  const long long base = (long long)blockIdx.x * CP_TILE;
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS; ++k) {
+    const long long o = base + k * CP_THREADS + threadIdx.x;
+    if (o >= nTop) break;
+    const int col = JA[o], before = scan[o];
+    const V v = A[o];
+    if (col < blockCols) { JK[before] = col; K[before] = v; }
+    else { const int p = (int)o - before; JR[p] = col; R[p] = v; }
+  }
+}
+
+// IK[i] (i = 0..blockRows): the corner CSR's rowPtr; IR[i] (i = 0..m): the remainder's.  IA has been validated, so
+// IA[i] <= nTop for i <= blockRows.
+__global__ void k_rowptrs(int m, int blockRows, int nCorner, const int* __restrict__ IA, const int* __restrict__ scan,
+                          int* __restrict__ IK, int* __restrict__ IR) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > m) return;
+  const int a = IA[i];
+  if (i <= blockRows) {
+    const int before = scan[a];
+    IK[i] = before;
+    IR[i] = a - before;
+  } else {
+    IR[i] = a - nCorner;
+  }
+}
+
+// ---- inverse ------------------------------------------------------------------------------------------------------------
+// IC[i] = corner row length (i < blockRows) + remainder row length, as an unsigned sum (each is below 2^31; the scan
+// adds unsigned into a 64-bit total)
+__global__ void k_cat_lens(int m, int blockRows, const int* __restrict__ IT, const int* __restrict__ IR,
+                           int* __restrict__ IC) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  unsigned len = (unsigned)(IR[i + 1] - IR[i]);
+  if (i < blockRows) len += (unsigned)(IT[i + 1] - IT[i]);
+  IC[i] = (int)len;
+}
+
+// One tile of C's entries per block, as pcsr::k_join_copy: the row by a search in IC bounded by the tile's rows, then the
+// corner's row first and the remainder's behind it; lane-strided reads staged in LDS, 16-byte stores.  The corner sits at
+// the top left, so its columns are global already.
+template <class V>
+__global__ __launch_bounds__(CP_THREADS) void k_cat_copy(int m, int nnz, int blockRows, const int* __restrict__ IT,
+                                                         const int* __restrict__ JT, const V* __restrict__ T,
+                                                         const int* __restrict__ IR, const int* __restrict__ JR,
+                                                         const V* __restrict__ R, const int* __restrict__ IC,
+                                                         int* __restrict__ JC, V* __restrict__ C) {
+  __shared__ int rows[2];
+  __shared__ __attribute__((aligned(16))) int sc[CP_TILE];
+  __shared__ __attribute__((aligned(16))) V sv[CP_TILE];
+  const long long base = (long long)blockIdx.x * CP_TILE;
+  reorder::tile_rows(IC, m, nnz, base, rows);
+#pragma unroll
+  for (int k = 0; k < CP_ITEMS; ++k) {
+    const int t = k * CP_THREADS + threadIdx.x;
+    const long long o = base + t;
+    if (o < nnz) {
+      const int r = reorder::row_of_entry(IC, rows[0], rows[1], (int)o);
+      const int off = (int)o - IC[r];
+      int s = 0, len = 0;
+      if (r < blockRows) { s = IT[r]; len = IT[r + 1] - s; }
+      if (off < len) {
+        sc[t] = JT[s + off];
+        sv[t] = T[s + off];
+      } else {
+        const int p = IR[r] + (off - len);
+        sc[t] = JR[p];
+        sv[t] = R[p];
+      }
+    }
+  }
+  __syncthreads();
+  const int t0 = threadIdx.x * CP_ITEMS;
+  const long long o0 = base + t0;
+  if (o0 >= nnz) return;
+  if (o0 + CP_ITEMS <= nnz) {
+    *reinterpret_cast<int4*>(JC + o0) = *reinterpret_cast<const int4*>(sc + t0);
+    const V v[CP_ITEMS] = {sv[t0], sv[t0 + 1], sv[t0 + 2], sv[t0 + 3]};
+    reorder::store4<V>(C + o0, v);
+  } else {
+    for (int k = 0; o0 + k < nnz; ++k) { JC[o0 + k] = sc[t0 + k]; C[o0 + k] = sv[t0 + k]; }
+  }
+}
+
+#define MC_ALLOC(...) if (!sc.get(__VA_ARGS__)) return sc.done(fail(SPGEMM_ERR_HIP, "device allocation failed"))
+#define MC_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
+
+static int check_corner(int m, int n, int r, int c, int blockRows, int blockCols) {
+  CHK(bcsr::check_tile_shape(r, c));
+  if (m < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative size");
+  if (blockRows < 0 || blockRows > m || blockCols < 0 || blockCols > n)
+    return fail(SPGEMM_ERR_ARG, "corner %d x %d outside the %d x %d matrix", blockRows, blockCols, m, n);
+  if (blockRows % r != 0)                          // the reference's assert, nlibs/MCSR.cc:15
+    return fail(SPGEMM_ERR_ARG, "blockRows=%d is not a multiple of r=%d", blockRows, r);
+  return SPGEMM_OK;
+}
+
+template <class V>
+static int to_mcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const V* dA, int r, int c,
+                   int blockRows, int blockCols, int** dIB, int** dJB, V** dB, int* nnzb, int** dIR, int** dJR, V** dR,
+                   int* nnzR) {
+  using namespace reorder;
+  if (!dIB || !dJB || !dB || !nnzb || !dIR || !dJR || !dR || !nnzR) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dIB = nullptr; *dJB = nullptr; *dB = nullptr; *nnzb = 0;
+  *dIR = nullptr; *dJR = nullptr; *dR = nullptr; *nnzR = 0;
+  if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
+  CHK(check_corner(m, n, r, c, blockRows, blockCols));
+  if ((m > 0 && !dIA) || (nnz > 0 && (!dJA || !dA))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnz);
+  if (m == 0 && nnz > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnz);
+  if (!h) CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  clear_stale_hip_error();
+  hipStream_t s = h->stream;
+  Scratch sc;
+  int *bad = nullptr, *scan = nullptr, *IK = nullptr, *JK = nullptr, *IR = nullptr, *JR = nullptr;
+  V *K = nullptr, *R = nullptr;
+  unsigned long long* tile = nullptr;
+  MC_ALLOC(&bad, sizeof(int));
+  MC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  // validation, one read-back: rowPtr (IA[blockRows] cuts the entries, scan is indexed with IA) and the column range
+  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnz, dIA, (int*)nullptr, (int*)nullptr, bad);
+  if (nnz > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnz), dim3(256), 0, s, nnz, n, dJA, bad);
+  int hbad = 0, nTop = 0;
+  if (blockRows > 0) MC_HIP(hipMemcpyAsync(&nTop, dIA + blockRows, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone row pointer ending at nnz=%d", nnz));
+  if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "column outside [0,%d)", n));
+  // (1) the flags of the top entries and their scan; its total sizes the two parts
+  MC_ALLOC(&scan, sizeof(int) * ((size_t)nTop + 1));
+  MC_ALLOC(&tile, scan_scratch_bytes((long long)nTop + 1));
+  const dim3 topGrid((unsigned)std::max(1, cdiv(nTop, CP_TILE)));
+  if (nTop > 0) hipLaunchKernelGGL(k_flags, topGrid, dim3(CP_THREADS), 0, s, nTop, blockCols, dJA, scan);
+  scan_inplace(s, scan, nTop, tile);
+  int nCorner = 0;
+  MC_HIP(hipMemcpyAsync(&nCorner, scan + nTop, sizeof(int), hipMemcpyDeviceToHost, s));
+  MC_HIP(hipStreamSynchronize(s));
+  const int nRest = nnz - nCorner;
+  MC_ALLOC(&IK, sizeof(int) * ((size_t)blockRows + 1));
+  MC_ALLOC(&JK, sizeof(int) * (size_t)std::max(nCorner, 1));
+  MC_ALLOC(&K, sizeof(V) * (size_t)std::max(nCorner, 1));
+  MC_ALLOC(&IR, sizeof(int) * ((size_t)m + 1), true);
+  MC_ALLOC(&JR, sizeof(int) * (size_t)std::max(nRest, 1), true);
+  MC_ALLOC(&R, sizeof(V) * (size_t)std::max(nRest, 1), true);
+  // (2) the partition of the top entries, the bulk copy of the rest, the two rowPtr arrays
+  if (nTop > 0) hipLaunchKernelGGL(k_scatter<V>, topGrid, dim3(CP_THREADS), 0, s, nTop, blockCols, dJA, dA, scan, JK, K, JR, R);
+  if (nnz > nTop) {
+    const size_t cnt = (size_t)(nnz - nTop), at = (size_t)(nTop - nCorner);
+    MC_HIP(hipMemcpyAsync(JR + at, dJA + nTop, sizeof(int) * cnt, hipMemcpyDeviceToDevice, s));
+    MC_HIP(hipMemcpyAsync(R + at, dA + nTop, sizeof(V) * cnt, hipMemcpyDeviceToDevice, s));
+  }
+  if (m > 0) hipLaunchKernelGGL(k_rowptrs, grid256((long long)m + 1), dim3(256), 0, s, m, blockRows, nCorner, dIA, scan, IK, IR);
+  else MC_HIP(hipMemsetAsync(IR, 0, sizeof(int), s));
+  MC_HIP(hipGetLastError());
+  // (3) the corner CSR (blockRows x blockCols, local columns) as tiles; on the same stream, it returns after its work
+  const int rc = bcsr::to_bcsr<V>(h, blockRows, blockCols, nCorner, IK, JK, K, r, c, dIB, dJB, dB, nnzb);
+  if (rc != SPGEMM_OK) {
+    hipStreamSynchronize(s);
+    return sc.done(rc);
+  }
+  *dIR = IR; *dJR = JR; *dR = R; *nnzR = nRest;
+  return sc.done(SPGEMM_OK);
+}
+
+template <class V>
+static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols, int nnzb, const int* dIB,
+                  const int* dJB, const V* dB, int nnzR, const int* dIR, const int* dJR, const V* dR, double drop_tol,
+                  int** dIC, int** dJC, V** dC, int* nnzC) {
+  using namespace reorder;
+  if (!dIC || !dJC || !dC || !nnzC) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dIC = nullptr; *dJC = nullptr; *dC = nullptr; *nnzC = 0;
+  if (nnzb < 0 || nnzR < 0) return fail(SPGEMM_ERR_ARG, "negative size");
+  CHK(check_corner(m, n, r, c, blockRows, blockCols));
+  if (!(drop_tol >= 0.0)) return fail(SPGEMM_ERR_ARG, "drop_tol=%g is negative or NaN", drop_tol);
+  if ((blockRows > 0 && !dIB) || (nnzb > 0 && (!dJB || !dB)))
+    return fail(SPGEMM_ERR_ARG, "BCSR arrays null with blockRows=%d nnzb=%d", blockRows, nnzb);
+  if (blockRows == 0 && nnzb > 0) return fail(SPGEMM_ERR_ARG, "nnzb=%d in a corner without rows", nnzb);
+  if ((m > 0 && !dIR) || (nnzR > 0 && (!dJR || !dR))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnzR);
+  if (m == 0 && nnzR > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnzR);
+  if (!h) CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  clear_stale_hip_error();
+  hipStream_t s = h->stream;
+  Scratch sc;
+  int *bad = nullptr, *IT = nullptr, *JT = nullptr, *IC = nullptr, *JC = nullptr;
+  V *T = nullptr, *C = nullptr;
+  unsigned long long* tile = nullptr;
+  MC_ALLOC(&bad, sizeof(int));
+  MC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  // validation, one read-back: the remainder's rowPtr against its count and its columns (the result must be a valid m x n
+  // CSR); the block rowPtr and the block columns are validated by bcsr::to_csr
+  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnzR, dIR, (int*)nullptr, (int*)nullptr, bad);
+  if (nnzR > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnzR), dim3(256), 0, s, nnzR, n, dJR, bad);
+  int hbad = 0;
+  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "the remainder's rowPtr is not a monotone row pointer ending at nnz=%d", nnzR));
+  if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "a remainder column is outside [0,%d)", n));
+  // (1) the corner's rows as a temporary CSR
+  int nnzT = 0;
+  const int rc = bcsr::to_csr<V>(h, blockRows, blockCols, r, c, nnzb, dIB, dJB, dB, drop_tol, &IT, &JT, &T, &nnzT);
+  if (rc != SPGEMM_OK) return sc.done(rc);
+  sc.tmp.push_back(IT); sc.tmp.push_back(JT); sc.tmp.push_back(T);
+  // (2) row lengths, scan, copy
+  MC_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
+  MC_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
+  if (m > 0) hipLaunchKernelGGL(k_cat_lens, grid256(m), dim3(256), 0, s, m, blockRows, IT, dIR, IC);
+  scan_inplace(s, IC, m, tile);
+  unsigned long long total = 0;
+  MC_HIP(hipMemcpyAsync(&total, tile, sizeof(total), hipMemcpyDeviceToHost, s));
+  MC_HIP(hipStreamSynchronize(s));
+  if (total > (unsigned long long)INT_MAX)
+    return sc.done(fail(SPGEMM_ERR_OVERFLOW, "%llu entries do not fit the int32 CSR", total));
+  const int nnz = (int)total;
+  MC_ALLOC(&JC, sizeof(int) * (size_t)std::max(nnz, 1), true);
+  MC_ALLOC(&C, sizeof(V) * (size_t)std::max(nnz, 1), true);
+  if (nnz > 0)
+    hipLaunchKernelGGL(k_cat_copy<V>, dim3((unsigned)cdiv(nnz, CP_TILE)), dim3(CP_THREADS), 0, s, m, nnz, blockRows, IT, JT, T,
+                       dIR, dJR, dR, IC, JC, C);
+  MC_HIP(hipGetLastError());
+  MC_HIP(hipStreamSynchronize(s));
+  *dIC = IC; *dJC = JC; *dC = C; *nnzC = nnz;
+  return sc.done(SPGEMM_OK);
+}
+
+#undef MC_ALLOC
+#undef MC_HIP
+
+}  // namespace mcsr
+
+extern "C" int hip_csr_to_mcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA, int r,
+                               int c, int blockRows, int blockCols, int** dIB, int** dJB, float** dB, int* nnzb, int** dIR,
+                               int** dJR, float** dR, int* nnzR) {
+  return mcsr::to_mcsr<float>(h, m, n, nnz, dIA, dJA, dA, r, c, blockRows, blockCols, dIB, dJB, dB, nnzb, dIR, dJR, dR, nnzR);
+}
+
+extern "C" int hip_csr_to_mcsr_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                                   int r, int c, int blockRows, int blockCols, int** dIB, int** dJB, double** dB, int* nnzb,
+                                   int** dIR, int** dJR, double** dR, int* nnzR) {
+  return mcsr::to_mcsr<double>(h, m, n, nnz, dIA, dJA, dA, r, c, blockRows, blockCols, dIB, dJB, dB, nnzb, dIR, dJR, dR, nnzR);
+}
+
+extern "C" int hip_mcsr_to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols, int nnzb,
+                               const int* dIB, const int* dJB, const float* dB, int nnzR, const int* dIR, const int* dJR,
+                               const float* dR, double drop_tol, int** dIC, int** dJC, float** dC, int* nnzC) {
+  return mcsr::to_csr<float>(h, m, n, r, c, blockRows, blockCols, nnzb, dIB, dJB, dB, nnzR, dIR, dJR, dR, drop_tol, dIC, dJC,
+                             dC, nnzC);
+}
+
+extern "C" int hip_mcsr_to_csr_f64(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols, int nnzb,
+                                   const int* dIB, const int* dJB, const double* dB, int nnzR, const int* dIR, const int* dJR,
+                                   const double* dR, double drop_tol, int** dIC, int** dJC, double** dC, int* nnzC) {
+  return mcsr::to_csr<double>(h, m, n, r, c, blockRows, blockCols, nnzb, dIB, dJB, dB, nnzR, dIR, dJR, dR, drop_tol, dIC, dJC,
+                              dC, nnzC);
+}

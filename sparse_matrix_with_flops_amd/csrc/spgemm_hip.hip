@@ -2115,6 +2115,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 #include "bcsr_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
+// mixed CSR (MCSR): a tiled top-left corner plus a CSR remainder, and back
+// ------------------------------------------------------------------------------------------------
+#include "mcsr_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL
 // ------------------------------------------------------------------------------------------------
 #include "sharded.hpp"

@@ -15,6 +15,8 @@ Mirrors (reference file:line):
                               struct PCSR, spmm(A, pB)         nlibs/PCSR.h:5-100, nlibs/PCSR.cc:3-56, correctTests/pcsrTest.cc:7-19
   BCSR.from_csr(dM, r, c) / to_csr / nonzero_density / is_equal
                               struct BCSR                      nlibs/BCSR.h:6-64, nlibs/BCSR.cc:3-116
+  MCSR.from_csr(dM, r, c, blockRows, blockCols) / to_csr / nonzero_density
+                              struct MCSR                      nlibs/MCSR.h:6-9, nlibs/MCSR.cc:58-92
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -61,6 +63,7 @@ EXPORTS = [
     "hip_csr_split_columns", "hip_csr_split_columns_f64", "hip_pcsr_join", "hip_pcsr_join_f64",
     "hip_pcsr_spmm", "hip_pcsr_spmm_f64",
     "hip_csr_to_bcsr", "hip_csr_to_bcsr_f64", "hip_bcsr_to_csr", "hip_bcsr_to_csr_f64",
+    "hip_csr_to_mcsr", "hip_csr_to_mcsr_f64", "hip_mcsr_to_csr", "hip_mcsr_to_csr_f64",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -198,6 +201,12 @@ def lib():
         L.hip_bcsr_to_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_double] + [C.POINTER(C.c_void_p)] * 3 + [_I]
         L.hip_bcsr_to_csr_f64.argtypes = L.hip_bcsr_to_csr.argtypes
+        L.hip_csr_to_mcsr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_int, C.c_int, C.c_int] + ([C.POINTER(C.c_void_p)] * 3 + [_I]) * 2
+        L.hip_csr_to_mcsr_f64.argtypes = L.hip_csr_to_mcsr.argtypes
+        L.hip_mcsr_to_csr.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] * 2 + \
+            [C.c_double] + [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_mcsr_to_csr_f64.argtypes = L.hip_mcsr_to_csr.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1401,3 +1410,91 @@ class BCSR:
             dev_free(p)
         self.rowPtr = self.colInd = self.values = None
         self.nnzb = 0
+
+
+# ---------------------------------------------------------------------------------------------
+# mixed CSR (include/spgemm_hip.h "mixed CSR"): the top-left corner as r x c dense tiles, the rest as a CSR, and back
+# ---------------------------------------------------------------------------------------------
+def _check_corner(m, n, r, c, blockRows, blockCols):
+    if r < 1 or c < 1 or r * c > BCSR_MAX_TILE:
+        raise SpgemmError(f"tile r={r} c={c}: need r >= 1, c >= 1, r * c <= {BCSR_MAX_TILE}")
+    if not (0 <= blockRows <= m and 0 <= blockCols <= n):
+        raise SpgemmError(f"corner {blockRows} x {blockCols} outside the {m} x {n} matrix")
+    if blockRows % r:
+        raise SpgemmError(f"corner: blockRows={blockRows} is not a multiple of r={r}")
+
+
+def csr_to_mcsr_raw(handle, m, n, nnz, IA, JA, VA, r, c, blockRows, blockCols, dtype=np.float32):
+    """hip_csr_to_mcsr (float32) / _f64 on raw device pointers -> (dIB, dJB, dB, nnzb, dIR, dJR, dR, nnzR): the corner's
+    block rowPtr int[blockRows / r + 1], block columns int[nnzb] and nnzb * r * c values, then the m x n remainder CSR; all
+    from the library pool (release with dev_free)."""
+    fn, name = _pcsr_fn("hip_csr_to_mcsr", dtype)
+    ib, jb, vb, nnzb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    ir, jr, vr, nnzr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(r),
+              int(c), int(blockRows), int(blockCols), C.byref(ib), C.byref(jb), C.byref(vb), C.byref(nnzb), C.byref(ir),
+              C.byref(jr), C.byref(vr), C.byref(nnzr)), name)
+    return ib.value, jb.value, vb.value, nnzb.value, ir.value, jr.value, vr.value, nnzr.value
+
+
+def mcsr_to_csr_raw(handle, m, n, r, c, blockRows, blockCols, nnzb, IB, JB, VB, nnzR, IR, JR, VR, drop_tol=1e-9,
+                    dtype=np.float32):
+    """hip_mcsr_to_csr / _f64: row i = the corner's row (as hip_bcsr_to_csr writes it) followed by the remainder's row
+    -> (dIC, dJC, dC, nnz) from the library pool."""
+    fn, name = _pcsr_fn("hip_mcsr_to_csr", dtype)
+    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+    _check(fn(handle.ptr if handle else None, int(m), int(n), int(r), int(c), int(blockRows), int(blockCols), int(nnzb),
+              C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzR), C.c_void_p(IR), C.c_void_p(JR), C.c_void_p(VR),
+              float(drop_tol), C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
+    return ic.value, jc.value, cv.value, nnz.value
+
+
+class MCSR:
+    """Mirror of the reference's `struct MCSR : public CSR, BCSR` (nlibs/MCSR.h:6-9, the fill pass nlibs/MCSR.cc:58-92) on
+    device arrays.  The BCSR side: rowPtr (int[bm + 1]), colInd (int[nnzb] block columns), values (nnzb * r * c) and
+    the fields m, n (the whole matrix), r, c, blockRows, blockCols, bm = blockRows / r, bn = ceil(blockCols / c), nnzb and
+    nnz = the entries that went into the corner, repeats counted.  The CSR side: `remainder`, a device CSR m x n with
+    global columns.  r comes before c, as in the reference's definition."""
+
+    def __init__(self, dM, r, c, blockRows, blockCols, handle=None):
+        assert dM.on_device
+        r, c, blockRows, blockCols = int(r), int(c), int(blockRows), int(blockCols)
+        _check_corner(dM.rows, dM.cols, r, c, blockRows, blockCols)
+        self.dtype = _value_dtype(dM.dtype)
+        self.m, self.n, self.r, self.c, self.blockRows, self.blockCols = dM.rows, dM.cols, r, c, blockRows, blockCols
+        self.bm, self.bn = blockRows // r, (blockCols + c - 1) // c
+        self.rowPtr, self.colInd, self.values, self.nnzb, ir, jr, vr, nnzr = csr_to_mcsr_raw(
+            handle, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, dM.values, r, c, blockRows, blockCols, self.dtype)
+        self.remainder = CSR(vr, jr, ir, dM.rows, dM.cols, nnzr, True, dtype=self.dtype)
+        self.nnz = dM.nnz - nnzr
+
+    @staticmethod
+    def from_csr(dM, r, c, blockRows, blockCols, handle=None):
+        return MCSR(dM, r, c, blockRows, blockCols, handle)
+
+    def to_csr(self, drop_tol=1e-9, handle=None):
+        """hip_mcsr_to_csr -> device CSR m x n: the corner's row i, then the remainder's row i"""
+        rest = self.remainder
+        if (rest.rows, rest.cols) != (self.m, self.n):
+            raise SpgemmError(f"shape mismatch: the mixed matrix is {self.m}x{self.n}, its remainder {rest.rows}x{rest.cols}")
+        if _value_dtype(rest.dtype) != self.dtype:
+            raise SpgemmError(f"mixed value types: the corner is {self.dtype}, the remainder {rest.dtype}")
+        _check_corner(self.m, self.n, self.r, self.c, self.blockRows, self.blockCols)
+        ic, jc, cv, nnz = mcsr_to_csr_raw(handle, self.m, self.n, self.r, self.c, self.blockRows, self.blockCols, self.nnzb,
+                                          self.rowPtr, self.colInd, self.values, rest.nnz, rest.rowPtr, rest.colInd,
+                                          rest.values, drop_tol, self.dtype)
+        return CSR(cv, jc, ic, self.m, self.n, nnz, True, dtype=self.dtype)
+
+    def nonzero_density(self):
+        """BCSR::nonzeroDensity (nlibs/BCSR.h:61-63) of the corner: nnz / (nnzb * r * c) * 100; 0.0 without tiles"""
+        cells = self.nnzb * self.r * self.c
+        return float(self.nnz) / cells * 100.0 if cells else 0.0
+
+    def dispose(self):
+        for p in (self.rowPtr, self.colInd, self.values):
+            dev_free(p)
+        self.rowPtr = self.colInd = self.values = None
+        self.nnzb = 0
+        if self.remainder is not None:
+            self.remainder.deviceDispose()
+            self.remainder = None
