@@ -10,7 +10,7 @@
 // block column appended when first met), and of repeated (row, col) the LAST in storage order stays.
 //
 // Forward.  key = ((brow << bcolBits) | bcol) << cellBits | cell with the entry's storage index as payload, sorted by the
-// stable LSD radix passes of coo_device.hpp over exactly the bits in use (bits_of(bm-1) + bits_of(bn-1) + bits_of(r*c-1)
+// stable LSD radix passes of csr_common_device.hpp over exactly the bits in use (bits_of(bm-1) + bits_of(bn-1) + bits_of(r*c-1)
 // <= 64 for every legal shape; the host checks).  Then
 //   * a group (one tile) is a run of equal (brow, bcol): head flags, the library's scan -> group id of every entry, nnzb;
 //   * equal keys sit together in storage order, so the first of a run carries the smallest index that hits its cell and
@@ -27,17 +27,15 @@
 // running offset plus the lane's rank in the ballot (v_mbcnt), which keeps the order inside the row.  A long block row is
 // spread over the 64 lanes; nothing is staged in LDS.
 //
-// Every value that becomes an address (rowPtr, the columns, the block columns) is checked first by reorder::k_check_rowptr
+// Every value that becomes an address (rowPtr, the columns, the block columns) is checked first by k_check_rowptr
 // / k_check_cols; the host reads the flag before anything is queued that indexes with them.  dB is addressed with 64-bit
-// offsets throughout.  Included at the end of spgemm_hip.hip behind pcsr_device.hpp (uses reorder's checks, row search,
-// scan, radix and Scratch).
+// offsets throughout.  Uses csr_common_device.hpp (the checks and their one read-back, row search, lower bound, scan,
+// radix sort, Scratch).
 #pragma once
 
 namespace bcsr {
 
-using reorder::CP_THREADS;
-using reorder::CP_ITEMS;
-using reorder::CP_TILE;
+using namespace csrdev;
 
 constexpr int ROW_WAVES = 4;                       // rows (waves) per block of the two inverse kernels
 
@@ -47,12 +45,12 @@ __global__ __launch_bounds__(CP_THREADS) void k_keys(int m, int nnz, int r, int 
                                                      unsigned long long* __restrict__ keys, int* __restrict__ payload) {
   __shared__ int rows[2];
   const long long base = (long long)blockIdx.x * CP_TILE;
-  reorder::tile_rows(IA, m, nnz, base, rows);
+  tile_rows(IA, m, nnz, base, rows);
 #pragma unroll
   for (int k = 0; k < CP_ITEMS; ++k) {
     const long long o = base + k * CP_THREADS + threadIdx.x;
     if (o >= nnz) break;
-    const int row = reorder::row_of_entry(IA, rows[0], rows[1], (int)o);
+    const int row = row_of_entry(IA, rows[0], rows[1], (int)o);
     const int col = JA[o], brow = row / r, bcol = col / c;
     const unsigned cell = (unsigned)((row - brow * r) * c + (col - bcol * c));
     keys[o] = (((((unsigned long long)(unsigned)brow) << bcolBits) | (unsigned)bcol) << cellBits) | cell;
@@ -105,13 +103,7 @@ __global__ void k_group_rank(int nnzb, int bcolBits, const int* __restrict__ gid
 // IB[b] = first tile of block row b or later, b = 0..bm
 __global__ void k_block_rowptr(int bm, int nnzb, const int* __restrict__ tbrow, int* __restrict__ IB) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b > bm) return;
-  int lo = 0, hi = nnzb;
-  while (lo < hi) {
-    const int mid = (int)(((long long)lo + hi) >> 1);
-    if (tbrow[mid] < b) lo = mid + 1; else hi = mid;
-  }
-  IB[b] = lo;
+  if (b <= bm) IB[b] = first_at_least(tbrow, 0, nnzb, b);
 }
 
 // the last of every run of equal keys writes its cell (B has been zeroed)
@@ -185,9 +177,6 @@ __global__ __launch_bounds__(ROW_WAVES * 64) void k_rows(int m, int n, int r, in
   }
 }
 
-#define BC_ALLOC(...) if (!sc.get(__VA_ARGS__)) return sc.done(fail(SPGEMM_ERR_HIP, "device allocation failed"))
-#define BC_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
-
 static int check_tile_shape(int r, int c) {
   if (r < 1 || c < 1 || (long long)r * c > SPGEMM_BCSR_MAX_TILE)
     return fail(SPGEMM_ERR_ARG, "tile r=%d c=%d: need r >= 1, c >= 1, r * c <= %d", r, c, SPGEMM_BCSR_MAX_TILE);
@@ -199,54 +188,45 @@ static inline int blocks_of(int len, int tile) { return (int)(((long long)len + 
 template <class V>
 static int to_bcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const V* dA, int r, int c,
                    int** dIB, int** dJB, V** dB, int* nnzb) {
-  using namespace reorder;
   if (!dIB || !dJB || !dB || !nnzb) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIB = nullptr; *dJB = nullptr; *dB = nullptr; *nnzb = 0;
   CHK(check_tile_shape(r, c));
-  if (m < 0 || n < 0 || nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
-  if ((m > 0 && !dIA) || (nnz > 0 && (!dJA || !dA))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnz);
-  if (m == 0 && nnz > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnz);
+  CHK(check_csr_args(m, n, nnz, dIA, dJA, dA));
   const int bm = blocks_of(m, r), bn = blocks_of(n, c), rc = r * c;
   const int browBits = bits_of(bm - 1), bcolBits = bits_of(bn - 1), cellBits = bits_of(rc - 1);
   if (browBits + bcolBits + cellBits > 64)
     return fail(SPGEMM_ERR_INTERNAL, "sort key of %d + %d + %d bits", browBits, bcolBits, cellBits);
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
-  int *bad = nullptr, *IB = nullptr, *JB = nullptr, *idxA = nullptr, *idxB = nullptr, *bhist = nullptr, *gscan = nullptr,
+  int *IB = nullptr, *JB = nullptr, *idxA = nullptr, *idxB = nullptr, *bhist = nullptr, *gscan = nullptr,
       *gidB = nullptr, *rank = nullptr, *tbrow = nullptr;
   unsigned* minIdx = nullptr;
   V* B = nullptr;
   unsigned long long *keyA = nullptr, *keyB = nullptr, *tile = nullptr, *ghead = nullptr, *key2B = nullptr;
-  BC_ALLOC(&bad, sizeof(int));
-  BC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   // validation, one read-back: rowPtr (the key kernel searches it) and the column range (the block column becomes an address)
-  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnz, dIA, (int*)nullptr, (int*)nullptr, bad);
-  if (nnz > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnz), dim3(256), 0, s, nnz, n, dJA, bad);
   int hbad = 0;
-  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (int rc = validate_csr(sc, s, m, n, nnz, dIA, dJA, &hbad)) return sc.done(rc);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone row pointer ending at nnz=%d", nnz));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "column outside [0,%d)", n));
-  BC_ALLOC(&IB, sizeof(int) * ((size_t)bm + 1), true);
+  CSR_ALLOC(&IB, sizeof(int) * ((size_t)bm + 1), true);
   if (nnz == 0) {
-    BC_ALLOC(&JB, sizeof(int), true);
-    BC_ALLOC(&B, sizeof(V), true);
-    BC_HIP(hipMemsetAsync(IB, 0, sizeof(int) * ((size_t)bm + 1), s));
-    BC_HIP(hipStreamSynchronize(s));
+    CSR_ALLOC(&JB, sizeof(int), true);
+    CSR_ALLOC(&B, sizeof(V), true);
+    CSR_HIP(hipMemsetAsync(IB, 0, sizeof(int) * ((size_t)bm + 1), s));
+    CSR_HIP(hipStreamSynchronize(s));
     *dIB = IB; *dJB = JB; *dB = B;
     return sc.done(SPGEMM_OK);
   }
   // (1) entries sorted by (block row, block column, cell), storage order inside equal keys
-  const int nblk = cdiv(nnz, coo::RS_TILE);
-  BC_ALLOC(&keyA, sizeof(unsigned long long) * (size_t)nnz);
-  BC_ALLOC(&keyB, sizeof(unsigned long long) * (size_t)nnz);
-  BC_ALLOC(&idxA, sizeof(int) * (size_t)nnz);
-  BC_ALLOC(&idxB, sizeof(int) * (size_t)nnz);
-  BC_ALLOC(&bhist, sizeof(int) * ((size_t)nblk * coo::RS_RADIX + 1));
-  BC_ALLOC(&tile, scan_scratch_bytes(std::max<long long>((long long)nblk * coo::RS_RADIX, nnz) + 1));
-  BC_ALLOC(&gscan, sizeof(int) * ((size_t)nnz + 1));
+  const int nblk = cdiv(nnz, RS_TILE);
+  CSR_ALLOC(&keyA, sizeof(unsigned long long) * (size_t)nnz);
+  CSR_ALLOC(&keyB, sizeof(unsigned long long) * (size_t)nnz);
+  CSR_ALLOC(&idxA, sizeof(int) * (size_t)nnz);
+  CSR_ALLOC(&idxB, sizeof(int) * (size_t)nnz);
+  CSR_ALLOC(&bhist, sizeof(int) * ((size_t)nblk * RS_RADIX + 1));
+  CSR_ALLOC(&tile, scan_scratch_bytes(std::max<long long>((long long)nblk * RS_RADIX, nnz) + 1));
+  CSR_ALLOC(&gscan, sizeof(int) * ((size_t)nnz + 1));
   hipLaunchKernelGGL(k_keys, dim3((unsigned)cdiv(nnz, CP_TILE)), dim3(CP_THREADS), 0, s, m, nnz, r, c, bcolBits, cellBits,
                      dIA, dJA, keyA, idxA);
   radix_sort_bits(s, nnz, 0, browBits + bcolBits + cellBits, keyA, keyB, idxA, idxB, bhist, tile);
@@ -254,21 +234,21 @@ static int to_bcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, cons
   hipLaunchKernelGGL(k_group_heads, grid256(nnz), dim3(256), 0, s, nnz, cellBits, keyA, gscan);
   scan_inplace(s, gscan, nnz, tile);
   int groups = 0;
-  BC_HIP(hipMemcpyAsync(&groups, gscan + nnz, sizeof(int), hipMemcpyDeviceToHost, s));
-  BC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipMemcpyAsync(&groups, gscan + nnz, sizeof(int), hipMemcpyDeviceToHost, s));
+  CSR_HIP(hipStreamSynchronize(s));
   const long long cells = (long long)groups * rc;
   if (cells > INT_MAX)
     return sc.done(fail(SPGEMM_ERR_OVERFLOW, "%d tiles of %d x %d: %lld values do not fit int32", groups, r, c, cells));
-  BC_ALLOC(&JB, sizeof(int) * (size_t)groups, true);
-  BC_ALLOC(&B, sizeof(V) * (size_t)cells, true);
-  BC_ALLOC(&ghead, sizeof(unsigned long long) * (size_t)groups);
-  BC_ALLOC(&key2B, sizeof(unsigned long long) * (size_t)groups);
-  BC_ALLOC(&minIdx, sizeof(unsigned) * (size_t)groups);
-  BC_ALLOC(&gidB, sizeof(int) * (size_t)groups);
-  BC_ALLOC(&rank, sizeof(int) * (size_t)groups);
-  BC_ALLOC(&tbrow, sizeof(int) * (size_t)groups);
-  BC_HIP(hipMemsetAsync(minIdx, 0xff, sizeof(unsigned) * (size_t)groups, s));
-  BC_HIP(hipMemsetAsync(B, 0, sizeof(V) * (size_t)cells, s));
+  CSR_ALLOC(&JB, sizeof(int) * (size_t)groups, true);
+  CSR_ALLOC(&B, sizeof(V) * (size_t)cells, true);
+  CSR_ALLOC(&ghead, sizeof(unsigned long long) * (size_t)groups);
+  CSR_ALLOC(&key2B, sizeof(unsigned long long) * (size_t)groups);
+  CSR_ALLOC(&minIdx, sizeof(unsigned) * (size_t)groups);
+  CSR_ALLOC(&gidB, sizeof(int) * (size_t)groups);
+  CSR_ALLOC(&rank, sizeof(int) * (size_t)groups);
+  CSR_ALLOC(&tbrow, sizeof(int) * (size_t)groups);
+  CSR_HIP(hipMemsetAsync(minIdx, 0xff, sizeof(unsigned) * (size_t)groups, s));
+  CSR_HIP(hipMemsetAsync(B, 0, sizeof(V) * (size_t)cells, s));
   hipLaunchKernelGGL(k_group_min, grid256(nnz), dim3(256), 0, s, nnz, cellBits, keyA, idxA, gscan, ghead, minIdx);
   // (3) the tiles of a block row in first-occurrence order: the groups sorted by their smallest storage index.  The
   // first sort's spare arrays hold nnz >= groups elements and serve as this sort's first pair.
@@ -281,8 +261,8 @@ static int to_bcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, cons
   hipLaunchKernelGGL(k_block_rowptr, grid256((long long)bm + 1), dim3(256), 0, s, bm, groups, tbrow, IB);
   // (4) values
   hipLaunchKernelGGL(k_fill<V>, grid256(nnz), dim3(256), 0, s, nnz, rc, cellBits, keyA, idxA, gscan, rank, dA, B);
-  BC_HIP(hipGetLastError());
-  BC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipStreamSynchronize(s));
   *dIB = IB; *dJB = JB; *dB = B; *nnzb = groups;
   return sc.done(SPGEMM_OK);
 }
@@ -290,7 +270,6 @@ static int to_bcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, cons
 template <class V>
 static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int nnzb, const int* dIB, const int* dJB, const V* dB,
                   double drop_tol, int** dIC, int** dJC, V** dC, int* nnzC) {
-  using namespace reorder;
   if (!dIC || !dJC || !dC || !nnzC) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIC = nullptr; *dJC = nullptr; *dC = nullptr; *nnzC = 0;
   CHK(check_tile_shape(r, c));
@@ -299,46 +278,35 @@ static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int nnzb, const 
   if ((m > 0 && !dIB) || (nnzb > 0 && (!dJB || !dB))) return fail(SPGEMM_ERR_ARG, "BCSR arrays null with m=%d nnzb=%d", m, nnzb);
   if (m == 0 && nnzb > 0) return fail(SPGEMM_ERR_ARG, "nnzb=%d in a matrix without rows", nnzb);
   const int bm = blocks_of(m, r), bn = blocks_of(n, c);
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
-  int *bad = nullptr, *IC = nullptr, *JC = nullptr;
+  int *IC = nullptr, *JC = nullptr;
   V* C = nullptr;
   unsigned long long* tile = nullptr;
-  BC_ALLOC(&bad, sizeof(int));
-  BC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   // validation, one read-back: the block rowPtr against nnzb and every block column (both become addresses into dB / JC)
-  if (bm > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(bm), dim3(256), 0, s, bm, nnzb, dIB, (int*)nullptr, (int*)nullptr, bad);
-  if (nnzb > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnzb), dim3(256), 0, s, nnzb, bn, dJB, bad);
   int hbad = 0;
-  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (int rc = validate_csr(sc, s, bm, bn, nnzb, dIB, dJB, &hbad)) return sc.done(rc);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone block row pointer ending at nnzb=%d", nnzb));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "block column outside [0,%d)", bn));
-  BC_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
-  BC_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
+  CSR_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
+  CSR_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
   const dim3 grid((unsigned)std::max(1, blocks_of(m, ROW_WAVES))), block(ROW_WAVES * 64);
   if (m > 0)
     hipLaunchKernelGGL((k_rows<V, false>), grid, block, 0, s, m, n, r, c, dIB, dJB, dB, drop_tol, IC, (int*)nullptr, (V*)nullptr);
-  scan_inplace(s, IC, m, tile);
   unsigned long long total = 0;
-  BC_HIP(hipMemcpyAsync(&total, tile, sizeof(total), hipMemcpyDeviceToHost, s));
-  BC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(scan_total(s, IC, m, tile, &total));
   if (total > (unsigned long long)INT_MAX)
     return sc.done(fail(SPGEMM_ERR_OVERFLOW, "%llu entries do not fit the int32 CSR", total));
-  BC_ALLOC(&JC, sizeof(int) * (size_t)std::max<unsigned long long>(total, 1), true);
-  BC_ALLOC(&C, sizeof(V) * (size_t)std::max<unsigned long long>(total, 1), true);
+  CSR_ALLOC(&JC, sizeof(int) * (size_t)std::max<unsigned long long>(total, 1), true);
+  CSR_ALLOC(&C, sizeof(V) * (size_t)std::max<unsigned long long>(total, 1), true);
   if (total > 0)
     hipLaunchKernelGGL((k_rows<V, true>), grid, block, 0, s, m, n, r, c, dIB, dJB, dB, drop_tol, IC, JC, C);
-  BC_HIP(hipGetLastError());
-  BC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipStreamSynchronize(s));
   *dIC = IC; *dJC = JC; *dC = C; *nnzC = (int)total;
   return sc.done(SPGEMM_OK);
 }
-
-#undef BC_ALLOC
-#undef BC_HIP
 
 }  // namespace bcsr
 

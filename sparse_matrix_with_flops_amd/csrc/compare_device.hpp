@@ -9,19 +9,21 @@
 // The entries are the work items, A's first and then B's, dealt 1024 to a block whatever rows they belong to -- a
 // 20 000-entry row next to empty ones is spread over 20 blocks (40 with its partner row) like any other 20 000 entries.
 // An item finds its row by a search in its own rowPtr bounded by the rows of the first and the last item its block
-// holds of that matrix (reorder::row_of_entry, as k_permute_copy does), then its partner by a binary search for its
+// holds of that matrix (row_of_entry, as the copy kernels do), then its partner by a binary search for its
 // column in the same row of the other matrix.  A common column is accounted by A's item; a B item reports only when it
 // has no partner.  The same pass compares every item's column with its predecessor's in the row (the "not sorted" flag).
 // Reductions: counts and first rows by integer atomics, maxima as the bit patterns of non-negative doubles (ordered like
 // integers, so order-independent), sum_sq in double in a fixed order: lane sums its items in tile order, a fixed shuffle
 // tree per wave, the four waves in order, one partial per block, and a single-block kernel over the partials.  No
 // floating-point atomic anywhere: two calls on the same input return the same bits.
-// Both rowPtr arrays are checked (reorder::k_check_rowptr) and the flag is read before anything is queued that forms an
+// Both rowPtr arrays are checked (k_check_rowptr) and the flag is read before anything is queued that forms an
 // address from a rowPtr value.  Columns are only compared, never used as addresses.
-// Included in spgemm_hip.hip behind reorder_device.hpp (uses its rowPtr check, row search and Scratch).
+// Uses csr_common_device.hpp (the rowPtr check and its one read-back, row search, lower bound, Scratch).
 #pragma once
 
 namespace compare {
+
+using namespace csrdev;
 
 constexpr int CMP_THREADS = 256, CMP_ITEMS = 4, CMP_TILE = CMP_THREADS * CMP_ITEMS;
 constexpr int NO_ROW = 0x7fffffff;
@@ -88,13 +90,13 @@ __global__ __launch_bounds__(CMP_THREADS) void k_diff_walk(int m, int nnzA, int 
   const long long end = base + CMP_TILE < total ? base + CMP_TILE : total;
   if (threadIdx.x == 0 && base < nnzA) {
     const long long last = (end < nnzA ? end : (long long)nnzA) - 1;
-    rows[0] = reorder::row_of_entry(IA, 0, m - 1, (int)base);
-    rows[1] = reorder::row_of_entry(IA, rows[0], m - 1, (int)last);
+    rows[0] = row_of_entry(IA, 0, m - 1, (int)base);
+    rows[1] = row_of_entry(IA, rows[0], m - 1, (int)last);
   }
   if (threadIdx.x == 64 && end > nnzA) {
     const long long first = (base > nnzA ? base : (long long)nnzA) - nnzA;
-    rows[2] = reorder::row_of_entry(IB, 0, m - 1, (int)first);
-    rows[3] = reorder::row_of_entry(IB, rows[2], m - 1, (int)(end - 1 - nnzA));
+    rows[2] = row_of_entry(IB, 0, m - 1, (int)first);
+    rows[3] = row_of_entry(IB, rows[2], m - 1, (int)(end - 1 - nnzA));
   }
   __syncthreads();
   Seen s = {0u, 0u, 0u, NO_ROW, NO_ROW, 0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -108,15 +110,11 @@ __global__ __launch_bounds__(CMP_THREADS) void k_diff_walk(int m, int nnzA, int 
     const int* __restrict__ JX = isA ? JA : JB;
     const int* __restrict__ IY = isA ? IB : IA;
     const int* __restrict__ JY = isA ? JB : JA;
-    const int r = reorder::row_of_entry(IX, rows[isA ? 0 : 2], rows[isA ? 1 : 3], o);
+    const int r = row_of_entry(IX, rows[isA ? 0 : 2], rows[isA ? 1 : 3], o);
     const int c = JX[o];
     if (o > IX[r] && JX[o - 1] >= c) s.unsorted = 1;
     const int ye = IY[r + 1];
-    int lo = IY[r], hi = ye;
-    while (lo < hi) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (JY[mid] < c) lo = mid + 1; else hi = mid;
-    }
+    const int lo = first_at_least(JY, IY[r], ye, c);
     const bool found = lo < ye && JY[lo] == c;
     if (isA) {
       const double a = (double)A[o];
@@ -209,9 +207,6 @@ __global__ __launch_bounds__(256) void k_differs_stats(int m, const int* __restr
   if (threadIdx.x < np + 4 && hist[threadIdx.x]) atomicAdd(&counts[threadIdx.x], hist[threadIdx.x]);
 }
 
-#define CMP_ALLOC(...) if (!sc.get(__VA_ARGS__)) return sc.done(fail(SPGEMM_ERR_HIP, "device allocation failed"))
-#define CMP_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
-
 template <class V>
 static int diff(spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, const V* dA, int nnzA, const int* dIB,
                 const int* dJB, const V* dB, int nnzB, double rel_tol, double abs_tol, spgemm_csr_diff* out) {
@@ -225,38 +220,35 @@ static int diff(spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, 
   if (!(rel_tol >= 0.0) || !(abs_tol >= 0.0)) return fail(SPGEMM_ERR_ARG, "tolerances must be non-negative numbers");
   const auto none = [&]() { out->first_len_row = out->first_only_row = out->first_beyond_row = -1; return SPGEMM_OK; };
   if (m == 0) return none();
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
-  reorder::Scratch sc;
+  hipStream_t s;
+  CHK(enter(h, &s));
+  Scratch sc;
   int* bad = nullptr;
   Acc* acc = nullptr;
   double* partial = nullptr;
   // (1) both rowPtr arrays, read back before the walk forms addresses from them
-  CMP_ALLOC(&bad, sizeof(int));
-  CMP_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-  hipLaunchKernelGGL(reorder::k_check_rowptr, reorder::grid256(m), dim3(256), 0, s, m, nnzA, dIA, (int*)nullptr, (int*)nullptr, bad);
-  hipLaunchKernelGGL(reorder::k_check_rowptr, reorder::grid256(m), dim3(256), 0, s, m, nnzB, dIB, (int*)nullptr, (int*)nullptr, bad);
+  if (int rc = flag_begin(sc, s, &bad)) return sc.done(rc);
+  queue_csr_checks(s, m, n, nnzA, dIA, nullptr, bad);
+  queue_csr_checks(s, m, n, nnzB, dIB, nullptr, bad);
   int hbad = 0;
-  if (reorder::read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
   if (hbad) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone row pointer ending at nnz (nnzA=%d nnzB=%d)", nnzA, nnzB));
   const long long total = (long long)nnzA + nnzB;
   if (total == 0) return sc.done(none());
   // (2) row lengths, the walk, the partials
   const int nblk = cdiv(total, CMP_TILE);
   static const Acc fresh = {0, 0, 0, 0, 0, 0, 0, 0, NO_ROW, NO_ROW, NO_ROW, 0, 0, 0.0};
-  CMP_ALLOC(&acc, sizeof(Acc));
-  CMP_ALLOC(&partial, sizeof(double) * (size_t)nblk);
-  CMP_HIP(hipMemcpyAsync(acc, &fresh, sizeof(Acc), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_len_differ, reorder::grid256(m), dim3(256), 0, s, m, dIA, dIB, acc);
+  CSR_ALLOC(&acc, sizeof(Acc));
+  CSR_ALLOC(&partial, sizeof(double) * (size_t)nblk);
+  CSR_HIP(hipMemcpyAsync(acc, &fresh, sizeof(Acc), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_len_differ, grid256(m), dim3(256), 0, s, m, dIA, dIB, acc);
   hipLaunchKernelGGL(k_diff_walk<V>, dim3((unsigned)nblk), dim3(CMP_THREADS), 0, s, m, nnzA, nnzB, dIA, dJA, dA, dIB, dJB, dB,
                      rel_tol, abs_tol, acc, partial);
   hipLaunchKernelGGL(k_diff_sum, dim3(1), dim3(CMP_THREADS), 0, s, nblk, partial, acc);
-  CMP_HIP(hipGetLastError());
+  CSR_HIP(hipGetLastError());
   Acc got;
-  CMP_HIP(hipMemcpyAsync(&got, acc, sizeof(Acc), hipMemcpyDeviceToHost, s));
-  CMP_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipMemcpyAsync(&got, acc, sizeof(Acc), hipMemcpyDeviceToHost, s));
+  CSR_HIP(hipStreamSynchronize(s));
   if (got.unsorted) return sc.done(fail(SPGEMM_ERR_INPUT, "a row is not strictly ascending by column (sort the rows first: hip_csr_sort_rows)"));
   const auto row = [](int r) { return r == NO_ROW ? -1 : r; };
   const auto val = [](unsigned long long b) { double d; memcpy(&d, &b, sizeof(d)); return d; };
@@ -285,26 +277,21 @@ static int differs_stats(spgemm_handle* h, int m, const int* dIA, const int* dIB
   const int slots = npercents + 4;
   memset(counts, 0, sizeof(int) * (size_t)slots);
   if (m == 0) return SPGEMM_OK;
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
-  reorder::Scratch sc;
+  hipStream_t s;
+  CHK(enter(h, &s));
+  Scratch sc;
   int* dcounts = nullptr;
   Q* dpercents = nullptr;
-  CMP_ALLOC(&dcounts, sizeof(int) * (size_t)slots);
-  CMP_ALLOC(&dpercents, sizeof(Q) * (size_t)MAX_PERCENTS);
-  CMP_HIP(hipMemsetAsync(dcounts, 0, sizeof(int) * (size_t)slots, s));
-  if (npercents > 0) CMP_HIP(hipMemcpyAsync(dpercents, percents, sizeof(Q) * (size_t)npercents, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_differs_stats<Q>, reorder::grid256(m), dim3(256), 0, s, m, dIA, dIB, dpercents, npercents, dcounts);
-  CMP_HIP(hipGetLastError());
-  CMP_HIP(hipMemcpyAsync(counts, dcounts, sizeof(int) * (size_t)slots, hipMemcpyDeviceToHost, s));
-  CMP_HIP(hipStreamSynchronize(s));
+  CSR_ALLOC(&dcounts, sizeof(int) * (size_t)slots);
+  CSR_ALLOC(&dpercents, sizeof(Q) * (size_t)MAX_PERCENTS);
+  CSR_HIP(hipMemsetAsync(dcounts, 0, sizeof(int) * (size_t)slots, s));
+  if (npercents > 0) CSR_HIP(hipMemcpyAsync(dpercents, percents, sizeof(Q) * (size_t)npercents, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_differs_stats<Q>, grid256(m), dim3(256), 0, s, m, dIA, dIB, dpercents, npercents, dcounts);
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipMemcpyAsync(counts, dcounts, sizeof(int) * (size_t)slots, hipMemcpyDeviceToHost, s));
+  CSR_HIP(hipStreamSynchronize(s));
   return sc.done(SPGEMM_OK);
 }
-
-#undef CMP_ALLOC
-#undef CMP_HIP
 
 }  // namespace compare
 

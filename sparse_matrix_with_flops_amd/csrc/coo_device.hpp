@@ -9,81 +9,16 @@
 // i.e. what rmclInit (nlibs/qrmcl.cc:126-134) and the Matrix-Market/SNAP loaders do after parsing the text.
 //
 // The sort is our own stable LSD radix sort (8 bits per pass: per-block digit histograms in LDS, the library's scan
-// kernels over the digit-major histogram, ballot-ranked stable scatter) of the 64-bit key row*cols+col carrying the
-// entry's input position, over exactly the bits the shape needs.  Stable order = input order inside a run of equal
+// kernels over the digit-major histogram, ballot-ranked stable scatter) of the 64-bit key (row << colBits) | col carrying
+// the entry's value, over exactly the bits the shape needs.  Stable order = input order inside a run of equal
 // (row,col), so duplicates are summed left to right like the CPU loop (bit-exact floats; a run is summed by one lane,
 // which is what keeps the order -- a pair repeated very many times serialises that lane).
-// Included at the end of spgemm_hip.hip (uses its pool / error helpers and the k_scan_* kernels).
+// Uses csr_common_device.hpp (the radix sort, scan, Scratch, call prologue).
 #pragma once
 
 namespace coo {
 
-constexpr int RS_THREADS = 256, RS_ITEMS = 8, RS_TILE = RS_THREADS * RS_ITEMS, RS_RADIX = 256;
-
-// pass 1 of a digit: how many keys of every digit value each block holds; blockHist is digit-major [256][nblk]
-__global__ __launch_bounds__(RS_THREADS) void k_radix_hist(int n, const unsigned long long* __restrict__ keys, int shift,
-                                                           int nblk, int* __restrict__ blockHist) {
-  __shared__ int hist[RS_RADIX];
-  const int tid = threadIdx.x;
-  hist[tid] = 0;
-  __syncthreads();
-  const long long base = (long long)blockIdx.x * RS_TILE;
-#pragma unroll
-  for (int i = 0; i < RS_ITEMS; ++i) {
-    const long long idx = base + i * RS_THREADS + tid;
-    if (idx < n) atomicAdd(&hist[(int)((keys[idx] >> shift) & 255ull)], 1);
-  }
-  __syncthreads();
-  blockHist[(size_t)tid * nblk + blockIdx.x] = hist[tid];
-}
-
-// pass 2: stable scatter.  blockOff = exclusive scan of blockHist (digit-major, block-minor): where the block's keys
-// of each digit start.  Inside the block the order is (round, wave, lane) = index order: per round every wave ranks its
-// lanes among the lanes with the same digit (8 ballots), one thread per digit turns the per-wave counts into offsets.
-__global__ __launch_bounds__(RS_THREADS) void k_radix_scatter(int n, const unsigned long long* __restrict__ keysIn,
-                                                              const int* __restrict__ idxIn,
-                                                              unsigned long long* __restrict__ keysOut, int* __restrict__ idxOut,
-                                                              int shift, int nblk, const int* __restrict__ blockOff) {
-  constexpr int NWV = RS_THREADS / smf::WAVE;
-  __shared__ int wcnt[NWV][RS_RADIX];
-  __shared__ int woff[NWV][RS_RADIX];
-  __shared__ int run[RS_RADIX];
-  const int tid = threadIdx.x, w = tid >> 6;
-  run[tid] = blockOff[(size_t)tid * nblk + blockIdx.x];
-  const long long base = (long long)blockIdx.x * RS_TILE;
-  for (int i = 0; i < RS_ITEMS; ++i) {
-#pragma unroll
-    for (int q = 0; q < NWV; ++q) wcnt[q][tid] = 0;
-    __syncthreads();
-    const long long idx = base + i * RS_THREADS + tid;
-    const bool valid = idx < n;
-    unsigned long long key = 0ull;
-    int payload = 0;
-    if (valid) { key = keysIn[idx]; payload = idxIn[idx]; }
-    const int d = (int)((key >> shift) & 255ull);
-    unsigned long long peers = smf::ballot64(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const unsigned long long mb = smf::ballot64(valid && ((d >> b) & 1));
-      peers &= ((d >> b) & 1) ? mb : ~mb;
-    }
-    const int rank = smf::mask_rank(peers);
-    if (valid && rank == 0) wcnt[w][d] = __popcll(peers);
-    __syncthreads();
-    {
-      int r = run[tid];
-#pragma unroll
-      for (int q = 0; q < NWV; ++q) { woff[q][tid] = r; r += wcnt[q][tid]; }
-      run[tid] = r;
-    }
-    __syncthreads();
-    if (valid) {
-      const int dst = woff[w][d] + rank;
-      keysOut[dst] = key;
-      idxOut[dst] = payload;
-    }
-  }
-}
+using namespace csrdev;
 
 __global__ void k_check_and_diag(int nnz, int rows, int cols, const int* __restrict__ ri, const int* __restrict__ ci,
                                  unsigned char* __restrict__ hasDiag, int* __restrict__ bad) {
@@ -143,13 +78,7 @@ __global__ void k_row_starts(int rows, int n, int colBits, const unsigned long l
                              const int* __restrict__ pos, int* __restrict__ IA) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r > rows) return;
-  const unsigned long long want = (unsigned long long)(unsigned)r << colBits;
-  int lo = 0, hi = n;                            // first index with keys[idx] >= want
-  while (lo < hi) {
-    const int mid = (int)(((long long)lo + hi) >> 1);
-    if (keys[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  IA[r] = pos[lo];
+  IA[r] = pos[first_at_least(keys, 0, n, (unsigned long long)(unsigned)r << colBits)];
 }
 
 __global__ void k_row_normalise(int rows, const int* __restrict__ IA, float* __restrict__ A) {
@@ -169,130 +98,87 @@ extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, con
   if (rows < 0 || cols < 0 || nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
   if (nnz > 0 && (!dRow || !dCol || !dVal)) return fail(SPGEMM_ERR_ARG, "COO arrays null with nnz=%d", nnz);
   if ((flags & SPGEMM_COO_SELF_LOOPS) && rows != cols) return fail(SPGEMM_ERR_ARG, "self loops need a square matrix");
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  using namespace coo;
+  hipStream_t s;
+  CHK(enter(h, &s));
   const int dedupe = (flags & SPGEMM_COO_DEDUPE) ? 1 : 0;
   const bool loops = (flags & SPGEMM_COO_SELF_LOOPS) != 0;
   const long long maxTotal = (long long)nnz + (loops ? rows : 0);
   if (maxTotal > 0x7fffffffLL) return fail(SPGEMM_ERR_OVERFLOW, "nnz does not fit int32");
 
+  Scratch sc;
   unsigned char* hasDiag = nullptr;
   int *bad = nullptr, *miss = nullptr, *missPos = nullptr, *idxA = nullptr, *idxB = nullptr, *head = nullptr, *pos = nullptr;
-  unsigned long long *keyA = nullptr, *keyB = nullptr;
-  void* tmp = nullptr;
+  unsigned long long *keyA = nullptr, *keyB = nullptr, *tile = nullptr;
   int* bhist = nullptr;                          // digit-major per-block histograms / offsets of the radix passes
   int *IA = nullptr, *JA = nullptr;
   float* A = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)hasDiag, (void*)bad, (void*)miss, (void*)missPos, (void*)idxA, (void*)idxB, (void*)head,
-                    (void*)pos, (void*)keyA, (void*)keyB, tmp, (void*)bhist})
-      pool().release(p);
-    if (rc != SPGEMM_OK) { pool().release(IA); pool().release(JA); pool().release(A); }
-    return rc;
-  };
-#define COO_ALLOC(ptr, bytes) if (pool().alloc((void**)&(ptr), (bytes)) != hipSuccess) return cleanup(fail(SPGEMM_ERR_HIP, "device allocation failed"))
-#define COO_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return cleanup(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
-  const int T = 256;
-  auto grid = [&](long long n) { return dim3((unsigned)std::max<long long>(1, (n + T - 1) / T)); };
-  auto bits_of = [](int maxval) { return maxval > 0 ? 32 - __builtin_clz((unsigned)maxval) : 0; };
   const int colBits = std::max(1, bits_of(cols - 1));      // key = (row << colBits) | col
   const int keyBits = std::max(1, bits_of(rows - 1) + colBits);
   // scratch of the scans: tile sums of the longest array scanned below (entries, rows + 1, or 256 x radix blocks)
-  const long long nblkMax = (maxTotal + coo::RS_TILE - 1) / coo::RS_TILE + 1;
-  const long long longest = std::max<long long>(std::max<long long>(maxTotal, (long long)rows + 1), nblkMax * coo::RS_RADIX) + 1;
-  unsigned long long* tile = nullptr;
-  COO_ALLOC(tmp, sizeof(unsigned long long) * (size_t)((longest + SCAN_TILE - 1) / SCAN_TILE + 2));
-  tile = (unsigned long long*)tmp;
-  // in-place exclusive scan of data[0..cnt) with data[cnt] = total (k_scan_* of the SpGEMM path), 64-bit total on the host
-  auto scan_inplace = [&](int* data, int cnt, unsigned long long* hostTotal) -> hipError_t {
-    const int ntiles = std::max(1, cdiv(cnt, SCAN_TILE));
-    hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(SCAN_THREADS), 0, s, cnt, data, tile + 1);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, ntiles, tile + 1, tile);
-    hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(SCAN_THREADS), 0, s, cnt, data, tile + 1, tile, 1);
-    if (hostTotal) {
-      hipError_t e = hipMemcpyAsync(hostTotal, tile, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-      if (e != hipSuccess) return e;
-      return hipStreamSynchronize(s);
-    }
-    return hipGetLastError();
-  };
-  COO_ALLOC(bad, sizeof(int));
-  COO_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  const long long nblkMax = (maxTotal + RS_TILE - 1) / RS_TILE + 1;
+  const long long longest = std::max<long long>(std::max<long long>(maxTotal, (long long)rows + 1), nblkMax * RS_RADIX) + 1;
+  CSR_ALLOC(&tile, scan_scratch_bytes(longest));
+  if (int rc = flag_begin(sc, s, &bad)) return sc.done(rc);
   // (1) validation, diagonal flags, self loops to append
   int extra = 0;
   if (loops && rows > 0) {
-    COO_ALLOC(hasDiag, (size_t)rows);
-    COO_ALLOC(miss, sizeof(int) * (size_t)rows);
-    COO_ALLOC(missPos, sizeof(int) * ((size_t)rows + 1));
-    COO_HIP(hipMemsetAsync(hasDiag, 0, (size_t)rows, s));
+    CSR_ALLOC(&hasDiag, (size_t)rows);
+    CSR_ALLOC(&miss, sizeof(int) * (size_t)rows);
+    CSR_ALLOC(&missPos, sizeof(int) * ((size_t)rows + 1));
+    CSR_HIP(hipMemsetAsync(hasDiag, 0, (size_t)rows, s));
   }
-  if (nnz > 0) hipLaunchKernelGGL(coo::k_check_and_diag, grid(nnz), dim3(T), 0, s, nnz, rows, cols, dRow, dCol, hasDiag, bad);
+  if (nnz > 0) hipLaunchKernelGGL(k_check_and_diag, grid256(nnz), dim3(256), 0, s, nnz, rows, cols, dRow, dCol, hasDiag, bad);
   if (loops && rows > 0) {
-    hipLaunchKernelGGL(coo::k_missing_flags, grid(rows), dim3(T), 0, s, rows, hasDiag, miss);
-    COO_HIP(hipMemcpyAsync(missPos, miss, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(k_missing_flags, grid256(rows), dim3(256), 0, s, rows, hasDiag, miss);
+    CSR_HIP(hipMemcpyAsync(missPos, miss, sizeof(int) * (size_t)rows, hipMemcpyDeviceToDevice, s));
     unsigned long long nmiss = 0;
-    COO_HIP(scan_inplace(missPos, rows, &nmiss));
+    CSR_HIP(scan_total(s, missPos, rows, tile, &nmiss));
     extra = (int)nmiss;
   }
   int hbad = 0;
-  COO_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  COO_HIP(hipStreamSynchronize(s));
-  if (hbad) return cleanup(fail(SPGEMM_ERR_INPUT, "COO entry outside the %d x %d matrix", rows, cols));
+  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (hbad) return sc.done(fail(SPGEMM_ERR_INPUT, "COO entry outside the %d x %d matrix", rows, cols));
   const int total = nnz + extra;
-  COO_ALLOC(IA, sizeof(int) * ((size_t)rows + 1));
-  COO_HIP(hipMemsetAsync(IA, 0, sizeof(int) * ((size_t)rows + 1), s));
+  CSR_ALLOC(&IA, sizeof(int) * ((size_t)rows + 1), true);
+  CSR_HIP(hipMemsetAsync(IA, 0, sizeof(int) * ((size_t)rows + 1), s));
   if (total == 0) {
-    COO_ALLOC(JA, sizeof(int));
-    COO_ALLOC(A, sizeof(float));
-    COO_HIP(hipStreamSynchronize(s));
+    CSR_ALLOC(&JA, sizeof(int), true);
+    CSR_ALLOC(&A, sizeof(float), true);
+    CSR_HIP(hipStreamSynchronize(s));
     *dIA = IA; *dJA = JA; *dA = A; *nnzOut = 0;
-    return cleanup(SPGEMM_OK);
+    return sc.done(SPGEMM_OK);
   }
-  // (2) keys + stable sort
-  COO_ALLOC(keyA, sizeof(unsigned long long) * (size_t)total);
-  COO_ALLOC(keyB, sizeof(unsigned long long) * (size_t)total);
-  COO_ALLOC(idxA, sizeof(int) * (size_t)total);
-  COO_ALLOC(idxB, sizeof(int) * (size_t)total);
-  hipLaunchKernelGGL(coo::k_make_keys, grid(std::max(nnz, loops ? rows : 0)), dim3(T), 0, s, nnz, rows, colBits, dRow, dCol,
+  // (2) keys + stable sort over exactly the bits the shape needs; the sorted arrays are (keyA, idxA)
+  CSR_ALLOC(&keyA, sizeof(unsigned long long) * (size_t)total);
+  CSR_ALLOC(&keyB, sizeof(unsigned long long) * (size_t)total);
+  CSR_ALLOC(&idxA, sizeof(int) * (size_t)total);
+  CSR_ALLOC(&idxB, sizeof(int) * (size_t)total);
+  CSR_ALLOC(&bhist, sizeof(int) * ((size_t)cdiv(total, RS_TILE) * RS_RADIX + 1));
+  hipLaunchKernelGGL(k_make_keys, grid256(std::max(nnz, loops ? rows : 0)), dim3(256), 0, s, nnz, rows, colBits, dRow, dCol,
                      dVal, missPos, loops ? miss : (int*)nullptr, keyA, idxA);
-  {
-    const int nblk = cdiv(total, coo::RS_TILE);
-    COO_ALLOC(bhist, sizeof(int) * ((size_t)nblk * coo::RS_RADIX + 1));
-    for (int shift = 0; shift < keyBits; shift += 8) {     // stable LSD passes over exactly the bits the shape needs
-      hipLaunchKernelGGL(coo::k_radix_hist, dim3(nblk), dim3(coo::RS_THREADS), 0, s, total, keyA, shift, nblk, bhist);
-      COO_HIP(scan_inplace(bhist, nblk * coo::RS_RADIX, nullptr));
-      hipLaunchKernelGGL(coo::k_radix_scatter, dim3(nblk), dim3(coo::RS_THREADS), 0, s, total, keyA, idxA, keyB, idxB, shift,
-                         nblk, bhist);
-      std::swap(keyA, keyB);
-      std::swap(idxA, idxB);
-    }
-    std::swap(keyA, keyB);                                 // the sorted arrays are called keyB / idxB below
-    std::swap(idxA, idxB);
-  }
+  radix_sort_bits(s, total, 0, keyBits, keyA, keyB, idxA, idxB, bhist, tile);
+  CSR_HIP(hipGetLastError());
   // (3) heads of runs -> output positions
-  COO_ALLOC(head, sizeof(int) * (size_t)total);
-  COO_ALLOC(pos, sizeof(int) * ((size_t)total + 1));
-  hipLaunchKernelGGL(coo::k_heads, grid(total), dim3(T), 0, s, total, keyB, dedupe, pos);
-  COO_HIP(hipMemcpyAsync(head, pos, sizeof(int) * (size_t)total, hipMemcpyDeviceToDevice, s));
+  CSR_ALLOC(&head, sizeof(int) * (size_t)total);
+  CSR_ALLOC(&pos, sizeof(int) * ((size_t)total + 1));
+  hipLaunchKernelGGL(k_heads, grid256(total), dim3(256), 0, s, total, keyA, dedupe, pos);
+  CSR_HIP(hipMemcpyAsync(head, pos, sizeof(int) * (size_t)total, hipMemcpyDeviceToDevice, s));
   unsigned long long nheads = 0;
-  COO_HIP(scan_inplace(pos, total, &nheads));
+  CSR_HIP(scan_total(s, pos, total, tile, &nheads));
   const int outN = (int)nheads;
   // (4) emit columns / values / row counts, scan the counts, optional row normalisation
-  COO_ALLOC(JA, sizeof(int) * (size_t)std::max(outN, 1));
-  COO_ALLOC(A, sizeof(float) * (size_t)std::max(outN, 1));
-  hipLaunchKernelGGL(coo::k_emit, grid(total), dim3(T), 0, s, total, colBits, keyB, idxB, head, pos, dedupe,
+  CSR_ALLOC(&JA, sizeof(int) * (size_t)std::max(outN, 1), true);
+  CSR_ALLOC(&A, sizeof(float) * (size_t)std::max(outN, 1), true);
+  hipLaunchKernelGGL(k_emit, grid256(total), dim3(256), 0, s, total, colBits, keyA, idxA, head, pos, dedupe,
                      (flags & SPGEMM_COO_ABS) ? 1 : 0, JA, A);
-  hipLaunchKernelGGL(coo::k_row_starts, grid((long long)rows + 1), dim3(T), 0, s, rows, total, colBits, keyB, pos, IA);
+  hipLaunchKernelGGL(k_row_starts, grid256((long long)rows + 1), dim3(256), 0, s, rows, total, colBits, keyA, pos, IA);
   if ((flags & SPGEMM_COO_ROW_NORMALISE) && rows > 0)
-    hipLaunchKernelGGL(coo::k_row_normalise, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, rows, IA, A);
-  COO_HIP(hipGetLastError());
-  COO_HIP(hipStreamSynchronize(s));
-#undef COO_ALLOC
-#undef COO_HIP
+    hipLaunchKernelGGL(k_row_normalise, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, rows, IA, A);
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipStreamSynchronize(s));
   *dIA = IA; *dJA = JA; *dA = A; *nnzOut = outN;
-  return cleanup(SPGEMM_OK);
+  return sc.done(SPGEMM_OK);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -321,49 +207,45 @@ __global__ void k_pow2_hist(int m, const int* __restrict__ val, const int* __res
 
 extern "C" int hip_flopsStats(spgemm_handle* h, const int* dIA, const int* dJA, const int* dIB, int m,
                               int stats[SPGEMM_STATS_LEN]) {
+  using namespace coo;
   if (!stats) return fail(SPGEMM_ERR_ARG, "stats is null");
   for (int i = 0; i < SPGEMM_STATS_LEN; ++i) stats[i] = 0;
   if (m < 0 || !dIA) return fail(SPGEMM_ERR_ARG, "bad argument");
   if (m == 0) return SPGEMM_OK;
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
+  hipStream_t s;
+  CHK(enter(h, &s));
+  Scratch sc;
   int *flops = nullptr, *hist = nullptr;
-  auto cleanup = [&](int rc) { pool().release(flops); pool().release(hist); return rc; };
-  if (pool().alloc((void**)&flops, sizeof(int) * (size_t)m) != hipSuccess ||
-      pool().alloc((void**)&hist, sizeof(int) * SPGEMM_STATS_LEN) != hipSuccess)
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation failed"));
+  CSR_ALLOC(&flops, sizeof(int) * (size_t)m);
+  CSR_ALLOC(&hist, sizeof(int) * SPGEMM_STATS_LEN);
   int rc = hip_csr_row_flops(h, dIA, dJA, dIB, m, flops, nullptr);
-  if (rc) return cleanup(rc);
-  if (hipMemsetAsync(hist, 0, sizeof(int) * SPGEMM_STATS_LEN, h->stream) != hipSuccess) return cleanup(fail(SPGEMM_ERR_HIP, "memset failed"));
-  hipLaunchKernelGGL(coo::k_pow2_hist, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, m, flops, (const int*)nullptr,
-                     SPGEMM_STATS_LEN, hist);
-  if (hipMemcpyAsync(stats, hist, sizeof(int) * SPGEMM_STATS_LEN, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return cleanup(fail(SPGEMM_ERR_HIP, "flops statistics failed: %s", hipGetErrorString(hipGetLastError())));
-  return cleanup(SPGEMM_OK);
+  if (rc) return sc.done(rc);
+  if (hipMemsetAsync(hist, 0, sizeof(int) * SPGEMM_STATS_LEN, s) != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "memset failed"));
+  hipLaunchKernelGGL(k_pow2_hist, grid256(m), dim3(256), 0, s, m, flops, (const int*)nullptr, SPGEMM_STATS_LEN, hist);
+  if (hipMemcpyAsync(stats, hist, sizeof(int) * SPGEMM_STATS_LEN, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return sc.done(fail(SPGEMM_ERR_HIP, "flops statistics failed: %s", hipGetErrorString(hipGetLastError())));
+  return sc.done(SPGEMM_OK);
 }
-
 
 // vector<int> CSR::nnzStats() (nlibs/CSR.cc:241-248): 18 power-of-two buckets of the ROW LENGTHS of a device CSR
 extern "C" int hip_nnzStats(spgemm_handle* h, const int* dIA, int m, int stats[SPGEMM_NNZ_STATS_LEN]) {
+  using namespace coo;
   if (!stats) return fail(SPGEMM_ERR_ARG, "stats is null");
   for (int i = 0; i < SPGEMM_NNZ_STATS_LEN; ++i) stats[i] = 0;
   if (m < 0 || !dIA) return fail(SPGEMM_ERR_ARG, "bad argument");
   if (m == 0) return SPGEMM_OK;
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
+  hipStream_t s;
+  CHK(enter(h, &s));
+  Scratch sc;
   int* hist = nullptr;
-  auto cleanup = [&](int rc) { pool().release(hist); return rc; };
-  if (pool().alloc((void**)&hist, sizeof(int) * SPGEMM_NNZ_STATS_LEN) != hipSuccess) return cleanup(fail(SPGEMM_ERR_HIP, "device allocation failed"));
-  if (hipMemsetAsync(hist, 0, sizeof(int) * SPGEMM_NNZ_STATS_LEN, h->stream) != hipSuccess) return cleanup(fail(SPGEMM_ERR_HIP, "memset failed"));
-  hipLaunchKernelGGL(coo::k_pow2_hist, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream, m, (const int*)nullptr, dIA,
-                     SPGEMM_NNZ_STATS_LEN, hist);
-  if (hipMemcpyAsync(stats, hist, sizeof(int) * SPGEMM_NNZ_STATS_LEN, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-      hipStreamSynchronize(h->stream) != hipSuccess)
-    return cleanup(fail(SPGEMM_ERR_HIP, "row-length statistics failed: %s", hipGetErrorString(hipGetLastError())));
-  return cleanup(SPGEMM_OK);
+  CSR_ALLOC(&hist, sizeof(int) * SPGEMM_NNZ_STATS_LEN);
+  if (hipMemsetAsync(hist, 0, sizeof(int) * SPGEMM_NNZ_STATS_LEN, s) != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "memset failed"));
+  hipLaunchKernelGGL(k_pow2_hist, grid256(m), dim3(256), 0, s, m, (const int*)nullptr, dIA, SPGEMM_NNZ_STATS_LEN, hist);
+  if (hipMemcpyAsync(stats, hist, sizeof(int) * SPGEMM_NNZ_STATS_LEN, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return sc.done(fail(SPGEMM_ERR_HIP, "row-length statistics failed: %s", hipGetErrorString(hipGetLastError())));
+  return sc.done(SPGEMM_OK);
 }
 
 // ------------------------------------------------------------------------------------------------

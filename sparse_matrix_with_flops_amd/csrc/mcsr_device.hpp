@@ -30,18 +30,17 @@
 //
 // Inverse.  bcsr::to_csr on the corner (m = blockRows, n = blockCols: a temporary CSR), then a row-wise concatenation with
 // the remainder: row lengths added, the library's scan (its 64-bit total decides the overflow), one copy kernel dealt by
-// OUTPUT entries as pcsr::k_join_copy.
+// OUTPUT entries (tile_copy).
 //
 // Every value that becomes an address (rowPtr, the columns, the block rowPtr and columns) is checked first by
-// reorder::k_check_rowptr / k_check_cols (here or inside the bcsr:: calls); the host reads the flag before anything is
-// queued that indexes with them.  Included at the end of spgemm_hip.hip behind bcsr_device.hpp.
+// k_check_rowptr / k_check_cols (here or inside the calls into bcsr_device.hpp); the host reads the flag before anything
+// is queued that indexes with them.  Uses csr_common_device.hpp (the checks and their one read-back, scan, tile copy,
+// Scratch) and bcsr_device.hpp.
 #pragma once
 
 namespace mcsr {
 
-using reorder::CP_THREADS;
-using reorder::CP_ITEMS;
-using reorder::CP_TILE;
+using namespace csrdev;
 
 // flag[o] = 1 where entry o < nTop lies left of blockCols (its row is above blockRows by the choice of nTop)
 __global__ __launch_bounds__(CP_THREADS) void k_flags(int nTop, int blockCols, const int* __restrict__ JA,
@@ -101,54 +100,27 @@ __global__ void k_cat_lens(int m, int blockRows, const int* __restrict__ IT, con
   IC[i] = (int)len;
 }
 
-// One tile of C's entries per block, as pcsr::k_join_copy: the row by a search in IC bounded by the tile's rows, then the
-// corner's row first and the remainder's behind it; lane-strided reads staged in LDS, 16-byte stores.  The corner sits at
-// the top left, so its columns are global already.
+// One tile of C's entries per block (tile_copy): the corner's row first and the remainder's behind it.  The corner sits
+// at the top left, so its columns are global already.
 template <class V>
 __global__ __launch_bounds__(CP_THREADS) void k_cat_copy(int m, int nnz, int blockRows, const int* __restrict__ IT,
                                                          const int* __restrict__ JT, const V* __restrict__ T,
                                                          const int* __restrict__ IR, const int* __restrict__ JR,
                                                          const V* __restrict__ R, const int* __restrict__ IC,
                                                          int* __restrict__ JC, V* __restrict__ C) {
-  __shared__ int rows[2];
-  __shared__ __attribute__((aligned(16))) int sc[CP_TILE];
-  __shared__ __attribute__((aligned(16))) V sv[CP_TILE];
-  const long long base = (long long)blockIdx.x * CP_TILE;
-  reorder::tile_rows(IC, m, nnz, base, rows);
-#pragma unroll
-  for (int k = 0; k < CP_ITEMS; ++k) {
-    const int t = k * CP_THREADS + threadIdx.x;
-    const long long o = base + t;
-    if (o < nnz) {
-      const int r = reorder::row_of_entry(IC, rows[0], rows[1], (int)o);
-      const int off = (int)o - IC[r];
-      int s = 0, len = 0;
-      if (r < blockRows) { s = IT[r]; len = IT[r + 1] - s; }
-      if (off < len) {
-        sc[t] = JT[s + off];
-        sv[t] = T[s + off];
-      } else {
-        const int p = IR[r] + (off - len);
-        sc[t] = JR[p];
-        sv[t] = R[p];
-      }
+  tile_copy<V>(m, nnz, IC, JC, C, [&](int r, int off, int& col, V& val) {
+    int s = 0, len = 0;
+    if (r < blockRows) { s = IT[r]; len = IT[r + 1] - s; }
+    if (off < len) {
+      col = JT[s + off];
+      val = T[s + off];
+    } else {
+      const int p = IR[r] + (off - len);
+      col = JR[p];
+      val = R[p];
     }
-  }
-  __syncthreads();
-  const int t0 = threadIdx.x * CP_ITEMS;
-  const long long o0 = base + t0;
-  if (o0 >= nnz) return;
-  if (o0 + CP_ITEMS <= nnz) {
-    *reinterpret_cast<int4*>(JC + o0) = *reinterpret_cast<const int4*>(sc + t0);
-    const V v[CP_ITEMS] = {sv[t0], sv[t0 + 1], sv[t0 + 2], sv[t0 + 3]};
-    reorder::store4<V>(C + o0, v);
-  } else {
-    for (int k = 0; o0 + k < nnz; ++k) { JC[o0 + k] = sc[t0 + k]; C[o0 + k] = sv[t0 + k]; }
-  }
+  });
 }
-
-#define MC_ALLOC(...) if (!sc.get(__VA_ARGS__)) return sc.done(fail(SPGEMM_ERR_HIP, "device allocation failed"))
-#define MC_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
 
 static int check_corner(int m, int n, int r, int c, int blockRows, int blockCols) {
   CHK(bcsr::check_tile_shape(r, c));
@@ -164,58 +136,52 @@ template <class V>
 static int to_mcsr(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const V* dA, int r, int c,
                    int blockRows, int blockCols, int** dIB, int** dJB, V** dB, int* nnzb, int** dIR, int** dJR, V** dR,
                    int* nnzR) {
-  using namespace reorder;
   if (!dIB || !dJB || !dB || !nnzb || !dIR || !dJR || !dR || !nnzR) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIB = nullptr; *dJB = nullptr; *dB = nullptr; *nnzb = 0;
   *dIR = nullptr; *dJR = nullptr; *dR = nullptr; *nnzR = 0;
   if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
   CHK(check_corner(m, n, r, c, blockRows, blockCols));
-  if ((m > 0 && !dIA) || (nnz > 0 && (!dJA || !dA))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnz);
-  if (m == 0 && nnz > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnz);
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  CHK(check_csr_args(m, n, nnz, dIA, dJA, dA));
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
   int *bad = nullptr, *scan = nullptr, *IK = nullptr, *JK = nullptr, *IR = nullptr, *JR = nullptr;
   V *K = nullptr, *R = nullptr;
   unsigned long long* tile = nullptr;
-  MC_ALLOC(&bad, sizeof(int));
-  MC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   // validation, one read-back: rowPtr (IA[blockRows] cuts the entries, scan is indexed with IA) and the column range
-  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnz, dIA, (int*)nullptr, (int*)nullptr, bad);
-  if (nnz > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnz), dim3(256), 0, s, nnz, n, dJA, bad);
+  if (int rc = flag_begin(sc, s, &bad)) return sc.done(rc);
+  queue_csr_checks(s, m, n, nnz, dIA, dJA, bad);
   int hbad = 0, nTop = 0;
-  if (blockRows > 0) MC_HIP(hipMemcpyAsync(&nTop, dIA + blockRows, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (blockRows > 0) CSR_HIP(hipMemcpyAsync(&nTop, dIA + blockRows, sizeof(int), hipMemcpyDeviceToHost, s));
   if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone row pointer ending at nnz=%d", nnz));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "column outside [0,%d)", n));
   // (1) the flags of the top entries and their scan; its total sizes the two parts
-  MC_ALLOC(&scan, sizeof(int) * ((size_t)nTop + 1));
-  MC_ALLOC(&tile, scan_scratch_bytes((long long)nTop + 1));
+  CSR_ALLOC(&scan, sizeof(int) * ((size_t)nTop + 1));
+  CSR_ALLOC(&tile, scan_scratch_bytes((long long)nTop + 1));
   const dim3 topGrid((unsigned)std::max(1, cdiv(nTop, CP_TILE)));
   if (nTop > 0) hipLaunchKernelGGL(k_flags, topGrid, dim3(CP_THREADS), 0, s, nTop, blockCols, dJA, scan);
   scan_inplace(s, scan, nTop, tile);
   int nCorner = 0;
-  MC_HIP(hipMemcpyAsync(&nCorner, scan + nTop, sizeof(int), hipMemcpyDeviceToHost, s));
-  MC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipMemcpyAsync(&nCorner, scan + nTop, sizeof(int), hipMemcpyDeviceToHost, s));
+  CSR_HIP(hipStreamSynchronize(s));
   const int nRest = nnz - nCorner;
-  MC_ALLOC(&IK, sizeof(int) * ((size_t)blockRows + 1));
-  MC_ALLOC(&JK, sizeof(int) * (size_t)std::max(nCorner, 1));
-  MC_ALLOC(&K, sizeof(V) * (size_t)std::max(nCorner, 1));
-  MC_ALLOC(&IR, sizeof(int) * ((size_t)m + 1), true);
-  MC_ALLOC(&JR, sizeof(int) * (size_t)std::max(nRest, 1), true);
-  MC_ALLOC(&R, sizeof(V) * (size_t)std::max(nRest, 1), true);
+  CSR_ALLOC(&IK, sizeof(int) * ((size_t)blockRows + 1));
+  CSR_ALLOC(&JK, sizeof(int) * (size_t)std::max(nCorner, 1));
+  CSR_ALLOC(&K, sizeof(V) * (size_t)std::max(nCorner, 1));
+  CSR_ALLOC(&IR, sizeof(int) * ((size_t)m + 1), true);
+  CSR_ALLOC(&JR, sizeof(int) * (size_t)std::max(nRest, 1), true);
+  CSR_ALLOC(&R, sizeof(V) * (size_t)std::max(nRest, 1), true);
   // (2) the partition of the top entries, the bulk copy of the rest, the two rowPtr arrays
   if (nTop > 0) hipLaunchKernelGGL(k_scatter<V>, topGrid, dim3(CP_THREADS), 0, s, nTop, blockCols, dJA, dA, scan, JK, K, JR, R);
   if (nnz > nTop) {
     const size_t cnt = (size_t)(nnz - nTop), at = (size_t)(nTop - nCorner);
-    MC_HIP(hipMemcpyAsync(JR + at, dJA + nTop, sizeof(int) * cnt, hipMemcpyDeviceToDevice, s));
-    MC_HIP(hipMemcpyAsync(R + at, dA + nTop, sizeof(V) * cnt, hipMemcpyDeviceToDevice, s));
+    CSR_HIP(hipMemcpyAsync(JR + at, dJA + nTop, sizeof(int) * cnt, hipMemcpyDeviceToDevice, s));
+    CSR_HIP(hipMemcpyAsync(R + at, dA + nTop, sizeof(V) * cnt, hipMemcpyDeviceToDevice, s));
   }
   if (m > 0) hipLaunchKernelGGL(k_rowptrs, grid256((long long)m + 1), dim3(256), 0, s, m, blockRows, nCorner, dIA, scan, IK, IR);
-  else MC_HIP(hipMemsetAsync(IR, 0, sizeof(int), s));
-  MC_HIP(hipGetLastError());
+  else CSR_HIP(hipMemsetAsync(IR, 0, sizeof(int), s));
+  CSR_HIP(hipGetLastError());
   // (3) the corner CSR (blockRows x blockCols, local columns) as tiles; on the same stream, it returns after its work
   const int rc = bcsr::to_bcsr<V>(h, blockRows, blockCols, nCorner, IK, JK, K, r, c, dIB, dJB, dB, nnzb);
   if (rc != SPGEMM_OK) {
@@ -230,7 +196,6 @@ template <class V>
 static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, int blockCols, int nnzb, const int* dIB,
                   const int* dJB, const V* dB, int nnzR, const int* dIR, const int* dJR, const V* dR, double drop_tol,
                   int** dIC, int** dJC, V** dC, int* nnzC) {
-  using namespace reorder;
   if (!dIC || !dJC || !dC || !nnzC) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIC = nullptr; *dJC = nullptr; *dC = nullptr; *nnzC = 0;
   if (nnzb < 0 || nnzR < 0) return fail(SPGEMM_ERR_ARG, "negative size");
@@ -239,24 +204,17 @@ static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, i
   if ((blockRows > 0 && !dIB) || (nnzb > 0 && (!dJB || !dB)))
     return fail(SPGEMM_ERR_ARG, "BCSR arrays null with blockRows=%d nnzb=%d", blockRows, nnzb);
   if (blockRows == 0 && nnzb > 0) return fail(SPGEMM_ERR_ARG, "nnzb=%d in a corner without rows", nnzb);
-  if ((m > 0 && !dIR) || (nnzR > 0 && (!dJR || !dR))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnzR);
-  if (m == 0 && nnzR > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnzR);
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  CHK(check_csr_args(m, n, nnzR, dIR, dJR, dR));
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
-  int *bad = nullptr, *IT = nullptr, *JT = nullptr, *IC = nullptr, *JC = nullptr;
+  int *IT = nullptr, *JT = nullptr, *IC = nullptr, *JC = nullptr;
   V *T = nullptr, *C = nullptr;
   unsigned long long* tile = nullptr;
-  MC_ALLOC(&bad, sizeof(int));
-  MC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   // validation, one read-back: the remainder's rowPtr against its count and its columns (the result must be a valid m x n
   // CSR); the block rowPtr and the block columns are validated by bcsr::to_csr
-  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnzR, dIR, (int*)nullptr, (int*)nullptr, bad);
-  if (nnzR > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnzR), dim3(256), 0, s, nnzR, n, dJR, bad);
   int hbad = 0;
-  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (int rc = validate_csr(sc, s, m, n, nnzR, dIR, dJR, &hbad)) return sc.done(rc);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "the remainder's rowPtr is not a monotone row pointer ending at nnz=%d", nnzR));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "a remainder column is outside [0,%d)", n));
   // (1) the corner's rows as a temporary CSR
@@ -265,29 +223,24 @@ static int to_csr(spgemm_handle* h, int m, int n, int r, int c, int blockRows, i
   if (rc != SPGEMM_OK) return sc.done(rc);
   sc.tmp.push_back(IT); sc.tmp.push_back(JT); sc.tmp.push_back(T);
   // (2) row lengths, scan, copy
-  MC_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
-  MC_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
+  CSR_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
+  CSR_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
   if (m > 0) hipLaunchKernelGGL(k_cat_lens, grid256(m), dim3(256), 0, s, m, blockRows, IT, dIR, IC);
-  scan_inplace(s, IC, m, tile);
   unsigned long long total = 0;
-  MC_HIP(hipMemcpyAsync(&total, tile, sizeof(total), hipMemcpyDeviceToHost, s));
-  MC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(scan_total(s, IC, m, tile, &total));
   if (total > (unsigned long long)INT_MAX)
     return sc.done(fail(SPGEMM_ERR_OVERFLOW, "%llu entries do not fit the int32 CSR", total));
   const int nnz = (int)total;
-  MC_ALLOC(&JC, sizeof(int) * (size_t)std::max(nnz, 1), true);
-  MC_ALLOC(&C, sizeof(V) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&JC, sizeof(int) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&C, sizeof(V) * (size_t)std::max(nnz, 1), true);
   if (nnz > 0)
     hipLaunchKernelGGL(k_cat_copy<V>, dim3((unsigned)cdiv(nnz, CP_TILE)), dim3(CP_THREADS), 0, s, m, nnz, blockRows, IT, JT, T,
                        dIR, dJR, dR, IC, JC, C);
-  MC_HIP(hipGetLastError());
-  MC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipStreamSynchronize(s));
   *dIC = IC; *dJC = JC; *dC = C; *nnzC = nnz;
   return sc.done(SPGEMM_OK);
 }
-
-#undef MC_ALLOC
-#undef MC_HIP
 
 }  // namespace mcsr
 

@@ -11,7 +11,7 @@
 //
 // Split.  A CSR is in row order already, so a stable sort of the entries by block id alone gives (block, row, storage
 // order): exactly that layout.  As hip_csr_transpose does with the column, the block id goes on top of a 64-bit key and
-// the stable LSD radix passes of coo_device.hpp run over the bits_of(c - 1) block bits only -- one pass for any c <= 64,
+// the stable LSD radix passes of csr_common_device.hpp run over the bits_of(c - 1) block bits only -- one pass for any c <= 64,
 // none for c == 1.  key = ((block << rowBits) | row) << colBits | local column.  The local column rides in the low bits
 // because the payload of a float entry is its value's bits (nothing then leads back to the source entry; a double entry
 // carries its source index instead, and its value is gathered by the emit kernel): bits_of(c - 1) + bits_of(stride - 1)
@@ -26,15 +26,14 @@
 // like any other constant.
 //
 // Every value that becomes an address (rowPtr of A / of every block, the column that selects a block) is checked first by
-// reorder::k_check_rowptr / k_check_cols; the host reads the flag before anything is queued that indexes with them.
-// Included at the end of spgemm_hip.hip behind compare_device.hpp (uses reorder's checks, row search, scan, radix, Scratch).
+// k_check_rowptr / k_check_cols; the host reads the flag before anything is queued that indexes with them.
+// Uses csr_common_device.hpp (the checks and their one read-back, row search, lower bound, scan, radix sort, tile copy,
+// Scratch).
 #pragma once
 
 namespace pcsr {
 
-using reorder::CP_THREADS;
-using reorder::CP_ITEMS;
-using reorder::CP_TILE;
+using namespace csrdev;
 
 template <class V>
 struct Blocks {
@@ -54,12 +53,12 @@ __global__ __launch_bounds__(CP_THREADS) void k_split_keys(int m, int nnz, int s
                                                            int* __restrict__ payload) {
   __shared__ int rows[2];
   const long long base = (long long)blockIdx.x * CP_TILE;
-  reorder::tile_rows(IA, m, nnz, base, rows);
+  tile_rows(IA, m, nnz, base, rows);
 #pragma unroll
   for (int k = 0; k < CP_ITEMS; ++k) {
     const long long o = base + k * CP_THREADS + threadIdx.x;
     if (o >= nnz) break;
-    const int r = reorder::row_of_entry(IA, rows[0], rows[1], (int)o);
+    const int r = row_of_entry(IA, rows[0], rows[1], (int)o);
     const int col = JA[o], b = col / stride;
     keys[o] = (((((unsigned long long)(unsigned)b) << rowBits) | (unsigned)r) << colBits) | (unsigned)(col - b * stride);
     if constexpr (sizeof(V) == 4) payload[o] = __float_as_int(A[o]); else payload[o] = (int)o;
@@ -76,21 +75,11 @@ __global__ void k_split_emit(int nnz, int colBits, const unsigned long long* __r
   if constexpr (sizeof(V) == 4) P[i] = __int_as_float(payload[i]); else P[i] = A[payload[i]];
 }
 
-// first sorted key in [lo, hi) that is not below want
-__device__ __forceinline__ int first_key_at_least(const unsigned long long* __restrict__ keys, int lo, int hi,
-                                                  unsigned long long want) {
-  while (lo < hi) {
-    const int mid = (int)(((long long)lo + hi) >> 1);
-    if (keys[mid] < want) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 // blockPtr[b] = first sorted key of block b or later, b = 0..c
 __global__ void k_block_starts(int c, int nnz, int shift, const unsigned long long* __restrict__ keys,
                                int* __restrict__ blockPtr) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b <= c) blockPtr[b] = first_key_at_least(keys, 0, nnz, (unsigned long long)(unsigned)b << shift);
+  if (b <= c) blockPtr[b] = first_at_least(keys, 0, nnz, (unsigned long long)(unsigned)b << shift);
 }
 
 // IP[b * (m + 1) + r] = entries of block b in rows below r, r = 0..m: one search per entry, inside the block
@@ -101,7 +90,7 @@ __global__ void k_split_rowptr(int m, int c, int rowBits, int colBits, const uns
   const int b = (int)(i / (m + 1)), r = (int)(i - (long long)b * (m + 1));
   const int s = blockPtr[b];
   const unsigned long long want = (((unsigned long long)(unsigned)b << rowBits) + (unsigned)r) << colBits;   // r == m: the next block
-  IP[i] = first_key_at_least(keys, s, blockPtr[b + 1], want) - s;
+  IP[i] = first_at_least(keys, s, blockPtr[b + 1], want) - s;
 }
 
 template <class V>
@@ -113,9 +102,9 @@ __global__ void k_join_lens(int m, int c, Blocks<V> blk, int* __restrict__ IC) {
   IC[r] = len;
 }
 
-// One tile of C's entries per block.  Read side, lane-strided: the row by a search in IC bounded by the tile's rows, the
-// block by walking the row's block lengths, the source position from that block's rowPtr; column made global; staged in
-// LDS.  Write side as k_permute_copy: every lane stores 4 consecutive entries with 16-byte stores.
+// One tile of C's entries per block, as tile_copy: the row by a search in IC bounded by the tile's rows, the block by
+// walking the row's block lengths, the source position from that block's rowPtr; column made global; staged in LDS for
+// tile_store.  The gather loop is written out here: as a tile_copy functor the block walk compiled to a longer loop.
 template <class V>
 __global__ __launch_bounds__(CP_THREADS) void k_join_copy(int m, int nnz, int c, int stride, Blocks<V> blk,
                                                           const int* __restrict__ IC, int* __restrict__ JC,
@@ -124,13 +113,13 @@ __global__ __launch_bounds__(CP_THREADS) void k_join_copy(int m, int nnz, int c,
   __shared__ __attribute__((aligned(16))) int sc[CP_TILE];
   __shared__ __attribute__((aligned(16))) V sv[CP_TILE];
   const long long base = (long long)blockIdx.x * CP_TILE;
-  reorder::tile_rows(IC, m, nnz, base, rows);
+  tile_rows(IC, m, nnz, base, rows);
 #pragma unroll
   for (int k = 0; k < CP_ITEMS; ++k) {
     const int t = k * CP_THREADS + threadIdx.x;
     const long long o = base + t;
     if (o < nnz) {
-      const int r = reorder::row_of_entry(IC, rows[0], rows[1], (int)o);
+      const int r = row_of_entry(IC, rows[0], rows[1], (int)o);
       int off = (int)o - IC[r], b = 0, s = blk.I[0][r], len = blk.I[0][r + 1] - s;
       while (off >= len && b + 1 < c) {             // the lengths add up to the row's: ends at the latest in the last block
         off -= len;
@@ -142,21 +131,8 @@ __global__ __launch_bounds__(CP_THREADS) void k_join_copy(int m, int nnz, int c,
       sv[t] = blk.A[b][s + off];
     }
   }
-  __syncthreads();
-  const int t0 = threadIdx.x * CP_ITEMS;
-  const long long o0 = base + t0;
-  if (o0 >= nnz) return;
-  if (o0 + CP_ITEMS <= nnz) {
-    *reinterpret_cast<int4*>(JC + o0) = *reinterpret_cast<const int4*>(sc + t0);
-    const V v[CP_ITEMS] = {sv[t0], sv[t0 + 1], sv[t0 + 2], sv[t0 + 3]};
-    reorder::store4<V>(C + o0, v);
-  } else {
-    for (int k = 0; o0 + k < nnz; ++k) { JC[o0 + k] = sc[t0 + k]; C[o0 + k] = sv[t0 + k]; }
-  }
+  tile_store<V>(base, nnz, sc, sv, JC, C);
 }
-
-#define PC_ALLOC(...) if (!sc.get(__VA_ARGS__)) return sc.done(fail(SPGEMM_ERR_HIP, "device allocation failed"))
-#define PC_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return sc.done(fail(SPGEMM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_))); } while (0)
 
 static int check_block_count(int c) {
   if (c < 1 || c > SPGEMM_PCSR_MAX_BLOCKS) return fail(SPGEMM_ERR_ARG, "c=%d outside [1,%d]", c, SPGEMM_PCSR_MAX_BLOCKS);
@@ -166,53 +142,44 @@ static int check_block_count(int c) {
 template <class V>
 static int split_columns(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const V* dA, int c,
                          int** dIP, int** dJP, V** dP, int* blockPtr) {
-  using namespace reorder;
   if (!dIP || !dJP || !dP || !blockPtr) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIP = nullptr; *dJP = nullptr; *dP = nullptr;
   CHK(check_block_count(c));
-  if (m < 0 || n < 0 || nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
-  if ((m > 0 && !dIA) || (nnz > 0 && (!dJA || !dA))) return fail(SPGEMM_ERR_ARG, "CSR arrays null with m=%d nnz=%d", m, nnz);
-  if (m == 0 && nnz > 0) return fail(SPGEMM_ERR_ARG, "nnz=%d in a matrix without rows", nnz);
+  CHK(check_csr_args(m, n, nnz, dIA, dJA, dA));
   const long long ipLen = (long long)c * ((long long)m + 1);
   if (ipLen > INT_MAX) return fail(SPGEMM_ERR_OVERFLOW, "c * (m + 1) = %lld row pointer entries do not fit int32", ipLen);
   for (int b = 0; b <= c; ++b) blockPtr[b] = 0;
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
-  int *bad = nullptr, *IP = nullptr, *JP = nullptr, *idxA = nullptr, *idxB = nullptr, *bhist = nullptr, *dBlockPtr = nullptr;
+  int *IP = nullptr, *JP = nullptr, *idxA = nullptr, *idxB = nullptr, *bhist = nullptr, *dBlockPtr = nullptr;
   V* P = nullptr;
   unsigned long long *keyA = nullptr, *keyB = nullptr, *tile = nullptr;
-  PC_ALLOC(&bad, sizeof(int));
-  PC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
   // validation, one read-back: rowPtr (the key kernel searches it) and the column range (the block id becomes an address)
-  if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnz, dIA, (int*)nullptr, (int*)nullptr, bad);
-  if (nnz > 0) hipLaunchKernelGGL(k_check_cols, grid256(nnz), dim3(256), 0, s, nnz, n, dJA, bad);
   int hbad = 0;
-  if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
+  if (int rc = validate_csr(sc, s, m, n, nnz, dIA, dJA, &hbad)) return sc.done(rc);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "rowPtr is not a monotone row pointer ending at nnz=%d", nnz));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "column outside [0,%d)", n));
-  PC_ALLOC(&IP, sizeof(int) * (size_t)ipLen, true);
-  PC_ALLOC(&JP, sizeof(int) * (size_t)std::max(nnz, 1), true);
-  PC_ALLOC(&P, sizeof(V) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&IP, sizeof(int) * (size_t)ipLen, true);
+  CSR_ALLOC(&JP, sizeof(int) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&P, sizeof(V) * (size_t)std::max(nnz, 1), true);
   if (nnz == 0) {
-    PC_HIP(hipMemsetAsync(IP, 0, sizeof(int) * (size_t)ipLen, s));
-    PC_HIP(hipStreamSynchronize(s));
+    CSR_HIP(hipMemsetAsync(IP, 0, sizeof(int) * (size_t)ipLen, s));
+    CSR_HIP(hipStreamSynchronize(s));
     *dIP = IP; *dJP = JP; *dP = P;
     return sc.done(SPGEMM_OK);
   }
   const int stride = stride_of(n, c);
   const int rowBits = std::max(1, bits_of(m - 1)), colBits = std::max(1, bits_of(stride - 1)), blockBits = bits_of(c - 1);
-  const int nblk = cdiv(nnz, coo::RS_TILE);
-  PC_ALLOC(&keyA, sizeof(unsigned long long) * (size_t)nnz);
-  PC_ALLOC(&idxA, sizeof(int) * (size_t)nnz);
-  PC_ALLOC(&dBlockPtr, sizeof(int) * ((size_t)c + 1));
+  const int nblk = cdiv(nnz, RS_TILE);
+  CSR_ALLOC(&keyA, sizeof(unsigned long long) * (size_t)nnz);
+  CSR_ALLOC(&idxA, sizeof(int) * (size_t)nnz);
+  CSR_ALLOC(&dBlockPtr, sizeof(int) * ((size_t)c + 1));
   if (blockBits > 0) {
-    PC_ALLOC(&keyB, sizeof(unsigned long long) * (size_t)nnz);
-    PC_ALLOC(&idxB, sizeof(int) * (size_t)nnz);
-    PC_ALLOC(&bhist, sizeof(int) * ((size_t)nblk * coo::RS_RADIX + 1));
-    PC_ALLOC(&tile, scan_scratch_bytes((long long)nblk * coo::RS_RADIX + 1));
+    CSR_ALLOC(&keyB, sizeof(unsigned long long) * (size_t)nnz);
+    CSR_ALLOC(&idxB, sizeof(int) * (size_t)nnz);
+    CSR_ALLOC(&bhist, sizeof(int) * ((size_t)nblk * RS_RADIX + 1));
+    CSR_ALLOC(&tile, scan_scratch_bytes((long long)nblk * RS_RADIX + 1));
   }
   hipLaunchKernelGGL(k_split_keys<V>, dim3((unsigned)cdiv(nnz, CP_TILE)), dim3(CP_THREADS), 0, s, m, nnz, stride, rowBits,
                      colBits, dIA, dJA, dA, keyA, idxA);
@@ -220,9 +187,9 @@ static int split_columns(spgemm_handle* h, int m, int n, int nnz, const int* dIA
   hipLaunchKernelGGL(k_split_emit<V>, grid256(nnz), dim3(256), 0, s, nnz, colBits, keyA, idxA, dA, JP, P);
   hipLaunchKernelGGL(k_block_starts, dim3(1), dim3(128), 0, s, c, nnz, rowBits + colBits, keyA, dBlockPtr);
   hipLaunchKernelGGL(k_split_rowptr, grid256(ipLen), dim3(256), 0, s, m, c, rowBits, colBits, keyA, dBlockPtr, IP);
-  PC_HIP(hipGetLastError());
-  PC_HIP(hipMemcpyAsync(blockPtr, dBlockPtr, sizeof(int) * ((size_t)c + 1), hipMemcpyDeviceToHost, s));
-  PC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipMemcpyAsync(blockPtr, dBlockPtr, sizeof(int) * ((size_t)c + 1), hipMemcpyDeviceToHost, s));
+  CSR_HIP(hipStreamSynchronize(s));
   *dIP = IP; *dJP = JP; *dP = P;
   return sc.done(SPGEMM_OK);
 }
@@ -246,7 +213,6 @@ static int check_blocks(int rows, int c, const int* const* dIB, const int* const
 template <class V>
 static int join(spgemm_handle* h, int m, int n, int c, const int* const* dIB, const int* const* dJB, const V* const* dB,
                 const int* nnzB, int** dIC, int** dJC, V** dC, int* nnzC) {
-  using namespace reorder;
   if (!dIC || !dJC || !dC || !nnzC) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIC = nullptr; *dJC = nullptr; *dC = nullptr; *nnzC = 0;
   CHK(check_block_count(c));
@@ -255,10 +221,8 @@ static int join(spgemm_handle* h, int m, int n, int c, const int* const* dIB, co
   CHK(check_blocks<V>(m, c, dIB, dJB, dB, nnzB, &total));
   if (total > INT_MAX) return fail(SPGEMM_ERR_OVERFLOW, "%lld entries do not fit the int32 CSR", total);
   const int nnz = (int)total, stride = stride_of(n, c);
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  clear_stale_hip_error();
-  hipStream_t s = h->stream;
+  hipStream_t s;
+  CHK(enter(h, &s));
   Scratch sc;
   int *bad = nullptr, *IC = nullptr, *JC = nullptr;
   V* C = nullptr;
@@ -267,29 +231,26 @@ static int join(spgemm_handle* h, int m, int n, int c, const int* const* dIB, co
   for (int b = 0; b < c; ++b) { blk.I[b] = dIB[b]; blk.J[b] = dJB[b]; blk.A[b] = dB[b]; }
   // validation, one read-back: every block's rowPtr against its count (they become addresses), every local column inside
   // [0, stride) and its global column below n (the result must be a valid m x n CSR)
-  PC_ALLOC(&bad, sizeof(int));
-  PC_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+  if (int rc = flag_begin(sc, s, &bad)) return sc.done(rc);
   for (int b = 0; b < c; ++b) {
-    if (m > 0) hipLaunchKernelGGL(k_check_rowptr, grid256(m), dim3(256), 0, s, m, nnzB[b], dIB[b], (int*)nullptr, (int*)nullptr, bad);
     const long long room = std::min<long long>(stride, (long long)n - (long long)b * stride);
-    if (nnzB[b] > 0)
-      hipLaunchKernelGGL(k_check_cols, grid256(nnzB[b]), dim3(256), 0, s, nnzB[b], (int)std::max<long long>(room, 0), dJB[b], bad);
+    queue_csr_checks(s, m, (int)std::max<long long>(room, 0), nnzB[b], dIB[b], dJB[b], bad);
   }
   int hbad = 0;
   if (read_flag(s, bad, &hbad)) return sc.done(SPGEMM_ERR_HIP);
   if (hbad & BAD_ROWPTR) return sc.done(fail(SPGEMM_ERR_INPUT, "a block's rowPtr is not a monotone row pointer ending at its nnz"));
   if (hbad & BAD_COLUMN) return sc.done(fail(SPGEMM_ERR_INPUT, "a block's column is outside [0,%d) or its global column outside [0,%d)", stride, n));
-  PC_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
-  PC_ALLOC(&JC, sizeof(int) * (size_t)std::max(nnz, 1), true);
-  PC_ALLOC(&C, sizeof(V) * (size_t)std::max(nnz, 1), true);
-  PC_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
+  CSR_ALLOC(&IC, sizeof(int) * ((size_t)m + 1), true);
+  CSR_ALLOC(&JC, sizeof(int) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&C, sizeof(V) * (size_t)std::max(nnz, 1), true);
+  CSR_ALLOC(&tile, scan_scratch_bytes((long long)m + 1));
   if (m > 0) hipLaunchKernelGGL(k_join_lens<V>, grid256(m), dim3(256), 0, s, m, c, blk, IC);
   scan_inplace(s, IC, m, tile);
   if (nnz > 0)
     hipLaunchKernelGGL(k_join_copy<V>, dim3((unsigned)cdiv(nnz, CP_TILE)), dim3(CP_THREADS), 0, s, m, nnz, c, stride, blk, IC,
                        JC, C);
-  PC_HIP(hipGetLastError());
-  PC_HIP(hipStreamSynchronize(s));
+  CSR_HIP(hipGetLastError());
+  CSR_HIP(hipStreamSynchronize(s));
   *dIC = IC; *dJC = JC; *dC = C; *nnzC = nnz;
   return sc.done(SPGEMM_OK);
 }
@@ -330,9 +291,6 @@ static int spmm(spgemm_handle* h, const int* dIA, const int* dJA, const V* dA, i
   }
   return SPGEMM_OK;
 }
-
-#undef PC_ALLOC
-#undef PC_HIP
 
 }  // namespace pcsr
 

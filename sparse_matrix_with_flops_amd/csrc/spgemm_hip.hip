@@ -2090,6 +2090,11 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 
 
 // ------------------------------------------------------------------------------------------------
+// what the six device CSR format headers below share: prologue, Scratch, validation, scan, radix sort, tile copy
+// ------------------------------------------------------------------------------------------------
+#include "csr_common_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // COO -> CSR on the device (the step in front of the path)
 // ------------------------------------------------------------------------------------------------
 #include "coo_device.hpp"
@@ -2118,6 +2123,9 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // mixed CSR (MCSR): a tiled top-left corner plus a CSR remainder, and back
 // ------------------------------------------------------------------------------------------------
 #include "mcsr_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the six headers above
+#undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------
 // multi-GPU: groups of shards, sharded SpGEMM, sharded R-MCL

@@ -38,7 +38,8 @@ def test_shipped_library_matches_sources():
     for ln in lines[start + 1:]:
         h, name = ln.split()
         seen[name] = h
-    assert set(seen) >= {"spgemm_hip.hip", "spgemm_device.hpp", "coo_device.hpp", "../../include/spgemm_hip.h"}, seen
+    assert set(seen) >= {"spgemm_hip.hip", "spgemm_device.hpp", "coo_device.hpp", "csr_common_device.hpp",
+                         "../../include/spgemm_hip.h"}, seen
     for name, h in seen.items():
         assert _sha(os.path.normpath(os.path.join(CSRC, name))) == h, f"{name} changed after libspgemm_hip.so was built"
     assert os.path.getmtime(SO) >= max(os.path.getmtime(os.path.normpath(os.path.join(CSRC, n))) for n in seen), \

@@ -87,6 +87,30 @@ def test_out_of_range_entry_is_an_error():
         hs.coo_to_csr(3, 3, np.array([0, 5], np.int32), np.array([1, 1], np.int32), np.ones(2, np.float32), hs.COO_DEDUPE)
 
 
+def test_radix_block_edges_and_a_failed_call_between():
+    """nnz on the edges of a radix block (RS_TILE keys) at rows = cols = 200: 8 + 8 key bits = two passes, so the sorted keys
+    land back in the first buffer pair.  Then a call that fails its validation, and the first case again on the same
+    handle: the failure path has left the pool and the handle usable."""
+    RS_TILE = 2048                                  # keys per block of the radix kernels (csr_common_device.hpp)
+    h = hs.Handle(0)
+    try:
+        cases = []
+        for nnz in (RS_TILE - 1, RS_TILE, RS_TILE + 1):
+            ri, ci, v = random_coo(200, 200, nnz, 100 + nnz)
+            for dedupe in (True, False):
+                cases.append((ri, ci, v, hs.COO_DEDUPE if dedupe else 0, po.coo_to_csr(200, 200, ri, ci, v, dedupe=dedupe)))
+        for ri, ci, v, flags, want in cases:
+            bits_equal(hs.coo_to_csr(200, 200, ri, ci, v, flags, handle=h), want)
+        ri, ci, v, flags, want = cases[0]
+        bad = ri.copy()
+        bad[RS_TILE // 2] = 200                     # one row index past the end
+        with pytest.raises(hs.SpgemmError):
+            hs.coo_to_csr(200, 200, bad, ci, v, flags, handle=h)
+        bits_equal(hs.coo_to_csr(200, 200, ri, ci, v, flags, handle=h), want)
+    finally:
+        h.close()
+
+
 @pytest.mark.parametrize("m,seed", [(3000, 21), (262144, 42)])
 def test_flops_stats_match_oracle(m, seed):
     """hip_flopsStats == the oracle's restatement of flopsStats (nlibs/tools/stats.cc:45-55)."""

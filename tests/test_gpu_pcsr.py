@@ -20,8 +20,8 @@ from sparse_matrix_with_flops_amd import hipspgemm as hs
 pytestmark = pytest.mark.gpu
 DTYPES = [np.float32, np.float64]
 ERR_INPUT = 5
-CP_TILE = 1024          # entries per block of the split key / join copy kernels (reorder_device.hpp, pcsr_device.hpp)
-RS_TILE = 2048          # keys per block of the radix kernels (coo_device.hpp)
+CP_TILE = 1024          # entries per block of the split key / join copy kernels (csr_common_device.hpp, pcsr_device.hpp)
+RS_TILE = 2048          # keys per block of the radix kernels (csr_common_device.hpp)
 BLOCK_COUNTS = [1, 2, 3, 7, 64]
 
 

@@ -19,8 +19,8 @@ from sparse_matrix_with_flops_amd import hipspgemm as hs
 pytestmark = pytest.mark.gpu
 DTYPES = [np.float32, np.float64]
 ERR_INPUT = 5
-CP_TILE = 1024          # entries per block of the permute copy / transpose key kernels (reorder_device.hpp)
-RS_TILE = 2048          # keys per block of the radix kernels (coo_device.hpp)
+CP_TILE = 1024          # entries per block of the permute copy / transpose key kernels (csr_common_device.hpp)
+RS_TILE = 2048          # keys per block of the radix kernels (csr_common_device.hpp)
 
 
 @pytest.fixture(scope="module", autouse=True)
