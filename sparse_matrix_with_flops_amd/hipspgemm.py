@@ -25,6 +25,7 @@ carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / 
 There is no CPU fallback: if the library or a HIP device is missing, calls raise SpgemmError.
 PyTorch is not needed here; bench.py / dist.py use it only for device memory and torch.distributed.
 """
+import contextlib
 import ctypes as C
 import weakref
 import os
@@ -256,6 +257,43 @@ def device_count():
     return n.value if rc == 0 else 0
 
 
+# ---------------------------------------------------------------------------------------------
+# the binding kit: what every wrapper of a device entry point does, once
+# ---------------------------------------------------------------------------------------------
+def _typed(name, dtype):
+    """-> (entry point, its name): `name` for float32 values, `name` + "_f64" for float64"""
+    name = name + "_f64" if _value_dtype(dtype) == np.float64 else name
+    return getattr(lib(), name), name
+
+
+def _call(name, dtype, *args):
+    fn, name = _typed(name, dtype)
+    _check(fn(*args), name)
+
+
+def _hp(handle):
+    """the spgemm_handle argument; no Handle = the library's default handle"""
+    return handle.ptr if handle else None
+
+
+def _ptrs(*device_pointers):
+    return [C.c_void_p(p) for p in device_pointers]
+
+
+class _CsrOut:
+    """the outputs of an entry point that makes a CSR: three device pointers and (count=True) an int.  refs() are the
+    arguments, values() what the call left in them: (rowPtr, colInd, values[, count])."""
+
+    def __init__(self, count=True):
+        self._slots = [C.c_void_p(), C.c_void_p(), C.c_void_p()] + ([C.c_int(0)] if count else [])
+
+    def refs(self):
+        return [C.byref(s) for s in self._slots]
+
+    def values(self):
+        return tuple(s.value for s in self._slots)
+
+
 # Objects that own something on the C side, closed in dependency order when the interpreter exits (jobs before the groups
 # they were made on, groups before plain handles): left to the garbage collector at shutdown they are finalised in any
 # order, after the HIP runtime has started to go away -- seen as a segmentation fault at exit after a failed test.
@@ -407,22 +445,17 @@ class CSR:
         assert not self.on_device and not B.on_device
         if self.cols != B.rows:
             raise SpgemmError(f"shape mismatch: A is {self.rows}x{self.cols}, B is {B.rows}x{B.cols}")
-        f64 = _common_dtype(self, B) == np.float64
+        dt = _common_dtype(self, B)
         L = lib()
-        P = _D if f64 else _F
+        P = _D if dt == np.float64 else _F
         ic, jc, cv, nnz = _I(), _I(), P(), C.c_int(0)
-        fn, name = (L.hip_CSR_SpMM_f64, "hip_CSR_SpMM_f64") if f64 else (L.hip_CSR_SpMM, "hip_CSR_SpMM")
+        fn, name = _typed("hip_CSR_SpMM", dt)
         rc = fn(self.rowPtr.ctypes.data_as(_I), self.colInd.ctypes.data_as(_I), self.values.ctypes.data_as(P),
                 self.nnz, B.rowPtr.ctypes.data_as(_I), B.colInd.ctypes.data_as(_I), B.values.ctypes.data_as(P),
                 B.nnz, C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz), self.rows, self.cols, B.cols)
         _check(rc, name)
-        n = nnz.value
-        rp = np.ctypeslib.as_array(ic, shape=(self.rows + 1,)).copy()
-        ci = np.ctypeslib.as_array(jc, shape=(n,)).copy() if n else np.zeros(0, np.int32)
-        v = np.ctypeslib.as_array(cv, shape=(n,)).copy() if n else np.zeros(0, self.dtype)
-        for p in (ic, jc, cv):                      # CSR::dispose() == free() (nlibs/CSR.h:323-327)
-            L.free(C.cast(p, C.c_void_p))
-        return CSR(v, ci, rp, self.rows, B.cols, n, dtype=self.dtype)
+        rp, ci, v = _take_malloced(L, ic, jc, cv, self.rows, nnz.value, self.dtype)
+        return CSR(v, ci, rp, self.rows, B.cols, nnz.value, dtype=self.dtype)
 
     # -- reordering (nlibs/CSR.cc:431-494) through the device entry points; host CSR in -> host CSR out (uploaded and
     #    downloaded around the call), device CSR in -> device CSR out, like the rest of the mirror --------------------
@@ -441,13 +474,12 @@ class CSR:
             out.deviceDispose()
 
     def _permuted(self, rowP, colP, handle):
-        f64 = _value_dtype(self.dtype) == np.float64
+        dt = _value_dtype(self.dtype)
 
         def run(d):
             ups = [h2d(x) if x is not None else None for x in (rowP, colP)]
             try:
-                raw = csr_permute_raw_f64 if f64 else csr_permute_raw
-                ib, jb, vb = raw(handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values, ups[0], ups[1])
+                ib, jb, vb = _csr_permute(dt, handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values, ups[0], ups[1])
             finally:
                 for p in ups:
                     dev_free(p)
@@ -476,11 +508,10 @@ class CSR:
 
     def transpose(self, handle=None):
         """self^T on the device (hip_csr_transpose): stable, so the result is column-sorted when no row repeats a column."""
-        f64 = _value_dtype(self.dtype) == np.float64
+        dt = _value_dtype(self.dtype)
 
         def run(d):
-            raw = csr_transpose_raw_f64 if f64 else csr_transpose_raw
-            it, jt, vt = raw(handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values)
+            it, jt, vt = _csr_transpose(dt, handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values)
             return CSR(vt, jt, it, d.cols, d.rows, d.nnz, True, dtype=d.dtype)
         return self._on_device(run)
 
@@ -524,9 +555,9 @@ class CSR:
 
     def diff(self, B, rel=1e-6, abs=0.0, handle=None):
         """hip_csr_diff of self against B (B is the reference side) -> CsrDiff"""
-        raw = csr_diff_raw_f64 if _value_dtype(self.dtype) == np.float64 else csr_diff_raw
-        return self._with_device_pair(B, lambda a, b: raw(handle, a.rows, a.cols, a.rowPtr, a.colInd, a.values, a.nnz,
-                                                          b.rowPtr, b.colInd, b.values, b.nnz, rel, abs))
+        dt = _value_dtype(self.dtype)
+        return self._with_device_pair(B, lambda a, b: _csr_diff(dt, handle, a.rows, a.cols, a.rowPtr, a.colInd, a.values,
+                                                                a.nnz, b.rowPtr, b.colInd, b.values, b.nnz, rel, abs))
 
     def differs(self, B, handle=None):
         """CSR::differs (nlibs/CSR.cc:210-240): the squared Frobenius norm of self - B, accumulated in double"""
@@ -618,7 +649,7 @@ def host_api_timed(A, B, reps=3):
 
 
 def _dev_args(M):
-    return [C.c_void_p(M.rowPtr), C.c_void_p(M.colInd), C.c_void_p(M.values), M.nnz]
+    return _ptrs(M.rowPtr, M.colInd, M.values) + [M.nnz]
 
 
 def gpuSpMMWrapper(dA, dB, handle=None):
@@ -626,56 +657,50 @@ def gpuSpMMWrapper(dA, dB, handle=None):
     assert dA.on_device and dB.on_device
     if dA.cols != dB.rows:
         raise SpgemmError("shape mismatch")
-    f64 = _common_dtype(dA, dB) == np.float64
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    fn, name = (lib().hip_gpuSpMM_f64, "hip_gpuSpMM_f64") if f64 else (lib().hip_gpuSpMM, "hip_gpuSpMM")
-    rc = fn(handle.ptr if handle else None, *_dev_args(dA), *_dev_args(dB), dA.rows, dA.cols, dB.cols,
-            C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
-    _check(rc, name)
-    return CSR(cv.value, jc.value, ic.value, dA.rows, dB.cols, nnz.value, True, dtype=dA.dtype)
+    ic, jc, cv, nnz = _gpu_spmm(_common_dtype(dA, dB), handle, dA.rowPtr, dA.colInd, dA.values, dA.nnz, dB.rowPtr, dB.colInd,
+                                dB.values, dB.nnz, dA.rows, dA.cols, dB.cols)
+    return CSR(cv, jc, ic, dA.rows, dB.cols, nnz, True, dtype=dA.dtype)
+
+
+def _gpu_spmm(dtype, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
+    out = _CsrOut()
+    _call("hip_gpuSpMM", dtype, _hp(handle), *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB), int(m), int(k),
+          int(n), *out.refs())
+    return out.values()
 
 
 def gpu_spmm_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
     """Raw-pointer form for callers that own device memory elsewhere (e.g. torch tensors' data_ptr())."""
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    rc = lib().hip_gpuSpMM(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
-                           C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
-                           C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
-    _check(rc, "hip_gpuSpMM")
-    return ic.value, jc.value, cv.value, nnz.value
+    return _gpu_spmm(np.float32, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n)
 
 
 def gpu_spmm_raw_f64(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
     """gpu_spmm_raw with float64 values (hip_gpuSpMM_f64)."""
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    rc = lib().hip_gpuSpMM_f64(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
-                               C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
-                               C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz))
-    _check(rc, "hip_gpuSpMM_f64")
-    return ic.value, jc.value, cv.value, nnz.value
+    return _gpu_spmm(np.float64, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n)
 
 
 def spgemm_symbolic_raw(handle, IA, JA, nnzA, IB, JB, nnzB, m, k, n, IC_out):
     """Phase 1 on raw device pointers: fills IC_out[m+1] (C.rowPtr), returns nnzC."""
     nnz = C.c_int(0)
-    _check(lib().hip_spgemm_symbolic(handle.ptr, C.c_void_p(IA), C.c_void_p(JA), int(nnzA), C.c_void_p(IB),
-                                     C.c_void_p(JB), int(nnzB), int(m), int(k), int(n), C.c_void_p(IC_out),
-                                     C.byref(nnz)), "hip_spgemm_symbolic")
+    # the two phases need the handle that carries the plan between them: handle.ptr, not _hp (None is an AttributeError)
+    _check(lib().hip_spgemm_symbolic(handle.ptr, *_ptrs(IA, JA), int(nnzA), *_ptrs(IB, JB), int(nnzB), int(m), int(k), int(n),
+                                     C.c_void_p(IC_out), C.byref(nnz)), "hip_spgemm_symbolic")
     return nnz.value
+
+
+def _spgemm_numeric(dtype, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out):
+    _call("hip_spgemm_numeric", dtype, handle.ptr, *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB), int(m), int(k),
+          int(n), *_ptrs(IC, JC_out, C_out))
 
 
 def spgemm_numeric_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out):
     """Phase 2 on raw device pointers: writes JC_out/C_out (caller-owned, nnzC entries each)."""
-    _check(lib().hip_spgemm_numeric(handle.ptr, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
-                                    C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
-                                    C.c_void_p(IC), C.c_void_p(JC_out), C.c_void_p(C_out)), "hip_spgemm_numeric")
+    _spgemm_numeric(np.float32, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out)
 
 
 def spgemm_numeric_raw_f64(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out):
     """Phase 2 with float64 values (hip_spgemm_numeric_f64) after spgemm_symbolic_raw on the same handle."""
-    _check(lib().hip_spgemm_numeric_f64(handle.ptr, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
-                                        C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), int(m), int(k), int(n),
-                                        C.c_void_p(IC), C.c_void_p(JC_out), C.c_void_p(C_out)), "hip_spgemm_numeric_f64")
+    _spgemm_numeric(np.float64, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n, IC, JC_out, C_out)
 
 
 def d2d(dst, src, nbytes):
@@ -692,26 +717,21 @@ def rmcl_prune_raw(handle, m, IC, JC, CV, nnz=None):
     """hip_rmcl_prune on raw device pointers: inflate/prune/normalise the rows of C, compacted into new pool arrays.
     nnz (optional): nnz(C) when the caller knows it (hip_rmcl_prune_n: no device read for it).
     Returns (IN, JN, CN, nnzN); release the three with dev_free."""
-    i_, j_, c_, n_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    hp = handle.ptr if handle else None
+    out = _CsrOut()
     if nnz is None:
-        _check(lib().hip_rmcl_prune(hp, int(m), C.c_void_p(IC), C.c_void_p(JC), C.c_void_p(CV),
-                                    C.byref(i_), C.byref(j_), C.byref(c_), C.byref(n_)), "hip_rmcl_prune")
+        _check(lib().hip_rmcl_prune(_hp(handle), int(m), *_ptrs(IC, JC, CV), *out.refs()), "hip_rmcl_prune")
     else:
-        _check(lib().hip_rmcl_prune_n(hp, int(m), int(nnz), C.c_void_p(IC), C.c_void_p(JC), C.c_void_p(CV),
-                                      C.byref(i_), C.byref(j_), C.byref(c_), C.byref(n_)), "hip_rmcl_prune_n")
-    return i_.value, j_.value, c_.value, n_.value
+        _check(lib().hip_rmcl_prune_n(_hp(handle), int(m), int(nnz), *_ptrs(IC, JC, CV), *out.refs()), "hip_rmcl_prune_n")
+    return out.values()
 
 
 def rmcl_expand_prune_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
     """hip_rmcl_expand_prune on raw device pointers: prune(A*B) of one R-MCL iteration without materialising the product.
     Returns (IN, JN, CN, nnzN) in pool arrays; release the three with dev_free."""
-    i_, j_, c_, n_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(lib().hip_rmcl_expand_prune(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA),
-                                       int(nnzA), C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB),
-                                       int(m), int(k), int(n), C.byref(i_), C.byref(j_), C.byref(c_), C.byref(n_)),
-           "hip_rmcl_expand_prune")
-    return i_.value, j_.value, c_.value, n_.value
+    out = _CsrOut()
+    _check(lib().hip_rmcl_expand_prune(_hp(handle), *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB),
+                                       int(m), int(k), int(n), *out.refs()), "hip_rmcl_expand_prune")
+    return out.values()
 
 
 def pool_trim(device=0):
@@ -732,15 +752,14 @@ def flopsStats(dA, dB, handle=None):
     """std::vector<int> flopsStats(...) (nlibs/tools/stats.cc:45-55) for device CSRs: 13 power-of-two buckets."""
     assert dA.on_device and dB.on_device
     out = (C.c_int * 13)()
-    _check(lib().hip_flopsStats(handle.ptr if handle else None, C.c_void_p(dA.rowPtr), C.c_void_p(dA.colInd),
-                                C.c_void_p(dB.rowPtr), dA.rows, out), "hip_flopsStats")
+    _check(lib().hip_flopsStats(_hp(handle), *_ptrs(dA.rowPtr, dA.colInd, dB.rowPtr), dA.rows, out), "hip_flopsStats")
     return [int(x) for x in out]
 
 
 def nnzStats(dA, handle=None):
     """CSR::nnzStats (nlibs/CSR.cc:241-248) of a device CSR: 18 power-of-two buckets of the row lengths."""
     out = (C.c_int * 18)()
-    _check(lib().hip_nnzStats(handle.ptr if handle else None, C.c_void_p(dA.rowPtr), int(dA.rows), out), "hip_nnzStats")
+    _check(lib().hip_nnzStats(_hp(handle), C.c_void_p(dA.rowPtr), int(dA.rows), out), "hip_nnzStats")
     return [int(x) for x in out]
 
 
@@ -762,11 +781,10 @@ def resultsComparison(hC, rC, hv, hqueue, rel=1e-6):
 
 def coo_to_csr_raw(handle, rows, cols, nnz, dRow, dCol, dVal, flags):
     """hip_coo_to_csr on raw device pointers -> (dIA, dJA, dA, nnz) from the library pool (release with dev_free)."""
-    ia, ja, av, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(lib().hip_coo_to_csr(handle.ptr if handle else None, int(rows), int(cols), int(nnz), C.c_void_p(dRow),
-                                C.c_void_p(dCol), C.c_void_p(dVal), int(flags), C.byref(ia), C.byref(ja), C.byref(av),
-                                C.byref(n)), "hip_coo_to_csr")
-    return ia.value, ja.value, av.value, n.value
+    out = _CsrOut()
+    _check(lib().hip_coo_to_csr(_hp(handle), int(rows), int(cols), int(nnz), *_ptrs(dRow, dCol, dVal), int(flags), *out.refs()),
+           "hip_coo_to_csr")
+    return out.values()
 
 
 def coo_to_csr(rows, cols, ri, ci, v, flags, handle=None):
@@ -784,57 +802,54 @@ def coo_to_csr(rows, cols, ri, ci, v, flags, handle=None):
     return CSR(av, ja, ia, rows, cols, n, True)
 
 
-def _csr_permute(fn, name, handle, m, n, nnz, IA, JA, VA, rowSrc, colMap):
-    ib, jb, vb = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA),
-              C.c_void_p(rowSrc), C.c_void_p(colMap), C.byref(ib), C.byref(jb), C.byref(vb)), name)
-    return ib.value, jb.value, vb.value
+def _csr_permute(dtype, handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
+    out = _CsrOut(count=False)
+    _call("hip_csr_permute", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA, rowSrc, colMap), *out.refs())
+    return out.values()
 
 
 def csr_permute_raw(handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
     """hip_csr_permute on raw device pointers (rowSrc / colMap: device int arrays or None = identity) -> (dIB, dJB, dB)
     from the library pool (release with dev_free)."""
-    return _csr_permute(lib().hip_csr_permute, "hip_csr_permute", handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
+    return _csr_permute(np.float32, handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
 
 
 def csr_permute_raw_f64(handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
     """csr_permute_raw with float64 values (hip_csr_permute_f64)."""
-    return _csr_permute(lib().hip_csr_permute_f64, "hip_csr_permute_f64", handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
+    return _csr_permute(np.float64, handle, m, n, nnz, IA, JA, VA, rowSrc, colMap)
 
 
-def _csr_transpose(fn, name, handle, m, n, nnz, IA, JA, VA):
-    it, jt, vt = C.c_void_p(), C.c_void_p(), C.c_void_p()
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA),
-              C.byref(it), C.byref(jt), C.byref(vt)), name)
-    return it.value, jt.value, vt.value
+def _csr_transpose(dtype, handle, m, n, nnz, IA, JA, VA):
+    out = _CsrOut(count=False)
+    _call("hip_csr_transpose", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA), *out.refs())
+    return out.values()
 
 
 def csr_transpose_raw(handle, m, n, nnz, IA, JA, VA):
     """hip_csr_transpose on raw device pointers -> (dIT[n+1], dJT, dAT) from the library pool (release with dev_free)."""
-    return _csr_transpose(lib().hip_csr_transpose, "hip_csr_transpose", handle, m, n, nnz, IA, JA, VA)
+    return _csr_transpose(np.float32, handle, m, n, nnz, IA, JA, VA)
 
 
 def csr_transpose_raw_f64(handle, m, n, nnz, IA, JA, VA):
     """csr_transpose_raw with float64 values (hip_csr_transpose_f64)."""
-    return _csr_transpose(lib().hip_csr_transpose_f64, "hip_csr_transpose_f64", handle, m, n, nnz, IA, JA, VA)
+    return _csr_transpose(np.float64, handle, m, n, nnz, IA, JA, VA)
 
 
-def _csr_diff(fn, name, handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol):
+def _csr_diff(dtype, handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol):
     out = CsrDiff()
-    _check(fn(handle.ptr if handle else None, int(m), int(n), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA),
-              C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzB), float(rel), float(abs_tol), C.byref(out)), name)
+    _call("hip_csr_diff", dtype, _hp(handle), int(m), int(n), *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB),
+          float(rel), float(abs_tol), C.byref(out))
     return out
 
 
 def csr_diff_raw(handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel=1e-6, abs_tol=0.0):
     """hip_csr_diff on raw device pointers (float32 values) -> CsrDiff"""
-    return _csr_diff(lib().hip_csr_diff, "hip_csr_diff", handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol)
+    return _csr_diff(np.float32, handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol)
 
 
 def csr_diff_raw_f64(handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel=1e-6, abs_tol=0.0):
     """csr_diff_raw with float64 values (hip_csr_diff_f64)"""
-    return _csr_diff(lib().hip_csr_diff_f64, "hip_csr_diff_f64", handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel,
-                     abs_tol)
+    return _csr_diff(np.float64, handle, m, n, IA, JA, VA, nnzA, IB, JB, VB, nnzB, rel, abs_tol)
 
 
 def csr_differs_stats_raw(handle, m, IA, IB, percents, dtype=np.float32):
@@ -845,23 +860,20 @@ def csr_differs_stats_raw(handle, m, IA, IB, percents, dtype=np.float32):
     if pc.ndim != 1:
         raise SpgemmError("differsStats: percents must be one-dimensional")
     counts = (C.c_int * (len(pc) + 4))()
-    fn, name = (lib().hip_csr_differsStats_f64, "hip_csr_differsStats_f64") if f64 else \
-        (lib().hip_csr_differsStats, "hip_csr_differsStats")
-    _check(fn(handle.ptr if handle else None, int(m), C.c_void_p(IA), C.c_void_p(IB),
-              pc.ctypes.data_as(_D if f64 else _F) if len(pc) else None, len(pc), counts), name)
+    _call("hip_csr_differsStats", dtype, _hp(handle), int(m), *_ptrs(IA, IB),
+          pc.ctypes.data_as(_D if f64 else _F) if len(pc) else None, len(pc), counts)
     return [int(x) for x in counts]
 
 
 def permutation_transpose_raw(handle, length, dP, dPt):
     """hip_permutation_transpose on raw device pointers: dPt[dP[i]] = i (dPt: caller's device int[length])."""
-    _check(lib().hip_permutation_transpose(handle.ptr if handle else None, int(length), C.c_void_p(dP), C.c_void_p(dPt)),
-           "hip_permutation_transpose")
+    _check(lib().hip_permutation_transpose(_hp(handle), int(length), *_ptrs(dP, dPt)), "hip_permutation_transpose")
 
 
 def row_descending_permutation_raw(handle, m, IA):
     """hip_csr_row_descending_permutation on a raw device rowPtr -> device int[m] from the pool (release with dev_free)."""
     dp = C.c_void_p()
-    _check(lib().hip_csr_row_descending_permutation(handle.ptr if handle else None, int(m), C.c_void_p(IA), C.byref(dp)),
+    _check(lib().hip_csr_row_descending_permutation(_hp(handle), int(m), C.c_void_p(IA), C.byref(dp)),
            "hip_csr_row_descending_permutation")
     return dp.value
 
@@ -883,8 +895,8 @@ def permutation_transpose(P, handle=None):
 def row_flops_raw(handle, IA, JA, IB, m, out_ptr):
     """Per-row product counts into a device int[m]; returns P."""
     tot = C.c_longlong(0)
-    _check(lib().hip_csr_row_flops(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(IB),
-                                   int(m), C.c_void_p(out_ptr), C.byref(tot)), "hip_csr_row_flops")
+    _check(lib().hip_csr_row_flops(_hp(handle), *_ptrs(IA, JA, IB), int(m), C.c_void_p(out_ptr), C.byref(tot)),
+           "hip_csr_row_flops")
     return tot.value
 
 
@@ -894,9 +906,8 @@ def gpuFlopsClassify(dA, dB, handle=None):
     ids, fl = C.c_void_p(), C.c_void_p()
     hv = (C.c_int * HV_LEN)()
     hv_len, tot = C.c_int(0), C.c_longlong(0)
-    rc = lib().hip_gpuFlopsClassify(handle.ptr if handle else None, C.c_void_p(dA.rowPtr), C.c_void_p(dA.colInd),
-                                    C.c_void_p(dB.rowPtr), dA.rows, dA.cols, C.byref(ids), C.byref(fl), hv,
-                                    C.byref(hv_len), C.byref(tot))
+    rc = lib().hip_gpuFlopsClassify(_hp(handle), *_ptrs(dA.rowPtr, dA.colInd, dB.rowPtr), dA.rows, dA.cols, C.byref(ids),
+                                    C.byref(fl), hv, C.byref(hv_len), C.byref(tot))
     _check(rc, "hip_gpuFlopsClassify")
     return [int(x) for x in hv], hv_len.value, ids.value, fl.value, tot.value
 
@@ -904,12 +915,12 @@ def gpuFlopsClassify(dA, dB, handle=None):
 def sgpuSpMMWrapper(dA, dB, drowIds, hv, dflops, handle=None):
     assert dA.on_device and dB.on_device
     hv_arr = (C.c_int * HV_LEN)(*hv)
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    rc = lib().hip_sgpuSpMM(handle.ptr if handle else None, *_dev_args(dA), *_dev_args(dB), dA.rows, dA.cols, dB.cols,
-                            C.c_void_p(drowIds), hv_arr, C.c_void_p(dflops), C.byref(ic), C.byref(jc), C.byref(cv),
-                            C.byref(nnz))
+    out = _CsrOut()
+    rc = lib().hip_sgpuSpMM(_hp(handle), *_dev_args(dA), *_dev_args(dB), dA.rows, dA.cols, dB.cols, C.c_void_p(drowIds), hv_arr,
+                            C.c_void_p(dflops), *out.refs())
     _check(rc, "hip_sgpuSpMM")
-    return CSR(cv.value, jc.value, ic.value, dA.rows, dB.cols, nnz.value, True)
+    ic, jc, cv, nnz = out.values()
+    return CSR(cv, jc, ic, dA.rows, dB.cols, nnz, True)
 
 
 def scudaSpMM(hA, hB, handle=None):
@@ -935,12 +946,10 @@ def scudaSpMM(hA, hB, handle=None):
 def rmcl_iter_device_raw(handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz):
     """hip_gpuRmclIter_device on raw device pointers: maxIter iterations Mt <- prune(Mgt * Mt) without packing Mt between
     them.  Returns (I, J, V, nnz) of the final Mt in pool arrays; release the three with dev_free."""
-    i_, j_, c_, n_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(lib().hip_gpuRmclIter_device(handle.ptr if handle else None, int(maxIter), int(rows), int(cols), C.c_void_p(gI),
-                                        C.c_void_p(gJ), C.c_void_p(gV), int(gnnz), C.c_void_p(tI), C.c_void_p(tJ),
-                                        C.c_void_p(tV), int(tnnz), C.byref(i_), C.byref(j_), C.byref(c_), C.byref(n_)),
-           "hip_gpuRmclIter_device")
-    return i_.value, j_.value, c_.value, n_.value
+    out = _CsrOut()
+    _check(lib().hip_gpuRmclIter_device(_hp(handle), int(maxIter), int(rows), int(cols), *_ptrs(gI, gJ, gV), int(gnnz),
+                                        *_ptrs(tI, tJ, tV), int(tnnz), *out.refs()), "hip_gpuRmclIter_device")
+    return out.values()
 
 
 def gpuRmclIter_device(maxIter, Mgt, Mt, handle=None):
@@ -961,13 +970,8 @@ def gpuRmclIter(maxIter, Mgt, Mt):
                            Mt.colInd.ctypes.data_as(_I), Mt.values.ctypes.data_as(_F), Mt.nnz,
                            C.byref(oi), C.byref(oj), C.byref(ov), C.byref(on))
     _check(rc, "hip_gpuRmclIter")
-    n = on.value
-    rp = np.ctypeslib.as_array(oi, shape=(Mt.rows + 1,)).copy()
-    ci = np.ctypeslib.as_array(oj, shape=(n,)).copy() if n else np.zeros(0, np.int32)
-    v = np.ctypeslib.as_array(ov, shape=(n,)).copy() if n else np.zeros(0, np.float32)
-    for p in (oi, oj, ov):
-        L.free(C.cast(p, C.c_void_p))
-    return CSR(v, ci, rp, Mt.rows, Mt.cols, n)
+    rp, ci, v = _take_malloced(L, oi, oj, ov, Mt.rows, on.value)
+    return CSR(v, ci, rp, Mt.rows, Mt.cols, on.value)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1040,11 +1044,12 @@ def _host_args(M):
     return [M.rowPtr.ctypes.data_as(_I), M.colInd.ctypes.data_as(_I), M.values.ctypes.data_as(_F), int(M.nnz)]
 
 
-def _take_malloced(L, pi, pj, pv, rows, n):
+def _take_malloced(L, pi, pj, pv, rows, n, dtype=np.float32):
+    """copies of the three malloc()ed arrays a host-array entry point returned, which are then freed"""
     rp = np.ctypeslib.as_array(pi, shape=(rows + 1,)).copy()
     ci = np.ctypeslib.as_array(pj, shape=(n,)).copy() if n else np.zeros(0, np.int32)
-    v = np.ctypeslib.as_array(pv, shape=(n,)).copy() if n else np.zeros(0, np.float32)
-    for p in (pi, pj, pv):
+    v = np.ctypeslib.as_array(pv, shape=(n,)).copy() if n else np.zeros(0, dtype)
+    for p in (pi, pj, pv):                          # CSR::dispose() == free() (nlibs/CSR.h:323-327)
         L.free(C.cast(p, C.c_void_p))
     return rp, ci, v
 
@@ -1171,21 +1176,47 @@ def gpuRmclIter_sharded(group, maxIter, Mgt, Mt):
 
 def sort_rows_device(dC, handle=None):
     """CSR::makeOrdered on a device CSR (hip_csr_sort_rows, or hip_csr_sort_rows_f64 for float64 values)."""
-    f64 = _value_dtype(dC.dtype) == np.float64
-    fn, name = (lib().hip_csr_sort_rows_f64, "hip_csr_sort_rows_f64") if f64 else (lib().hip_csr_sort_rows, "hip_csr_sort_rows")
-    _check(fn(handle.ptr if handle else None, dC.rows, C.c_void_p(dC.rowPtr), C.c_void_p(dC.colInd),
-              C.c_void_p(dC.values)), name)
+    _call("hip_csr_sort_rows", dC.dtype, _hp(handle), dC.rows, *_ptrs(dC.rowPtr, dC.colInd, dC.values))
+
+
+@contextlib.contextmanager
+def _sorted_copy_pair(mine, dB, handle):
+    """-> (mine, a deep copy of dB), both row-sorted on the device, for one comparison; dB itself is left alone.  Owns
+    `mine` (a device CSR made for the comparison) and the copy: both are released on the way out."""
+    try:
+        ib, jb, vb = _csr_permute(dB.dtype, handle, dB.rows, dB.cols, dB.nnz, dB.rowPtr, dB.colInd, dB.values)   # identity maps
+        theirs = CSR(vb, jb, ib, dB.rows, dB.cols, dB.nnz, True, dtype=dB.dtype)
+        try:
+            sort_rows_device(mine, handle)
+            sort_rows_device(theirs, handle)
+            yield mine, theirs
+        finally:
+            theirs.deviceDispose()
+    finally:
+        mine.deviceDispose()
+
+
+# what the two tiled formats (BCSR, MCSR's corner) share: rowPtr / colInd / values of nnzb tiles of r x c, nnz entries in them
+def _check_tile(r, c):
+    if r < 1 or c < 1 or r * c > BCSR_MAX_TILE:
+        raise SpgemmError(f"tile r={r} c={c}: need r >= 1, c >= 1, r * c <= {BCSR_MAX_TILE}")
+
+
+def _tile_density(t):
+    cells = t.nnzb * t.r * t.c
+    return float(t.nnz) / cells * 100.0 if cells else 0.0
+
+
+def _free_tiles(t):
+    for p in (t.rowPtr, t.colInd, t.values):
+        dev_free(p)
+    t.rowPtr = t.colInd = t.values = None
+    t.nnzb = 0
 
 
 # ---------------------------------------------------------------------------------------------
 # column-partitioned CSR (include/spgemm_hip.h "column-partitioned CSR"): split, blockwise product, join
 # ---------------------------------------------------------------------------------------------
-def _pcsr_fn(name, dtype):
-    f64 = _value_dtype(dtype) == np.float64
-    name = name + "_f64" if f64 else name
-    return getattr(lib(), name), name
-
-
 def _block_table(blocks):
     """blocks: sequence of (rowPtr, colInd, values, nnz) device pointers -> the four host arrays the C side takes"""
     c = len(blocks)
@@ -1196,32 +1227,27 @@ def _block_table(blocks):
 def csr_split_columns_raw(handle, m, n, nnz, IA, JA, VA, c, dtype=np.float32):
     """hip_csr_split_columns (float32) / _f64 on raw device pointers -> (dIP, dJP, dP, blockPtr): the packed arrays from
     the library pool (release the three with dev_free) and the host list of c + 1 block starts."""
-    fn, name = _pcsr_fn("hip_csr_split_columns", dtype)
-    ip, jp, vp = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    out = _CsrOut(count=False)
     bp = (C.c_int * (max(int(c), 0) + 1))()
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(c),
-              C.byref(ip), C.byref(jp), C.byref(vp), bp), name)
-    return ip.value, jp.value, vp.value, [int(x) for x in bp]
+    _call("hip_csr_split_columns", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA), int(c), *out.refs(), bp)
+    return out.values() + ([int(x) for x in bp],)
 
 
 def pcsr_join_raw(handle, m, n, blocks, dtype=np.float32):
     """hip_pcsr_join / _f64: blocks = c tuples (rowPtr, colInd, values, nnz) of device pointers, each an m x stride CSR
     -> (dIC, dJC, dC, nnz) from the library pool (release with dev_free)."""
-    fn, name = _pcsr_fn("hip_pcsr_join", dtype)
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(fn(handle.ptr if handle else None, int(m), int(n), len(blocks), *_block_table(blocks),
-              C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
-    return ic.value, jc.value, cv.value, nnz.value
+    out = _CsrOut()
+    _call("hip_pcsr_join", dtype, _hp(handle), int(m), int(n), len(blocks), *_block_table(blocks), *out.refs())
+    return out.values()
 
 
 def pcsr_spmm_raw(handle, IA, JA, VA, nnzA, m, k, n, blocks, dtype=np.float32):
     """hip_pcsr_spmm / _f64: A (m x k) times the c blocks of a k x n matrix -> list of c tuples (dIC, dJC, dC, nnz), each
     its own allocation (release with dev_free).  handle.stats() afterwards describes the last block's product."""
-    fn, name = _pcsr_fn("hip_pcsr_spmm", dtype)
     c = len(blocks)
     ic, jc, cv, nnz = (C.c_void_p * c)(), (C.c_void_p * c)(), (C.c_void_p * c)(), (C.c_int * c)()
-    _check(fn(handle.ptr if handle else None, C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(nnzA), int(m), int(k),
-              int(n), c, *_block_table(blocks), ic, jc, cv, nnz), name)
+    _call("hip_pcsr_spmm", dtype, _hp(handle), *_ptrs(IA, JA, VA), int(nnzA), int(m), int(k), int(n), c, *_block_table(blocks),
+          ic, jc, cv, nnz)
     return [(ic[b], jc[b], cv[b], int(nnz[b])) for b in range(c)]
 
 
@@ -1297,19 +1323,8 @@ class PCSR:
             return False
         if _value_dtype(dB.dtype) != self.dtype:
             raise SpgemmError(f"mixed value types: the partitioned matrix is {self.dtype}, B is {dB.dtype}")
-        raw = csr_permute_raw_f64 if self.dtype == np.float64 else csr_permute_raw
-        mine = self.join(handle)
-        try:
-            ib, jb, vb = raw(handle, dB.rows, dB.cols, dB.nnz, dB.rowPtr, dB.colInd, dB.values)       # a deep copy
-            theirs = CSR(vb, jb, ib, dB.rows, dB.cols, dB.nnz, True, dtype=dB.dtype)
-            try:
-                sort_rows_device(mine, handle)
-                sort_rows_device(theirs, handle)
-                return mine.isEqual(theirs, handle)
-            finally:
-                theirs.deviceDispose()
-        finally:
-            mine.deviceDispose()
+        with _sorted_copy_pair(self.join(handle), dB, handle) as (mine, theirs):
+            return mine.isEqual(theirs, handle)
 
     def deviceDispose(self):
         if self._base is not None:
@@ -1328,21 +1343,18 @@ class PCSR:
 def csr_to_bcsr_raw(handle, m, n, nnz, IA, JA, VA, r, c, dtype=np.float32):
     """hip_csr_to_bcsr (float32) / _f64 on raw device pointers -> (dIB, dJB, dB, nnzb): block rowPtr int[bm + 1], block
     columns int[nnzb], nnzb * r * c values, all from the library pool (release with dev_free)."""
-    fn, name = _pcsr_fn("hip_csr_to_bcsr", dtype)
-    ib, jb, vb, nnzb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(r),
-              int(c), C.byref(ib), C.byref(jb), C.byref(vb), C.byref(nnzb)), name)
-    return ib.value, jb.value, vb.value, nnzb.value
+    out = _CsrOut()
+    _call("hip_csr_to_bcsr", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA), int(r), int(c), *out.refs())
+    return out.values()
 
 
 def bcsr_to_csr_raw(handle, m, n, r, c, nnzb, IB, JB, VB, drop_tol=1e-9, dtype=np.float32):
     """hip_bcsr_to_csr / _f64: the tiles written out row by row -> (dIC, dJC, dC, nnz) from the library pool; a cell is kept
     when its column is below n and fabs(value) > drop_tol (compared in double)."""
-    fn, name = _pcsr_fn("hip_bcsr_to_csr", dtype)
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(r), int(c), int(nnzb), C.c_void_p(IB), C.c_void_p(JB),
-              C.c_void_p(VB), float(drop_tol), C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
-    return ic.value, jc.value, cv.value, nnz.value
+    out = _CsrOut()
+    _call("hip_bcsr_to_csr", dtype, _hp(handle), int(m), int(n), int(r), int(c), int(nnzb), *_ptrs(IB, JB, VB), float(drop_tol),
+          *out.refs())
+    return out.values()
 
 
 class BCSR:
@@ -1354,8 +1366,7 @@ class BCSR:
     def __init__(self, dM, r, c, handle=None):
         assert dM.on_device
         r, c = int(r), int(c)
-        if r < 1 or c < 1 or r * c > BCSR_MAX_TILE:
-            raise SpgemmError(f"tile r={r} c={c}: need r >= 1, c >= 1, r * c <= {BCSR_MAX_TILE}")
+        _check_tile(r, c)
         self.dtype = _value_dtype(dM.dtype)
         self.m, self.n, self.r, self.c, self.nnz = dM.rows, dM.cols, r, c, dM.nnz
         self.bm, self.bn = (self.m + r - 1) // r, (self.n + c - 1) // c
@@ -1375,8 +1386,7 @@ class BCSR:
     def nonzero_density(self):
         """BCSR::nonzeroDensity (nlibs/BCSR.h:61-63): nnz / (nnzb * r * c) * 100; 0.0 without tiles (the reference
         divides by zero there)"""
-        cells = self.nnzb * self.r * self.c
-        return float(self.nnz) / cells * 100.0 if cells else 0.0
+        return _tile_density(self)
 
     def is_equal(self, dB, handle=None):
         """BCSR::isEqual (nlibs/BCSR.cc:67-116) against a device CSR: the tiles written out with drop_tol = 1e-9 and a
@@ -1388,36 +1398,20 @@ class BCSR:
             raise SpgemmError(f"shape mismatch: the blocked matrix is {self.m}x{self.n}, B is {dB.rows}x{dB.cols}")
         if _value_dtype(dB.dtype) != self.dtype:
             raise SpgemmError(f"mixed value types: the blocked matrix is {self.dtype}, B is {dB.dtype}")
-        f64 = self.dtype == np.float64
-        copy, diff = (csr_permute_raw_f64, csr_diff_raw_f64) if f64 else (csr_permute_raw, csr_diff_raw)
-        mine = self.to_csr(1e-9, handle)
-        try:
-            ib, jb, vb = copy(handle, dB.rows, dB.cols, dB.nnz, dB.rowPtr, dB.colInd, dB.values)       # a deep copy
-            theirs = CSR(vb, jb, ib, dB.rows, dB.cols, dB.nnz, True, dtype=dB.dtype)
-            try:
-                sort_rows_device(mine, handle)
-                sort_rows_device(theirs, handle)
-                d = diff(handle, self.m, self.n, mine.rowPtr, mine.colInd, mine.values, mine.nnz, theirs.rowPtr,
-                         theirs.colInd, theirs.values, theirs.nnz, 0.0, 1e-9)
-                return d.rows_len_differ == 0 and d.beyond == 0 and d.max_abs_only_b <= 1e-9
-            finally:
-                theirs.deviceDispose()
-        finally:
-            mine.deviceDispose()
+        with _sorted_copy_pair(self.to_csr(1e-9, handle), dB, handle) as (mine, theirs):
+            d = _csr_diff(self.dtype, handle, self.m, self.n, mine.rowPtr, mine.colInd, mine.values, mine.nnz, theirs.rowPtr,
+                          theirs.colInd, theirs.values, theirs.nnz, 0.0, 1e-9)
+            return d.rows_len_differ == 0 and d.beyond == 0 and d.max_abs_only_b <= 1e-9
 
     def dispose(self):
-        for p in (self.rowPtr, self.colInd, self.values):
-            dev_free(p)
-        self.rowPtr = self.colInd = self.values = None
-        self.nnzb = 0
+        _free_tiles(self)
 
 
 # ---------------------------------------------------------------------------------------------
 # mixed CSR (include/spgemm_hip.h "mixed CSR"): the top-left corner as r x c dense tiles, the rest as a CSR, and back
 # ---------------------------------------------------------------------------------------------
 def _check_corner(m, n, r, c, blockRows, blockCols):
-    if r < 1 or c < 1 or r * c > BCSR_MAX_TILE:
-        raise SpgemmError(f"tile r={r} c={c}: need r >= 1, c >= 1, r * c <= {BCSR_MAX_TILE}")
+    _check_tile(r, c)
     if not (0 <= blockRows <= m and 0 <= blockCols <= n):
         raise SpgemmError(f"corner {blockRows} x {blockCols} outside the {m} x {n} matrix")
     if blockRows % r:
@@ -1428,25 +1422,20 @@ def csr_to_mcsr_raw(handle, m, n, nnz, IA, JA, VA, r, c, blockRows, blockCols, d
     """hip_csr_to_mcsr (float32) / _f64 on raw device pointers -> (dIB, dJB, dB, nnzb, dIR, dJR, dR, nnzR): the corner's
     block rowPtr int[blockRows / r + 1], block columns int[nnzb] and nnzb * r * c values, then the m x n remainder CSR; all
     from the library pool (release with dev_free)."""
-    fn, name = _pcsr_fn("hip_csr_to_mcsr", dtype)
-    ib, jb, vb, nnzb = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    ir, jr, vr, nnzr = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(nnz), C.c_void_p(IA), C.c_void_p(JA), C.c_void_p(VA), int(r),
-              int(c), int(blockRows), int(blockCols), C.byref(ib), C.byref(jb), C.byref(vb), C.byref(nnzb), C.byref(ir),
-              C.byref(jr), C.byref(vr), C.byref(nnzr)), name)
-    return ib.value, jb.value, vb.value, nnzb.value, ir.value, jr.value, vr.value, nnzr.value
+    corner, rest = _CsrOut(), _CsrOut()
+    _call("hip_csr_to_mcsr", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA), int(r), int(c), int(blockRows),
+          int(blockCols), *corner.refs(), *rest.refs())
+    return corner.values() + rest.values()
 
 
 def mcsr_to_csr_raw(handle, m, n, r, c, blockRows, blockCols, nnzb, IB, JB, VB, nnzR, IR, JR, VR, drop_tol=1e-9,
                     dtype=np.float32):
     """hip_mcsr_to_csr / _f64: row i = the corner's row (as hip_bcsr_to_csr writes it) followed by the remainder's row
     -> (dIC, dJC, dC, nnz) from the library pool."""
-    fn, name = _pcsr_fn("hip_mcsr_to_csr", dtype)
-    ic, jc, cv, nnz = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
-    _check(fn(handle.ptr if handle else None, int(m), int(n), int(r), int(c), int(blockRows), int(blockCols), int(nnzb),
-              C.c_void_p(IB), C.c_void_p(JB), C.c_void_p(VB), int(nnzR), C.c_void_p(IR), C.c_void_p(JR), C.c_void_p(VR),
-              float(drop_tol), C.byref(ic), C.byref(jc), C.byref(cv), C.byref(nnz)), name)
-    return ic.value, jc.value, cv.value, nnz.value
+    out = _CsrOut()
+    _call("hip_mcsr_to_csr", dtype, _hp(handle), int(m), int(n), int(r), int(c), int(blockRows), int(blockCols), int(nnzb),
+          *_ptrs(IB, JB, VB), int(nnzR), *_ptrs(IR, JR, VR), float(drop_tol), *out.refs())
+    return out.values()
 
 
 class MCSR:
@@ -1487,14 +1476,10 @@ class MCSR:
 
     def nonzero_density(self):
         """BCSR::nonzeroDensity (nlibs/BCSR.h:61-63) of the corner: nnz / (nnzb * r * c) * 100; 0.0 without tiles"""
-        cells = self.nnzb * self.r * self.c
-        return float(self.nnz) / cells * 100.0 if cells else 0.0
+        return _tile_density(self)
 
     def dispose(self):
-        for p in (self.rowPtr, self.colInd, self.values):
-            dev_free(p)
-        self.rowPtr = self.colInd = self.values = None
-        self.nnzb = 0
+        _free_tiles(self)
         if self.remainder is not None:
             self.remainder.deviceDispose()
             self.remainder = None

@@ -1,0 +1,138 @@
+"""The test kit of the device-CSR formats (reorder, compare, pcsr, bcsr, mcsr, coo) and of the modules around them: the
+fixtures and helpers that two or more test modules used to spell out themselves.  A plain module, imported by name:
+
+    from devcsr import built_gpu, handle  # noqa: F401      (pytest registers a fixture in the importing module, so
+                                                             module scope and autouse mean "per test module", as before)
+    from devcsr import typed, take, assert_bits
+
+pytest does not rewrite the asserts of a helper module: every assert here carries its message."""
+import ctypes as C
+import socket
+
+import numpy as np
+import pytest
+
+import reorder_ref as rr
+from helpers import po, synth_csr
+from sparse_matrix_with_flops_amd import hipspgemm as hs
+
+
+# ---- fixtures --------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    """the native pieces are compiled (the *_abi.py modules: no GPU needed)"""
+    import __graft_entry__ as ge
+    ge.build()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built_gpu():
+    """the native pieces are compiled and there is a HIP device (the test_gpu_*.py modules)"""
+    import __graft_entry__ as ge
+    ge.build()
+    assert hs.device_count() >= 1, "no HIP device"
+
+
+@pytest.fixture(scope="module")
+def handle():
+    h = hs.Handle(0)
+    yield h
+    h.close()
+
+
+# ---- inputs (made once by their callers, never modified) -------------------------------------------------------------
+def with_nnz(rows, cols, nnz, seed):
+    """exactly nnz entries over `rows` rows, random columns (repeats allowed), some rows empty"""
+    rng = np.random.default_rng(seed)
+    owner = np.sort(rng.integers(0, rows, size=nnz))
+    rp = np.zeros(rows + 1, np.int32)
+    np.cumsum(np.bincount(owner, minlength=rows), out=rp[1:])
+    return rr.Host(rp, rng.integers(0, cols, size=nnz), (rng.random(nnz) + 0.25).astype(np.float32), rows, cols)
+
+
+def one_long_row(rows=300, cols=300, row=17):
+    """row `row` holds 20 000 entries (columns repeat), every other row is empty"""
+    rng = np.random.default_rng(17)
+    rp = np.zeros(rows + 1, np.int32)
+    rp[row + 1:] = 20000
+    return rr.Host(rp, rng.integers(0, cols, size=20000), (rng.random(20000) + 0.25).astype(np.float32), rows, cols)
+
+
+def _plain(M):
+    return rr.Host(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
+
+
+def _special(dtype):
+    """name -> value: NaN with a payload, -0.0, a denormal, 1e-9 and the next number above it, in `dtype`"""
+    dt = np.dtype(dtype)
+    nan = np.array([0x7fc12345] if dt == np.float32 else [0x7ff8000012345678], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
+    tiny = np.array([1], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
+    at = dt.type(1e-9)
+    return {"nan": nan, "-0": dt.type(-0.0), "denormal": tiny, "1e-9": at, "above": np.nextafter(at, dt.type(1))}
+
+
+def _strided_tiles(ntiles, side, tile):
+    """side x side, one entry in the top left cell of each of the first `ntiles` tile x tile tiles"""
+    per_row = (side + tile - 1) // tile
+    t = np.arange(ntiles, dtype=np.int64)
+    rows_of, cols_of = (t // per_row) * tile, (t % per_row) * tile
+    rp = np.zeros(side + 1, np.int64)
+    np.cumsum(np.bincount(rows_of, minlength=side), out=rp[1:])
+    return rr.Host(rp, cols_of, np.ones(ntiles, np.float32), side, side)
+
+
+def _graph(m, seed):
+    """the R-MCL start matrix of a synthetic graph: transpose + self loops + row-normalise"""
+    A = synth_csr(m, seed, 2)
+    ri = np.repeat(np.arange(A.rows, dtype=np.int32), np.diff(A.rowPtr))
+    return po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))
+
+
+def unpack(z, prefix):
+    r, c = z[prefix + "_shape"]
+    return po.CSRHost(z[prefix + "_rowPtr"], z[prefix + "_colInd"], z[prefix + "_values"], int(r), int(c))
+
+
+# ---- host <-> device -------------------------------------------------------------------------------------------------
+def to_hs(M):
+    return hs.CSR.from_arrays(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
+
+
+def typed(M, dtype):
+    """host hs.CSR of M; float64 values get bits a float cannot hold"""
+    v = np.asarray(M.values, np.float64)
+    if np.dtype(dtype) == np.float64:
+        v = v + 2.0 ** -40
+    return hs.CSR.from_arrays(M.rowPtr, M.colInd, v, M.rows, M.cols, dtype=dtype)
+
+
+def typed_plain(M, dtype):
+    return hs.CSR.from_arrays(M.rowPtr, M.colInd, np.asarray(M.values, dtype), M.rows, M.cols, dtype=dtype)
+
+
+def take(dev):
+    host = dev.toCpuCSR()
+    dev.deviceDispose()
+    return host
+
+
+def assert_bits(got, want, what=""):
+    assert got.rows == want.rows and got.cols == want.cols, what
+    assert np.array_equal(np.asarray(got.rowPtr), np.asarray(want.rowPtr)), f"{what}: rowPtr"
+    assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
+    g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
+    assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
+
+
+# ---- the rest --------------------------------------------------------------------------------------------------------
+def _outs(n=3):
+    """n non-null output slots for an entry point that must fail before it writes them"""
+    return [C.c_void_p(1) for _ in range(n)]
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p

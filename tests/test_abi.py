@@ -7,14 +7,9 @@ import re
 import numpy as np
 import pytest
 
+from devcsr import built  # noqa: F401
 from helpers import ROOT
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
 
 
 def declared_symbols():

@@ -10,6 +10,8 @@ import pytest
 
 import bcsr_ref as br
 import reorder_ref as rr
+from devcsr import built  # noqa: F401
+from devcsr import _outs
 from helpers import ROOT, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -17,13 +19,8 @@ ERR_ARG = 2
 TWINS = ["", "_f64"]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-
-
 # ---- the hand-worked matrices ----------------------------------------------------------------------------------------
+# per format: a matrix worked by hand for this format's layout (3 x 6 for 2 x 2 tiles)
 def _hand():
     """A is 3 x 6, r = c = 2, so bm = 2, bn = 3:
     row 0   (5, 1.0) (0, 2.0)
@@ -91,10 +88,6 @@ def test_restatement_keeps_float64_bits_and_applies_the_tolerance_in_double():
 
 # ---- argument errors: no device is touched (the "device pointers" are never dereferenced) ----------------------------
 ONE = C.c_void_p(8)
-
-
-def _outs(n=3):
-    return [C.c_void_p(1) for _ in range(n)]
 
 
 @pytest.mark.parametrize("twin", TWINS)
@@ -185,7 +178,7 @@ def test_python_mirror_refuses_mismatches_before_device_work():
 def test_cpp_mirror_refuses_a_shape_mismatch_before_device_work():
     """tests/cpp/bcsr_check.cc --shape-check: BCSR::isEqual against another row count and another column count"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "Makefile.bcsr"])
+    subprocess.check_call(["make", "-s", "-C", cpp, "bcsr_check.x"])
     out = subprocess.run([os.path.join(cpp, "bcsr_check.x"), "--shape-check"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "refused" in out.stdout and "B 5 x 4" in out.stdout and "B 4 x 5" in out.stdout

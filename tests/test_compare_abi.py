@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 
 import compare_ref as cr
+from devcsr import built  # noqa: F401
 from helpers import DATA, ROOT, po
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 ERR_ARG = 2
 REF_PERCENTS = [-30, -20, -5, 0, 5, 20, 30, 100]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
 
 
 @pytest.mark.parametrize("name", ["hip_csr_diff", "hip_csr_diff_f64"])
@@ -145,7 +140,7 @@ def test_restatement_matches_the_mirrors_host_differs_stats(tmp_path):
     B = po.rmcl_iters(A, A, 1)
     assert A.rows == B.rows and not np.array_equal(A.rowPtr, B.rowPtr)
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "Makefile.compare"])
+    subprocess.check_call(["make", "-s", "-C", cpp, "compare_check.x"])
     files = []
     for name, M in (("a.txt", A), ("b.txt", B)):
         files.append(str(tmp_path / name))

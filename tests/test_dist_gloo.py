@@ -3,7 +3,6 @@ flops-balanced row partition, per-rank symbolic/numeric into a slice of the gath
 send/recv pairs — with the local compute swapped for the CPU oracle (tests may use the oracle; the product's
 engine is HipEngine and has no CPU fallback)."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -11,6 +10,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from devcsr import _free_port
 from helpers import assert_parity, po, synth_csr
 from sparse_matrix_with_flops_amd.dist import ShardedRMCL, ShardedSpGEMM, equal_partition64
 
@@ -49,14 +49,6 @@ class OracleEngine:
     def expand_prune(self, A, B):
         R = po.rmcl_iters(self._host(A), self._host(B), 1)               # prune(A*B), rows of A
         return (torch.from_numpy(R.rowPtr.copy()), torch.from_numpy(R.colInd.copy()), torch.from_numpy(R.values.copy()))
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, m, seed, q, chunks=1):

@@ -7,14 +7,9 @@ import numpy as np
 import pytest
 
 from f64ref import Host64, spgemm_f64
+from devcsr import built  # noqa: F401
 from helpers import po, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
 
 
 def test_f64_argument_errors_do_not_need_a_gpu():

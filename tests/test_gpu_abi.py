@@ -6,18 +6,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devcsr import built_gpu  # noqa: F401
+from devcsr import to_hs
 from helpers import po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-from test_gpu_parity import to_hs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
 
 
 def test_pool_is_per_device_and_trimmed_with_the_last_handle():

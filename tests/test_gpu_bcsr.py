@@ -12,6 +12,8 @@ import pytest
 
 import bcsr_ref as br
 import reorder_ref as rr
+from devcsr import built_gpu, handle  # noqa: F401
+from devcsr import _plain, _special, _strided_tiles, assert_bits, one_long_row, take, typed, with_nnz
 from helpers import ROOT, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -23,38 +25,8 @@ RS_TILE = 2048          # keys per block of the radix kernels (csr_common_device
 SHAPES = [(1, 1), (2, 2), (3, 5), (64, 64), (1, 4096), (4096, 1)]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
-
-
 # ---- inputs (made once, never modified) ------------------------------------------------------------------------------
-def with_nnz(rows, cols, nnz, seed):
-    """exactly nnz entries over `rows` rows, random columns (repeats allowed), some rows empty"""
-    rng = np.random.default_rng(seed)
-    owner = np.sort(rng.integers(0, rows, size=nnz))
-    rp = np.zeros(rows + 1, np.int32)
-    np.cumsum(np.bincount(owner, minlength=rows), out=rp[1:])
-    return rr.Host(rp, rng.integers(0, cols, size=nnz), (rng.random(nnz) + 0.25).astype(np.float32), rows, cols)
-
-
-def one_long_row():
-    """300 x 300, row 17 holds 20 000 entries (columns repeat), every other row is empty"""
-    rng = np.random.default_rng(17)
-    rp = np.zeros(301, np.int32)
-    rp[18:] = 20000
-    return rr.Host(rp, rng.integers(0, 300, size=20000), (rng.random(20000) + 0.25).astype(np.float32), 300, 300)
-
-
+# this format's own edge: the tile boundaries b * c (pcsr: its block stride; mcsr: the corner's last column)
 def boundary_columns(rows, n, c):
     """every row holds the columns b * c - 1 and b * c for each b: the last column of one block and the first of the
     next, in descending order"""
@@ -64,10 +36,7 @@ def boundary_columns(rows, n, c):
     return rr.Host(rp, np.tile(cols, rows), v, rows, n)
 
 
-def _plain(M):
-    return rr.Host(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
-
-
+# per format: the second member is this format's parameter list (tile shapes; pcsr: block counts)
 def _cases():
     """name -> (matrix, tile shapes)"""
     out = {"0x0": (rr.Host(np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), 0, 0), SHAPES),
@@ -87,28 +56,7 @@ CASES = _cases()
 REPEATS = ["long row"] + [f"nnz {x}" for x in (CP_TILE + 1, RS_TILE + 1)]
 
 
-def typed(M, dtype):
-    """host hs.CSR of M; float64 values get bits a float cannot hold"""
-    v = np.asarray(M.values, np.float64)
-    if np.dtype(dtype) == np.float64:
-        v = v + 2.0 ** -40
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, v, M.rows, M.cols, dtype=dtype)
-
-
-def take(dev):
-    host = dev.toCpuCSR()
-    dev.deviceDispose()
-    return host
-
-
-def assert_bits(got, want, what=""):
-    assert got.rows == want.rows and got.cols == want.cols, what
-    assert np.array_equal(np.asarray(got.rowPtr), np.asarray(want.rowPtr)), f"{what}: rowPtr"
-    assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
-    g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
-    assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
-
-
+# per format: what is downloaded and the restatement's type differ (here bcsr_ref.Blocked)
 def downloaded(b):
     """the three arrays of a hs.BCSR as a bcsr_ref.Blocked"""
     return br.Blocked(hs.d2h(b.rowPtr, b.bm + 1, np.int32), hs.d2h(b.colInd, b.nnzb, np.int32),
@@ -166,15 +114,6 @@ def test_repeated_columns_give_the_same_bytes_twice(handle, name, dtype):
 
 
 # ---- bits ------------------------------------------------------------------------------------------------------------
-def _special(dtype):
-    """name -> value: NaN with a payload, -0.0, a denormal, 1e-9 and the next number above it, in `dtype`"""
-    dt = np.dtype(dtype)
-    nan = np.array([0x7fc12345] if dt == np.float32 else [0x7ff8000012345678], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
-    tiny = np.array([1], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
-    at = dt.type(1e-9)
-    return {"nan": nan, "-0": dt.type(-0.0), "denormal": tiny, "1e-9": at, "above": np.nextafter(at, dt.type(1))}
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_special_values_keep_their_bits_and_the_tolerance_is_applied_in_double(handle, dtype):
     sp = _special(dtype)
@@ -244,16 +183,6 @@ def test_round_trip_of_a_sorted_matrix_is_the_matrix(handle, name, dtype):
 
 
 # ---- bad input -------------------------------------------------------------------------------------------------------
-def _strided_tiles(ntiles, side, tile):
-    """side x side, one entry in the top left cell of each of the first `ntiles` tile x tile tiles"""
-    per_row = (side + tile - 1) // tile
-    t = np.arange(ntiles, dtype=np.int64)
-    rows_of, cols_of = (t // per_row) * tile, (t % per_row) * tile
-    rp = np.zeros(side + 1, np.int64)
-    np.cumsum(np.bincount(rows_of, minlength=side), out=rp[1:])
-    return rr.Host(rp, cols_of, np.ones(ntiles, np.float32), side, side)
-
-
 def test_bad_input_is_an_error_not_a_fault(handle):
     L = hs.lib()
     M = typed(CASES["1000x257"][0], np.float32)
@@ -378,7 +307,7 @@ def test_python_bcsr_round_trip_and_is_equal(handle, dtype):
 def test_cpp_mirror_runs_the_blocked_scenarios():
     """tests/cpp/bcsr_check.cc: the two scenarios of the reference's tests/BCSR_test.cc on the C++ mirror"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "-f", "Makefile.bcsr"])
+    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "bcsr_check.x"])
     out = subprocess.run([os.path.join(cpp, "bcsr_check.x")], capture_output=True, text=True, timeout=120)
     print(out.stdout)
     assert out.returncode == 0, out.stdout + out.stderr

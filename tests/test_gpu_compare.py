@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 import compare_ref as cr
+from reorder_ref import Host
+from devcsr import built_gpu, handle  # noqa: F401
 from helpers import DATA, ROOT, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -26,29 +28,7 @@ MAX_FIELDS = ("max_abs_err", "max_rel_err", "max_abs_only_a", "max_abs_only_b")
 REF_PERCENTS = [-30, -20, -5, 0, 5, 20, 30, 100]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
-
-
 # ---- inputs (made once per name, never modified) ---------------------------------------------------------------------
-class Host:
-    def __init__(self, rowPtr, colInd, values, rows, cols):
-        self.rowPtr = np.ascontiguousarray(rowPtr, dtype=np.int32)
-        self.colInd = np.ascontiguousarray(colInd, dtype=np.int32)
-        self.values = np.ascontiguousarray(values)
-        self.rows, self.cols, self.nnz = int(rows), int(cols), len(self.colInd)
-
-
 def from_flat(pos, values, rows, cols):
     """sorted distinct flat positions row * cols + col -> CSR with strictly ascending rows"""
     pos = np.asarray(pos, np.int64)
@@ -127,6 +107,7 @@ def case(name, dtype):
     return A, B, rep, cr.sum_sq(terms), seq
 
 
+# unlike devcsr.to_hs: the values' own dtype, not float32
 def to_hs(M):
     return hs.CSR.from_arrays(M.rowPtr, M.colInd, M.values, M.rows, M.cols, dtype=M.values.dtype)
 
@@ -420,7 +401,7 @@ def test_cpp_mirror_runs_the_end_of_run_check_on_the_device():
     """tests/cpp/compare_check.cc: RMCL(..., GPU), the result and its deepCopy sorted and compared on the device (Same),
     then one value changed by 1e-3 (Diffs, naming the row)"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "-f", "Makefile.compare"])
+    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "compare_check.x"])
     for name in ("own_graph.snap", "t2.snap"):
         out = subprocess.run([os.path.join(cpp, "compare_check.x"), os.path.join(DATA, name), "3"], capture_output=True,
                              text=True, timeout=120)

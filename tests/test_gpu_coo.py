@@ -7,18 +7,12 @@ import os
 import numpy as np
 import pytest
 
+from devcsr import built_gpu  # noqa: F401
 from helpers import DATA, GOLDEN, po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 pytestmark = pytest.mark.gpu
 FX = np.load(os.path.join(GOLDEN, "fixtures.npz"))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
 
 
 def bits_equal(dev, want):

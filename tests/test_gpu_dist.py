@@ -3,7 +3,6 @@
 tensors with libspgemm_hip.so doing the local work on every rank -- everything of the multi-GPU step except the RCCL
 transport itself, which only an 8-GPU node can exercise."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -11,23 +10,10 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from devcsr import _free_port, _graph
 from helpers import assert_parity, po, synth_csr
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _graph(m, seed):
-    A = synth_csr(m, seed, 2)
-    ri = np.repeat(np.arange(A.rows, dtype=np.int32), np.diff(A.rowPtr))
-    return po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))
 
 
 def _worker(rank, world, port, kind, m, seed, q, chunks=1, partition="flops"):

@@ -15,6 +15,8 @@ import pytest
 import mcsr_ref as mr
 import bcsr_ref as br
 import reorder_ref as rr
+from devcsr import built_gpu, handle  # noqa: F401
+from devcsr import _plain, _special, _strided_tiles, assert_bits, one_long_row, take, typed
 from helpers import ROOT, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -25,20 +27,6 @@ CP_TILE = 1024          # entries per block of the flag / scatter / copy kernels
 SCAN_TILE = 4096        # ints per block of the library's scan (spgemm_device.hpp; checked against the source below)
 RS_TILE = 2048          # keys per block of the radix kernels the corner's tiling runs (csr_common_device.hpp)
 TILES = [(1, 1), (2, 2), (3, 5), (64, 64)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
 
 
 def test_the_tile_sizes_are_the_ones_in_the_code():
@@ -53,10 +41,6 @@ def test_the_tile_sizes_are_the_ones_in_the_code():
 
 
 # ---- inputs (made once, never modified) ------------------------------------------------------------------------------
-def _plain(M):
-    return rr.Host(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
-
-
 def top_heavy(rows, cols, top_rows, n_top, n_rest, seed):
     """exactly n_top entries over the first top_rows rows and n_rest over the others; random columns (repeats allowed),
     some rows empty"""
@@ -68,14 +52,7 @@ def top_heavy(rows, cols, top_rows, n_top, n_rest, seed):
     return rr.Host(rp, rng.integers(0, cols, size=nnz), (rng.random(nnz) + 0.25).astype(np.float32), rows, cols)
 
 
-def one_long_row(rows, cols, row):
-    """row `row` holds 20 000 entries (columns repeat), every other row is empty"""
-    rng = np.random.default_rng(17)
-    rp = np.zeros(rows + 1, np.int32)
-    rp[row + 1:] = 20000
-    return rr.Host(rp, rng.integers(0, cols, size=20000), (rng.random(20000) + 0.25).astype(np.float32), rows, cols)
-
-
+# this format's own edge: the one boundary between corner and remainder (bcsr, pcsr: every tile / block boundary)
 def boundary_columns(rows, n, block_cols):
     """every row holds the columns n - 1, block_cols, block_cols - 1 and 0 in this (descending) order: the first column
     of the remainder stands before the last column of the corner"""
@@ -100,28 +77,7 @@ def corners(m, n, r, c):
     return [(a, b) for a in rows for b in cols]
 
 
-def typed(M, dtype):
-    """host hs.CSR of M; float64 values get bits a float cannot hold"""
-    v = np.asarray(M.values, np.float64)
-    if np.dtype(dtype) == np.float64:
-        v = v + 2.0 ** -40
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, v, M.rows, M.cols, dtype=dtype)
-
-
-def take(dev):
-    host = dev.toCpuCSR()
-    dev.deviceDispose()
-    return host
-
-
-def assert_bits(got, want, what=""):
-    assert got.rows == want.rows and got.cols == want.cols, what
-    assert np.array_equal(np.asarray(got.rowPtr), np.asarray(want.rowPtr)), f"{what}: rowPtr"
-    assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
-    g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
-    assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
-
-
+# per format: what is downloaded and the restatement's type differ (here mcsr_ref.Mixed)
 def downloaded(x):
     """the arrays of a hs.MCSR as a mcsr_ref.Mixed"""
     corner = br.Blocked(hs.d2h(x.rowPtr, x.bm + 1, np.int32), hs.d2h(x.colInd, x.nnzb, np.int32),
@@ -224,15 +180,6 @@ def test_one_long_row_gives_the_same_bytes_twice(handle, where, dtype):
 
 
 # ---- bits ------------------------------------------------------------------------------------------------------------
-def _special(dtype):
-    """name -> value: NaN with a payload, -0.0, a denormal, 1e-9 and the next number above it, in `dtype`"""
-    dt = np.dtype(dtype)
-    nan = np.array([0x7fc12345] if dt == np.float32 else [0x7ff8000012345678], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
-    tiny = np.array([1], np.uint32 if dt == np.float32 else np.uint64).view(dt)[0]
-    at = dt.type(1e-9)
-    return {"nan": nan, "-0": dt.type(-0.0), "denormal": tiny, "1e-9": at, "above": np.nextafter(at, dt.type(1))}
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_special_values_keep_their_bits_and_only_the_corner_drops_them(handle, dtype):
     sp = _special(dtype)
@@ -302,16 +249,6 @@ def test_round_trip_of_a_sorted_matrix_is_the_matrix(handle, name, dtype):
 
 
 # ---- bad input -------------------------------------------------------------------------------------------------------
-def _strided_tiles(ntiles, side, tile):
-    """side x side, one entry in the top left cell of each of the first `ntiles` tile x tile tiles"""
-    per_row = (side + tile - 1) // tile
-    t = np.arange(ntiles, dtype=np.int64)
-    rows_of, cols_of = (t // per_row) * tile, (t % per_row) * tile
-    rp = np.zeros(side + 1, np.int64)
-    np.cumsum(np.bincount(rows_of, minlength=side), out=rp[1:])
-    return rr.Host(rp, cols_of, np.ones(ntiles, np.float32), side, side)
-
-
 def test_bad_input_is_an_error_not_a_fault(handle):
     L = hs.lib()
     M = typed(TALL, np.float32)
@@ -453,7 +390,7 @@ def test_python_mcsr_on_the_reference_vectors(handle, dtype):
 def test_cpp_mirror_runs_the_reference_scenario():
     """tests/cpp/mcsr_check.cc: the scenario of the reference's tests/MCSR_test.cc on the C++ mirror"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "-f", "Makefile.mcsr"])
+    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "mcsr_check.x"])
     out = subprocess.run([os.path.join(cpp, "mcsr_check.x")], capture_output=True, text=True, timeout=120)
     print(out.stdout)
     assert out.returncode == 0, out.stdout + out.stderr

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+from devcsr import to_hs, unpack
 from helpers import DATA, GOLDEN, assert_parity, canonical_arrays, po, random_csr, summarize, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -19,15 +20,6 @@ pytestmark = pytest.mark.gpu
 FX = np.load(os.path.join(GOLDEN, "fixtures.npz"))
 SM = np.load(os.path.join(GOLDEN, "synth_small.npz"))
 META = json.load(open(os.path.join(GOLDEN, "golden.json")))
-
-
-def unpack(z, prefix):
-    r, c = z[prefix + "_shape"]
-    return po.CSRHost(z[prefix + "_rowPtr"], z[prefix + "_colInd"], z[prefix + "_values"], int(r), int(c))
-
-
-def to_hs(M):
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
 
 
 @pytest.fixture(scope="module")

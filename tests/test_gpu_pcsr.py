@@ -14,6 +14,8 @@ import pytest
 
 import pcsr_ref as pr
 import reorder_ref as rr
+from devcsr import built_gpu, handle  # noqa: F401
+from devcsr import assert_bits, one_long_row, take, typed, typed_plain, with_nnz
 from helpers import DATA, ROOT, po, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -25,38 +27,8 @@ RS_TILE = 2048          # keys per block of the radix kernels (csr_common_device
 BLOCK_COUNTS = [1, 2, 3, 7, 64]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
-
-
 # ---- inputs (made once, never modified) ------------------------------------------------------------------------------
-def with_nnz(rows, cols, nnz, seed):
-    """exactly nnz entries over `rows` rows, random columns (repeats allowed), some rows empty"""
-    rng = np.random.default_rng(seed)
-    owner = np.sort(rng.integers(0, rows, size=nnz))
-    rp = np.zeros(rows + 1, np.int32)
-    np.cumsum(np.bincount(owner, minlength=rows), out=rp[1:])
-    return rr.Host(rp, rng.integers(0, cols, size=nnz), (rng.random(nnz) + 0.25).astype(np.float32), rows, cols)
-
-
-def one_long_row():
-    """300 x 300, row 17 holds 20 000 entries (columns repeat), every other row is empty"""
-    rng = np.random.default_rng(17)
-    rp = np.zeros(301, np.int32)
-    rp[18:] = 20000
-    return rr.Host(rp, rng.integers(0, 300, size=20000), (rng.random(20000) + 0.25).astype(np.float32), 300, 300)
-
-
+# this format's own edge: the block boundaries b * stride_of(n, c) (bcsr: b * c; mcsr: the corner's last column)
 def boundary_columns(rows, n, c):
     """every row holds exactly the columns b * stride - 1 and b * stride for each b: the last column of a block and the
     first of the next, in descending order"""
@@ -67,6 +39,7 @@ def boundary_columns(rows, n, c):
     return rr.Host(rp, np.tile(cols, rows), v, rows, n)
 
 
+# per format: the second member is this format's parameter list (block counts; bcsr: tile shapes)
 def _cases():
     """name -> (matrix, block counts)"""
     out = {"0x0": (rr.Host(np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), 0, 0), BLOCK_COUNTS),
@@ -85,28 +58,7 @@ def _cases():
 CASES = _cases()
 
 
-def typed(M, dtype):
-    """host hs.CSR of M; float64 values get bits a float cannot hold"""
-    v = np.asarray(M.values, np.float64)
-    if np.dtype(dtype) == np.float64:
-        v = v + 2.0 ** -40
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, v, M.rows, M.cols, dtype=dtype)
-
-
-def take(dev):
-    host = dev.toCpuCSR()
-    dev.deviceDispose()
-    return host
-
-
-def assert_bits(got, want, what=""):
-    assert got.rows == want.rows and got.cols == want.cols, what
-    assert np.array_equal(np.asarray(got.rowPtr), np.asarray(want.rowPtr)), f"{what}: rowPtr"
-    assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
-    g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
-    assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
-
-
+# per format: what is downloaded and the restatement's type differ (here pcsr_ref.Split)
 def downloaded(p):
     """the packed arrays of a split hs.PCSR as a pcsr_ref.Split"""
     ip, jp, vp = p._base
@@ -166,10 +118,6 @@ def test_join_of_separate_allocations_equals_join_of_the_packed_views(handle, na
         for d in apart + [dM]:
             d.deviceDispose()
         p.deviceDispose()
-
-
-def typed_plain(M, dtype):
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, np.asarray(M.values, dtype), M.rows, M.cols, dtype=dtype)
 
 
 # ---- bad input -------------------------------------------------------------------------------------------------------
@@ -367,7 +315,7 @@ def test_a_failing_block_clears_every_output(handle, products):
 def test_cpp_mirror_runs_the_column_partition_experiment():
     """tests/cpp/pcsr_check.cc: the flow of the reference's correctTests/pcsrTest.cc on the C++ mirror, c = 2 and c = 3"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "-f", "Makefile.pcsr"])
+    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "pcsr_check.x"])
     for c in ("2", "3"):
         out = subprocess.run([os.path.join(cpp, "pcsr_check.x"), os.path.join(DATA, "own_graph.snap"), c], capture_output=True,
                              text=True, timeout=120)

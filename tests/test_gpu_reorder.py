@@ -13,6 +13,8 @@ import pytest
 
 import f64ref
 import reorder_ref as rr
+from devcsr import built_gpu, handle  # noqa: F401
+from devcsr import assert_bits, one_long_row, take, typed, typed_plain, with_nnz
 from helpers import DATA, ROOT, assert_parity, po, random_csr, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -23,38 +25,7 @@ CP_TILE = 1024          # entries per block of the permute copy / transpose key 
 RS_TILE = 2048          # keys per block of the radix kernels (csr_common_device.hpp)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
-
-
 # ---- inputs (made once, never modified) ------------------------------------------------------------------------------
-def with_nnz(rows, cols, nnz, seed):
-    """exactly nnz entries over `rows` rows, random columns (repeats allowed), some rows empty"""
-    rng = np.random.default_rng(seed)
-    owner = np.sort(rng.integers(0, rows, size=nnz))
-    rp = np.zeros(rows + 1, np.int32)
-    np.cumsum(np.bincount(owner, minlength=rows), out=rp[1:])
-    return rr.Host(rp, rng.integers(0, cols, size=nnz), (rng.random(nnz) + 0.25).astype(np.float32), rows, cols)
-
-
-def one_long_row():
-    """300 x 300, row 17 holds 20 000 entries (columns repeat), every other row is empty"""
-    rng = np.random.default_rng(17)
-    rp = np.zeros(301, np.int32)
-    rp[18:] = 20000
-    return rr.Host(rp, rng.integers(0, 300, size=20000), (rng.random(20000) + 0.25).astype(np.float32), 300, 300)
-
-
 def _shapes():
     out = {"0x0": rr.Host(np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), 0, 0),
            "5x7 empty": rr.Host(np.zeros(6, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), 5, 7),
@@ -67,28 +38,6 @@ def _shapes():
 
 
 SHAPES = _shapes()
-
-
-def typed(M, dtype):
-    """host hs.CSR of M; float64 values get bits a float cannot hold"""
-    v = np.asarray(M.values, np.float64)
-    if np.dtype(dtype) == np.float64:
-        v = v + 2.0 ** -40
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, v, M.rows, M.cols, dtype=dtype)
-
-
-def take(dev):
-    host = dev.toCpuCSR()
-    dev.deviceDispose()
-    return host
-
-
-def assert_bits(got, want, what=""):
-    assert got.rows == want.rows and got.cols == want.cols, what
-    assert np.array_equal(np.asarray(got.rowPtr), np.asarray(want.rowPtr)), f"{what}: rowPtr"
-    assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
-    g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
-    assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
 
 
 def perms(n, seed):
@@ -342,10 +291,6 @@ def _permuted_product(A, P, dtype, handle):
     return take(dC)
 
 
-def typed_plain(M, dtype):
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, np.asarray(M.values, dtype), M.rows, M.cols, dtype=dtype)
-
-
 @pytest.mark.parametrize("order", ["random", "descending"])
 def test_product_does_not_depend_on_the_ordering(handle, experiment, order):
     A, want = experiment
@@ -374,7 +319,7 @@ def test_product_does_not_depend_on_the_ordering_f64(handle, experiment):
 def test_cpp_mirror_runs_the_ordering_experiment():
     """tests/cpp/permu_check.cc: the flow of the reference's correctTests/permuTest.cc on the C++ mirror"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "-f", "Makefile.permu"])
+    subprocess.check_call(["make", "-s", "-B", "-C", cpp, "permu_check.x"])
     out = subprocess.run([os.path.join(cpp, "permu_check.x"), os.path.join(DATA, "own_graph.snap")], capture_output=True,
                          text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr

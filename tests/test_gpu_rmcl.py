@@ -8,18 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
+from devcsr import built_gpu  # noqa: F401
+from devcsr import _graph, to_hs, unpack
 from helpers import DATA, GOLDEN, ROOT, assert_rmcl_step, canonical_arrays, po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-from test_gpu_parity import FX, SQUARE, to_hs, unpack
+from test_gpu_parity import FX, SQUARE
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
 
 
 def ordered(M):
@@ -37,12 +32,6 @@ def test_rmcl_fixtures_match_reference_goldens(name, iters):
     wr, wc, wv = ordered(want)
     assert np.array_equal(gr, wr) and np.array_equal(gc, wc)
     assert np.allclose(gv, wv, rtol=1e-6, atol=0.0)                       # north_star: values within 1e-6 relative
-
-
-def _graph(m, seed):
-    A = synth_csr(m, seed, 2)
-    ri = np.repeat(np.arange(A.rows, dtype=np.int32), np.diff(A.rowPtr))
-    return po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))     # transpose + self loops + row-normalise
 
 
 def _device_steps(Mt, iters, fused=True):

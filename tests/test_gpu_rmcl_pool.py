@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from devcsr import built_gpu, handle  # noqa: F401
 from helpers import po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -15,14 +16,7 @@ ENV = ("SPGEMM_RMCL_MAXP", "SPGEMM_RMCL_SYMBOLIC", "SPGEMM_RMCL_PACK")
 
 
 @pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _seasoned_pool(_built):
+def _seasoned_pool(built_gpu):  # noqa: F811
     """The figure compared is the pool's cached bytes, so no call may fetch a block from the driver: such a block is
     cached when it is released, and the figure grows although nothing leaked -- in whichever call first finds no fitting
     block, which depends on what earlier tests left in the pool (the best fit of a call's requests moves once its own
@@ -31,13 +25,6 @@ def _seasoned_pool(_built):
     block that is not released always shows, because its replacement comes out of the cache."""
     for p in [hs.dev_alloc(int(n)) for n in np.geomspace(1 << 10, 1 << 23, 160)]:
         hs.dev_free(p)
-
-
-@pytest.fixture(scope="module")
-def handle():
-    h = hs.Handle(0)
-    yield h
-    h.close()
 
 
 def _graph(base):

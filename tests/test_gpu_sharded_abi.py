@@ -7,24 +7,12 @@ the transports a one-GPU box can run: PEER (device copies), HOST (staged through
 import numpy as np
 import pytest
 
+from devcsr import built_gpu  # noqa: F401
+from devcsr import _graph, to_hs
 from helpers import assert_parity, assert_rmcl_step, po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-from test_gpu_parity import to_hs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
-
-
-def _graph(m, seed):
-    A = synth_csr(m, seed, 2)
-    ri = np.repeat(np.arange(A.rows, dtype=np.int32), np.diff(A.rowPtr))
-    return po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))
 
 
 @pytest.mark.parametrize("shards,transport", [(1, hs.XCHG_PEER), (2, hs.XCHG_PEER), (3, hs.XCHG_HOST), (5, hs.XCHG_PEER),

@@ -12,18 +12,12 @@ compressive product whose previous call undersized C.
 import numpy as np
 import pytest
 
+from devcsr import built_gpu  # noqa: F401
+from devcsr import to_hs
 from helpers import assert_parity, po, random_csr, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
-from test_gpu_parity import to_hs
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-    assert hs.device_count() >= 1
 
 
 def handle_with(monkeypatch, path, cfg=0):

@@ -11,17 +11,13 @@ import pytest
 
 import mcsr_ref as mr
 import reorder_ref as rr
+from devcsr import built  # noqa: F401
+from devcsr import _outs
 from helpers import ROOT, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 ERR_ARG = 2
 TWINS = ["", "_f64"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
 
 
 def kat():
@@ -45,6 +41,7 @@ def test_restatement_on_the_reference_vectors():
     assert rr.same_bits(mr.to_csr(M, 1e-9), A)               # r == 1, sorted rows: the matrix itself
 
 
+# per format: a matrix worked by hand for this format's layout (5 x 6 with a 4 x 3 corner)
 def _hand():
     """A is 5 x 6; r = c = 2, blockRows = 4, blockCols = 3, so bm = 2, bn = 2 (the last block column is ragged):
     row 0   (4, 1) (1, 2) (2, 3)
@@ -93,10 +90,6 @@ def test_restatement_edges():
 
 # ---- argument errors: no device is touched (the "device pointers" are never dereferenced) ----------------------------
 ONE = C.c_void_p(8)
-
-
-def _outs(n):
-    return [C.c_void_p(1) for _ in range(n)]
 
 
 @pytest.mark.parametrize("twin", TWINS)

@@ -6,16 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from devcsr import unpack
 from helpers import DATA, GOLDEN, assert_parity, po, summarize, synth_csr
 
 FX = np.load(os.path.join(GOLDEN, "fixtures.npz"))
 SM = np.load(os.path.join(GOLDEN, "synth_small.npz"))
 META = json.load(open(os.path.join(GOLDEN, "golden.json")))
-
-
-def unpack(z, prefix):
-    r, c = z[prefix + "_shape"]
-    return po.CSRHost(z[prefix + "_rowPtr"], z[prefix + "_colInd"], z[prefix + "_values"], int(r), int(c))
 
 
 def bit_equal(a, b):

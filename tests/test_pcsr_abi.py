@@ -11,6 +11,8 @@ import pytest
 
 import pcsr_ref as pr
 import reorder_ref as rr
+from devcsr import built  # noqa: F401
+from devcsr import _outs
 from helpers import ROOT, po, random_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -18,13 +20,8 @@ ERR_ARG, ERR_OVERFLOW = 2, 3
 TWINS = ["", "_f64"]
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _built():
-    import __graft_entry__ as ge
-    ge.build()
-
-
 # ---- the hand-worked pair --------------------------------------------------------------------------------------------
+# per format: a matrix worked by hand for this format's layout (3 x 5 for two column blocks)
 def _hand():
     """A is 3 x 5, c = 2, stride = 3:
     row 0    (4, 1.0) (0, 2.0) (3, 3.0)      unsorted
@@ -79,10 +76,6 @@ def test_restatement_blockwise_product_is_the_whole_product():
 
 # ---- argument errors: no device is touched (the "device pointers" are never dereferenced) ----------------------------
 ONE = C.c_void_p(8)
-
-
-def _outs(n=3):
-    return [C.c_void_p(1) for _ in range(n)]
 
 
 def _table(c, ptr=8, nnz=0):
@@ -205,7 +198,7 @@ def test_python_mirror_refuses_mismatches_before_device_work():
 def test_cpp_mirror_refuses_a_shape_mismatch_before_device_work():
     """tests/cpp/pcsr_check.cc --shape-check: PCSR::isEqual against another row count, column count and nnz"""
     cpp = os.path.join(ROOT, "tests", "cpp")
-    subprocess.check_call(["make", "-s", "-C", cpp, "-f", "Makefile.pcsr"])
+    subprocess.check_call(["make", "-s", "-C", cpp, "pcsr_check.x"])
     out = subprocess.run([os.path.join(cpp, "pcsr_check.x"), "--shape-check"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "refused" in out.stdout and "B_rows = 4" in out.stdout and "B_cols = 6" in out.stdout and "B_nnz = 6" in out.stdout

@@ -16,46 +16,15 @@ differsStats hip_csr_differsStats(A, C) with the reference's eight percents agai
              matrix downloaded whole (three arrays, what a gpuRmclIter(1) per iteration through the host moves one way)
              and the host loop of CSR::differsStats restated in numpy; the rowPtr-only download is timed as well.
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchkit import finish, hs, load, med, need_device, parser, rounded, take_turns
 
-from sparse_matrix_with_flops_amd import hipspgemm as hs  # noqa: E402
-from sparse_matrix_with_flops_amd import synth  # noqa: E402
-
-WORKLOADS = {
-    "synth_1m_16": lambda: synth.powerlaw_csr(1 << 20, 43, 2)[:3],          # the matrix bench.py times
-    "web_google_surrogate": lambda: synth.webgraph_csr(916428, 46)[:3],
-}
 REF_PERCENTS = [-30, -20, -5, 0, 5, 20, 30, 100]
 
 
-def clock(fn):
-    t0 = time.perf_counter()
-    out = fn()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def alternate(arms, reps, warmup):
-    """arms: {name: fn}; the arms take turns; -> ({name: [ms per repetition]}, {name: last result})"""
-    times, last = {k: [] for k in arms}, {}
-    for it in range(warmup + reps):
-        for name, fn in arms.items():
-            ms, last[name] = clock(fn)
-            if it >= warmup:
-                times[name].append(ms)
-    return times, last
-
-
 def summary(times):
-    return {k: {"ms": round(float(np.median(v)), 4), "runs_ms": [round(x, 4) for x in v]} for k, v in times.items()}
+    return {k: {"ms": med(v), "runs_ms": rounded(v)} for k, v in times.items()}
 
 
 def host_parity(X, Y, rel):
@@ -95,8 +64,9 @@ def diff_arms(h, dC, dOther, rel, reps, warmup):
     def host():
         return host_parity(*download(), rel)
     pair = download()
-    times, last = alternate({"hip_csr_diff": device, "download_and_host_compare": host, "download_only": download,
-                             "host_compare_only": lambda: host_parity(pair[0], pair[1], rel)}, reps, warmup)
+    # the arms' results are reports and host objects: nothing to free, the last of each is compared below
+    times, last = take_turns({"hip_csr_diff": device, "download_and_host_compare": host, "download_only": download,
+                              "host_compare_only": lambda: host_parity(pair[0], pair[1], rel)}, reps, warmup, free=None)
     d, (same, beyond) = last["hip_csr_diff"], last["download_and_host_compare"]
     device_same = d.rows_len_differ == 0 and d.only_a == 0 and d.only_b == 0 and d.beyond == 0
     if device_same != same:
@@ -109,9 +79,8 @@ def diff_arms(h, dC, dOther, rel, reps, warmup):
 
 
 def run(name, reps, warmup):
-    rp, ci, v = WORKLOADS[name]()
-    m = len(rp) - 1
-    hA = hs.CSR.from_arrays(rp, ci, v, m, m)
+    hA = load(name)
+    m = hA.rows
     h = hs.Handle(0)
     dA = hA.toGpuCSR()
     made = [dA]
@@ -142,8 +111,8 @@ def run(name, reps, warmup):
 
         def stats_rowptr():
             return host_differs_stats(hA.rowPtr, hs.d2h(dC.rowPtr, m + 1, np.int32), REF_PERCENTS)
-        times, last = alternate({"hip_csr_differsStats": stats_device, "download_matrix_and_host_loop": stats_whole,
-                                 "download_rowptr_and_host_loop": stats_rowptr}, reps, warmup)
+        times, last = take_turns({"hip_csr_differsStats": stats_device, "download_matrix_and_host_loop": stats_whole,
+                                  "download_rowptr_and_host_loop": stats_rowptr}, reps, warmup, free=None)
         if not (last["hip_csr_differsStats"] == last["download_matrix_and_host_loop"] == last["download_rowptr_and_host_loop"]):
             raise SystemExit(f"differsStats: the routes disagree: {last}")
         out["differsStats"] = summary(times)
@@ -158,22 +127,11 @@ def run(name, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = parser(__doc__, "compare_bench")
     ap.add_argument("--workloads", default="synth_1m_16,web_google_surrogate")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "compare_bench.json"))
     args = ap.parse_args()
-    if hs.device_count() < 1:
-        raise SystemExit("compare_bench.py needs a HIP device (there is no CPU fallback)")
-    res = {"tool": "compare_bench", "timing": "host clock around blocking calls, median", "reps": args.reps,
-           "warmup": args.warmup, "workloads": {}}
-    for name in args.workloads.split(","):
-        res["workloads"][name] = run(name, args.reps, args.warmup)
-    with open(args.out, "w") as f:                          # only after the routes agreed
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    need_device("compare_bench")
+    finish("compare_bench", args, {name: run(name, args.reps, args.warmup) for name in args.workloads.split(",")})   # the routes agreed
 
 
 if __name__ == "__main__":

@@ -50,9 +50,6 @@ def rand_csr(rng, rows, cols, kind):
     v = (rng.random(nnz) + 0.25).astype(np.float32)
     return po.CSRHost(rp.astype(np.int32), ci.astype(np.int32), v, rows, cols), bool(dup_ok)
 
-def to_hs(M):
-    return hs.CSR.from_arrays(M.rowPtr, M.colInd, M.values, M.rows, M.cols)
-
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 150
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
@@ -68,7 +65,7 @@ def main():
         B, dupB = rand_csr(rng, k, n, str(rng.choice(["sparse", "skew", "onebig", "dense", "tiny"])))
         want = po.sequential_spmm(A, B) if m and A.nnz and B.nnz else po.CSRHost(np.zeros(m + 1, np.int32), np.zeros(0, np.int32), np.zeros(0, np.float32), m, n)
         tag = f"case {case} (seed {seed}): A {m}x{k} nnz {A.nnz}, B {k}x{n} nnz {B.nnz}, nnzC {want.nnz}"
-        hA, hB = to_hs(A), to_hs(B)
+        hA, hB = (hs.CSR.from_arrays(M.rowPtr, M.colInd, M.values, M.rows, M.cols) for M in (A, B))
         dA, dB = hA.toGpuCSR(), hB.toGpuCSR()
         try:
             dC = hs.gpuSpMMWrapper(dA, dB, h)                                   # one-shot

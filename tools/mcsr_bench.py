@@ -19,19 +19,10 @@ to_csr       hip_mcsr_to_csr (drop_tol = 1e-9) of that result
 bcsr         beside them, per shape: hip_csr_to_bcsr / hip_bcsr_to_csr of the WHOLE reordered matrix, with its bytes
 d2d          beside them: the three CSR arrays copied device to device on the same stream
 """
-import argparse
-import json
-import os
-import sys
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-
-from sparse_matrix_with_flops_amd import hipspgemm as hs  # noqa: E402
-from bcsr_bench import WORKLOADS, Events, med  # noqa: E402
+from benchkit import HIP_EVENTS, WORKLOADS, Events, copy_buffers, d2d_arm, finish, hs, load, med, need_device, parser, rounded, \
+    round_trip_differs, take_turns
 
 
 def csr_bytes(m, nnz):
@@ -56,7 +47,7 @@ def parity_gate(h, dA, dSorted, r, c, k):
     try:
         hs.sort_rows_device(back, h)
         d = back.diff(dSorted, rel=0.0, abs=0.0, handle=h)
-        if back.nnz != dSorted.nnz or d.rows_len_differ or d.only_a or d.only_b or d.beyond:
+        if round_trip_differs(back, dSorted, d):
             raise SystemExit(f"parity gate, r={r} c={c} corner {k}: the round trip differs from the matrix: {d.as_dict()}")
         out = describe(x, dA.nnz)
         out["max_abs_err"] = d.max_abs_err
@@ -70,27 +61,15 @@ def time_shape(h, ev, dA, copy, r, c, ks, reps, warmup):
     """all arms of one tile shape in one rotation: the three corners, the whole-matrix BCSR and the copy"""
     held = {k: hs.MCSR(dA, r, c, k, k, h) for k in ks}
     whole = hs.BCSR(dA, r, c, h)
-
-    def d2d():
-        ev.copy(copy[0], dA.rowPtr, 4 * (dA.rows + 1))
-        ev.copy(copy[1], dA.colInd, 4 * dA.nnz)
-        ev.copy(copy[2], dA.values, 4 * dA.nnz)
-
     arms = {}
     for k in ks:
-        arms[f"to_mcsr_{k}"] = (lambda k=k: hs.MCSR(dA, r, c, k, k, h), lambda o: o.dispose())
-        arms[f"to_csr_{k}"] = (lambda k=k: held[k].to_csr(1e-9, h), lambda o: o.deviceDispose())
-    arms["to_bcsr"] = (lambda: hs.BCSR(dA, r, c, h), lambda o: o.dispose())
-    arms["bcsr_to_csr"] = (lambda: whole.to_csr(1e-9, h), lambda o: o.deviceDispose())
-    arms["d2d"] = (d2d, lambda o: None)
-    times = {name: [] for name in arms}
+        arms[f"to_mcsr_{k}"] = lambda k=k: hs.MCSR(dA, r, c, k, k, h)
+        arms[f"to_csr_{k}"] = lambda k=k: held[k].to_csr(1e-9, h)
+    arms["to_bcsr"] = lambda: hs.BCSR(dA, r, c, h)
+    arms["bcsr_to_csr"] = lambda: whole.to_csr(1e-9, h)
+    arms["d2d"] = d2d_arm(dA, copy, ev)
     try:
-        for it in range(warmup + reps):
-            for name, (fn, free) in arms.items():
-                ms, out = ev.ms(fn)
-                free(out)
-                if it >= warmup:
-                    times[name].append(ms)
+        times, _ = take_turns(arms, reps, warmup, timer=ev.ms)
         whole_bytes = tiles_bytes(whole.bm, whole.nnzb, r, c)
         whole_info = {"nnzb": whole.nnzb, "fill_percent": round(whole.nonzero_density(), 4), "bytes": whole_bytes,
                       "bytes_over_csr": round(whole_bytes / csr_bytes(dA.rows, dA.nnz), 4)}
@@ -101,7 +80,7 @@ def time_shape(h, ev, dA, copy, r, c, ks, reps, warmup):
 
     def arm(name):
         t = times[name]
-        return {"ms": med(t), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4), "runs_ms": [round(x, 4) for x in t]}
+        return {"ms": med(t), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4), "runs_ms": rounded(t)}
     out = {"r": r, "c": c, "whole_matrix_bcsr": dict(whole_info, to_bcsr=arm("to_bcsr"), to_csr=arm("bcsr_to_csr")),
            "d2d": arm("d2d"), "corners": {}}
     for k in ks:
@@ -110,20 +89,19 @@ def time_shape(h, ev, dA, copy, r, c, ks, reps, warmup):
 
 
 def run(name, shapes, ks, reps, warmup):
-    rp, ci, v = WORKLOADS[name]()
-    m = len(rp) - 1
-    hA = hs.CSR.from_arrays(rp, ci, v, m, m)
+    hA = load(name)
+    m = hA.rows
     h = hs.Handle(0)
     ev = Events(h.stream())
     d0 = hA.toGpuCSR()
     dA = dSorted = None
-    copy = [hs.dev_alloc(4 * (m + 1)), hs.dev_alloc(4 * hA.nnz), hs.dev_alloc(4 * hA.nnz)]
+    copy = copy_buffers(d0)
     try:
         P = d0.rowDescendingOrderPermutation(h)
         dA = d0.PMPt(P, h)                                  # heavy rows and columns first; rows unsorted
         dSorted = d0.PMPt(P, h)
         hs.sort_rows_device(dSorted, h)
-        lens = np.diff(rp)[P]
+        lens = np.diff(hA.rowPtr)[P]
         out = {"m": m, "nnz": hA.nnz, "longest_row": int(lens[0]), "reordering": "P = row_descending_permutation, PMPt",
                "row_length_at": {str(k): int(lens[k - 1]) for k in ks if k <= m}, "shapes": {}}
         gates = {(r, c, k): parity_gate(h, dA, dSorted, r, c, k) for r, c in shapes for k in ks}   # every gate before any time
@@ -146,25 +124,16 @@ def run(name, shapes, ks, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = parser(__doc__, "mcsr_bench")
     ap.add_argument("--workload", default="synth_1m_16", choices=sorted(WORKLOADS))
     ap.add_argument("--corners", default="4096,16384,65536")
     ap.add_argument("--shapes", default="2x2,4x4,8x8")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcsr_bench.json"))
     args = ap.parse_args()
     shapes = [tuple(int(x) for x in s.split("x")) for s in args.shapes.split(",")]
     ks = [int(x) for x in args.corners.split(",")]
-    if hs.device_count() < 1:
-        raise SystemExit("mcsr_bench.py needs a HIP device (there is no CPU fallback)")
-    res = {"tool": "mcsr_bench", "timing": "HIP events on the handle's stream around blocking calls, median", "reps": args.reps,
-           "warmup": args.warmup, "dtype": "float32",
-           "workloads": {args.workload: run(args.workload, shapes, ks, args.reps, args.warmup)}}
-    with open(args.out, "w") as f:                          # only after every gate has passed
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    need_device("mcsr_bench")
+    finish("mcsr_bench", args, {args.workload: run(args.workload, shapes, ks, args.reps, args.warmup)}, timing=HIP_EVENTS,
+           dtype="float32")
 
 
 if __name__ == "__main__":

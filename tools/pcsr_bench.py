@@ -21,63 +21,13 @@ per block    a separate pass with the big-row kernels' event timing on: hip_gpuS
              k_num_big (which takes the last bin's rows instead of k_num_bighash when C is narrow enough); the same
              for the whole product.
 """
-import argparse
-import json
-import os
-import sys
-import time
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchkit import copy_buffers, d2d_arm, finish, hs, load, med, need_device, parser, rounded, round_trip_differs, take_turns
 
-from sparse_matrix_with_flops_amd import hipspgemm as hs  # noqa: E402
-from sparse_matrix_with_flops_amd import synth  # noqa: E402
-
-WORKLOADS = {
-    "synth_1m_16": lambda: synth.powerlaw_csr(1 << 20, 43, 2)[:3],          # the matrix bench.py times
-    "web_google_surrogate": lambda: synth.webgraph_csr(916428, 46)[:3],
-}
 PHASES = ("ms_classify", "ms_symbolic", "ms_scan_alloc", "ms_numeric")
 K_SYM_BIG, K_NUM_BIG, K_NUM_BIGHASH = 8, 15, 16             # SPGEMM_K_* of include/spgemm_hip.h
 BIG_KERNELS = ("k_sym_big", "k_num_big", "k_num_bighash")   # the last bin's numeric kernel is k_num_big when C is narrow
-
-
-def clock(fn):
-    """-> (milliseconds of the blocking call, its result)"""
-    t0 = time.perf_counter()
-    out = fn()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def med(x):
-    return round(float(np.median(x)), 4)
-
-
-def alternate(arms, reps, warmup):
-    """arms: {name: fn -> object with deviceDispose() or None}; the arms take turns; -> {name: [ms per repetition]}"""
-    times = {k: [] for k in arms}
-    for it in range(warmup + reps):
-        for name, fn in arms.items():
-            ms, out = clock(fn)
-            if out is not None:
-                out.deviceDispose()
-            if it >= warmup:
-                times[name].append(ms)
-    return times
-
-
-def d2d_arm(M, copy):
-    """copies the three arrays of device CSR M into `copy` and waits for them"""
-    isz = M.dtype.itemsize
-
-    def run():
-        hs.d2d(copy[0], M.rowPtr, 4 * (M.rows + 1))
-        hs.d2d(copy[1], M.colInd, 4 * M.nnz)
-        hs.d2d(copy[2], M.values, isz * M.nnz)
-        hs.device_synchronize()
-    return run
 
 
 def parity_gate(h, dA, whole_sorted, c):
@@ -87,7 +37,7 @@ def parity_gate(h, dA, whole_sorted, c):
     try:
         hs.sort_rows_device(joined, h)
         d = joined.diff(whole_sorted, rel=1e-6, abs=0.0, handle=h)
-        if joined.nnz != whole_sorted.nnz or d.rows_len_differ or d.only_a or d.only_b or d.beyond:
+        if round_trip_differs(joined, whole_sorted, d):
             raise SystemExit(f"parity gate, c={c}: the blockwise product differs from the whole product: {d.as_dict()}")
         return {"max_abs_err": d.max_abs_err, "max_rel_err": d.max_rel_err}
     finally:
@@ -120,26 +70,23 @@ def per_block(h, dA, mats, reps, warmup):
 
 
 def one_block_count(h, dA, dC, c, reps, warmup):
-    m, n = dA.rows, dA.cols
     pB = hs.PCSR(dA, c, h)
     pC = pB.spmm_left(dA, h)
-    copyB = [hs.dev_alloc(4 * (m + 1)), hs.dev_alloc(4 * dA.nnz), hs.dev_alloc(4 * dA.nnz)]
-    copyC = [hs.dev_alloc(4 * (m + 1)), hs.dev_alloc(4 * dC.nnz), hs.dev_alloc(4 * dC.nnz)]
+    copyB, copyC = copy_buffers(dA), copy_buffers(dC)
     try:
         arms = {
             "split": lambda: hs.PCSR(dA, c, h), "d2d_B": d2d_arm(dA, copyB),
             "join": lambda: pC.join(h), "d2d_C": d2d_arm(dC, copyC),
             "hip_pcsr_spmm": lambda: pB.spmm_left(dA, h), "hip_gpuSpMM": lambda: hs.gpuSpMMWrapper(dA, dA, h),
         }
-        t = alternate(arms, reps, warmup)
+        t, _ = take_turns(arms, reps, warmup)
         out = {"stride": pB.stride, "block_nnz": [b.nnz for b in pB.blocks], "product_block_nnz": [b.nnz for b in pC.blocks]}
         for name, ceiling in (("split", "d2d_B"), ("join", "d2d_C")):
             out[name] = {"ms": med(t[name]), "d2d_ms": med(t[ceiling]), "ms_over_d2d": round(med(t[name]) / med(t[ceiling]), 2),
-                         "runs_ms": [round(x, 4) for x in t[name]], "d2d_runs_ms": [round(x, 4) for x in t[ceiling]]}
+                         "runs_ms": rounded(t[name]), "d2d_runs_ms": rounded(t[ceiling])}
         out["product"] = {"hip_pcsr_spmm_ms": med(t["hip_pcsr_spmm"]), "hip_gpuSpMM_ms": med(t["hip_gpuSpMM"]),
                           "blockwise_over_whole": round(med(t["hip_pcsr_spmm"]) / med(t["hip_gpuSpMM"]), 3),
-                          "hip_pcsr_spmm_runs_ms": [round(x, 4) for x in t["hip_pcsr_spmm"]],
-                          "hip_gpuSpMM_runs_ms": [round(x, 4) for x in t["hip_gpuSpMM"]]}
+                          "hip_pcsr_spmm_runs_ms": rounded(t["hip_pcsr_spmm"]), "hip_gpuSpMM_runs_ms": rounded(t["hip_gpuSpMM"])}
         mats = {f"block {b}": pB.block(b) for b in range(c)}
         mats["whole"] = dA
         out["per_block"] = per_block(h, dA, mats, reps, warmup)
@@ -156,14 +103,12 @@ def one_block_count(h, dA, dC, c, reps, warmup):
 
 
 def run(name, counts, reps, warmup):
-    rp, ci, v = WORKLOADS[name]()
-    m = len(rp) - 1
-    hA = hs.CSR.from_arrays(rp, ci, v, m, m)
+    hA = load(name)
     h = hs.Handle(0)
     dA = hA.toGpuCSR()
     dC = hs.gpuSpMMWrapper(dA, dA, h)
     try:
-        out = {"m": m, "nnzA": hA.nnz, "nnzC": dC.nnz, "longest_row": int(np.diff(rp).max()), "parity": {}, "blocks": {}}
+        out = {"m": hA.rows, "nnzA": hA.nnz, "nnzC": dC.nnz, "longest_row": int(np.diff(hA.rowPtr).max()), "parity": {}, "blocks": {}}
         hs.sort_rows_device(dC, h)
         for c in counts:                                     # every gate before any time
             out["parity"][str(c)] = parity_gate(h, dA, dC, c)
@@ -178,24 +123,13 @@ def run(name, counts, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = parser(__doc__, "pcsr_bench")
     ap.add_argument("--workloads", default="synth_1m_16,web_google_surrogate")
     ap.add_argument("--blocks", default="1,2,4,8")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pcsr_bench.json"))
     args = ap.parse_args()
-    if hs.device_count() < 1:
-        raise SystemExit("pcsr_bench.py needs a HIP device (there is no CPU fallback)")
+    need_device("pcsr_bench")
     counts = [int(x) for x in args.blocks.split(",")]
-    res = {"tool": "pcsr_bench", "timing": "host clock around blocking calls, median", "reps": args.reps,
-           "warmup": args.warmup, "workloads": {}}
-    for name in args.workloads.split(","):
-        res["workloads"][name] = run(name, counts, args.reps, args.warmup)
-    with open(args.out, "w") as f:                          # only after every gate has passed
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    finish("pcsr_bench", args, {name: run(name, counts, args.reps, args.warmup) for name in args.workloads.split(",")})
 
 
 if __name__ == "__main__":

@@ -22,56 +22,18 @@ permuTest    correctTests/permuTest.cc on the device: hip_gpuSpMM of A*A for thr
              back with PtMP and row-sorted, must have the structure hash of the unpermuted product and value checksums
              within 1e-6 relative; if it fails the tool fails and writes no times.
 """
-import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from benchkit import ROOT, copy_buffers, d2d_arm, finish, hs, load, med, need_device, parser, release, rounded, take_turns
+
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-
 from helpers import structure_hash, value_checksums  # noqa: E402
-from sparse_matrix_with_flops_amd import hipspgemm as hs  # noqa: E402
-from sparse_matrix_with_flops_amd import synth  # noqa: E402
 
-WORKLOADS = {
-    "synth_1m_16": lambda: synth.powerlaw_csr(1 << 20, 43, 2)[:3],          # the matrix bench.py times
-    "web_google_surrogate": lambda: synth.webgraph_csr(916428, 46)[:3],
-}
 PEAK_HBM_GBPS = 8000.0                                      # MI355X HBM3E peak (DESIGN.md section 8)
 PHASES = ("ms_classify", "ms_symbolic", "ms_scan_alloc", "ms_numeric")
-
-
-def clock(fn):
-    """-> (milliseconds of the blocking call, its result)"""
-    t0 = time.perf_counter()
-    out = fn()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def free_all(ptrs):
-    for p in ptrs:
-        hs.dev_free(p)
-
-
-def alternate(arms, reps, warmup):
-    """arms: {name: fn -> device pointers to free}; the arms take turns; -> {name: [ms per repetition]}"""
-    times = {k: [] for k in arms}
-    for it in range(warmup + reps):
-        for name, fn in arms.items():
-            ms, ptrs = clock(fn)
-            free_all(ptrs)
-            if it >= warmup:
-                times[name].append(ms)
-    return times
-
-
-def med(x):
-    return round(float(np.median(x)), 4)
 
 
 def algorithmic_bytes(m, n, nnz):
@@ -89,37 +51,29 @@ def algorithmic_bytes(m, n, nnz):
 def primitives(h, dA, P, Pt, reps, warmup):
     m, n, nnz = dA.rows, dA.cols, dA.nnz
     dP, dPt = hs.h2d(P), hs.h2d(Pt)
-    copy = [hs.dev_alloc(4 * (m + 1)), hs.dev_alloc(4 * nnz), hs.dev_alloc(4 * nnz)]
+    copy = copy_buffers(dA)
 
     # a device-to-device hipMemcpy may return before the copy has run: the device synchronise makes the arm as blocking
-    # as the entry points it is compared with
-    def d2d_csr():
-        hs.d2d(copy[0], dA.rowPtr, 4 * (m + 1))
-        hs.d2d(copy[1], dA.colInd, 4 * nnz)
-        hs.d2d(copy[2], dA.values, 4 * nnz)
-        hs.device_synchronize()
-        return []
-
+    # as the entry points it is compared with (benchkit.d2d_arm does the same for the three arrays)
     def d2d_rowptr():
         hs.d2d(copy[0], dA.rowPtr, 4 * (m + 1))
         hs.device_synchronize()
-        return []
 
     def permute(rowSrc, colMap):
         return lambda: list(hs.csr_permute_raw(h, m, n, nnz, dA.rowPtr, dA.colInd, dA.values, rowSrc, colMap))
     arms = {
-        "d2d_csr": d2d_csr, "d2d_rowptr": d2d_rowptr,
+        "d2d_csr": d2d_arm(dA, copy), "d2d_rowptr": d2d_rowptr,
         "PM": permute(dP, None), "MP": permute(None, dP), "PMPt": permute(dP, dPt),
         "transpose": lambda: list(hs.csr_transpose_raw(h, m, n, nnz, dA.rowPtr, dA.colInd, dA.values)),
         "rowDescendingOrderPermutation": lambda: [hs.row_descending_permutation_raw(h, m, dA.rowPtr)],
     }
     try:
-        t = alternate(arms, reps, warmup)
+        t, _ = take_turns(arms, reps, warmup)
     finally:
-        free_all(copy + [dP, dPt])
+        release(copy + [dP, dPt])
     nbytes = algorithmic_bytes(m, n, nnz)
     out = {"d2d_csr_ms": med(t["d2d_csr"]), "d2d_rowptr_ms": med(t["d2d_rowptr"]),
-           "d2d_csr_runs_ms": [round(x, 4) for x in t["d2d_csr"]], "d2d_rowptr_runs_ms": [round(x, 4) for x in t["d2d_rowptr"]]}
+           "d2d_csr_runs_ms": rounded(t["d2d_csr"]), "d2d_rowptr_runs_ms": rounded(t["d2d_rowptr"])}
     # a copy reads and writes every byte once: a time below what PEAK_HBM allows has not waited for the copy
     copied = 2 * (4 * (m + 1) + 8 * nnz)
     out["d2d_csr_GBps"] = round(copied / (out["d2d_csr_ms"] * 1e-3) / 1e9, 1)
@@ -129,7 +83,7 @@ def primitives(h, dA, P, Pt, reps, warmup):
         ceiling = out["d2d_rowptr_ms"] if name == "rowDescendingOrderPermutation" else out["d2d_csr_ms"]
         ms = med(t[name])
         out[name] = {"ms": ms, "bytes": int(nbytes[name]), "GBps": round(nbytes[name] / (ms * 1e-3) / 1e9, 1),
-                     "d2d_ms": ceiling, "ms_over_d2d": round(ms / ceiling, 2), "runs_ms": [round(x, 4) for x in t[name]]}
+                     "d2d_ms": ceiling, "ms_over_d2d": round(ms / ceiling, 2), "runs_ms": rounded(t[name])}
     return out
 
 
@@ -147,13 +101,13 @@ def transpose_gate(h, hA, dA, reps, warmup):
         a, b = new(), old()                                                   # same bits first
         same = all(np.array_equal(hs.d2h(x, cnt, np.int32), hs.d2h(y, cnt, np.int32))
                    for x, y, cnt in zip(a, b, (n + 1, nnz, nnz)))
-        free_all(a + b)
+        release(a + b)
         if not same:
             raise SystemExit("transpose gate: hip_csr_transpose and the hip_coo_to_csr route disagree")
-        t = alternate({"hip_csr_transpose": new, "coo_to_csr_route": old}, reps, warmup)
+        t, _ = take_turns({"hip_csr_transpose": new, "coo_to_csr_route": old}, reps, warmup)
     finally:
         hs.dev_free(dRow)
-    out = {k: {"ms": med(v), "runs_ms": [round(x, 4) for x in v]} for k, v in t.items()}
+    out = {k: {"ms": med(v), "runs_ms": rounded(v)} for k, v in t.items()}
     out["new_over_old"] = round(out["hip_csr_transpose"]["ms"] / out["coo_to_csr_route"]["ms"], 3)
     out["radix_passes"] = {"hip_csr_transpose": -(-max(1, int(n - 1).bit_length()) // 8),
                            "coo_to_csr_route": -(-(max(1, int(n - 1).bit_length()) + int(m - 1).bit_length()) // 8)}
@@ -206,7 +160,7 @@ def permu_test(h, dA, orders, reps, warmup):
                 d.deviceDispose()
     out = {"parity": "structure hash equal, checksums within 1e-6 relative"}
     for name, sts in runs.items():
-        out[name] = {"ms_total": med([s["ms_total"] for s in sts]), "runs_ms_total": [round(s["ms_total"], 4) for s in sts],
+        out[name] = {"ms_total": med([s["ms_total"] for s in sts]), "runs_ms_total": rounded(s["ms_total"] for s in sts),
                      "phases_ms": {k: med([s[k] for s in sts]) for k in PHASES}, "bin_rows": sts[-1]["bin_rows"],
                      "nnzC": sts[-1]["nnzC"], "P": sts[-1]["total_flops"]}
     base = out["as_generated"]["ms_total"]
@@ -216,16 +170,15 @@ def permu_test(h, dA, orders, reps, warmup):
 
 
 def run(name, reps, warmup):
-    rp, ci, v = WORKLOADS[name]()
-    m = len(rp) - 1
-    hA = hs.CSR.from_arrays(rp, ci, v, m, m)
+    hA = load(name)
+    m = hA.rows
     h = hs.Handle(0)
     dA = hA.toGpuCSR()
     try:
         P = np.random.default_rng(2024).permutation(m).astype(np.int32)
         Pt = hs.permutation_transpose(P, h)
         Pdesc = dA.rowDescendingOrderPermutation(h)
-        lens = np.diff(rp)
+        lens = np.diff(hA.rowPtr)
         assert np.array_equal(Pdesc, np.argsort(-lens.astype(np.int64), kind="stable"))
         out = {"m": m, "nnzA": hA.nnz, "longest_row": int(lens.max())}
         out["permuTest"] = permu_test(h, dA, {"as_generated": None, "random": P, "descending_length": Pdesc}, reps, warmup)
@@ -238,22 +191,11 @@ def run(name, reps, warmup):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--reps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap = parser(__doc__, "reorder_bench")
     ap.add_argument("--workloads", default="synth_1m_16,web_google_surrogate")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "reorder_bench.json"))
     args = ap.parse_args()
-    if hs.device_count() < 1:
-        raise SystemExit("reorder_bench.py needs a HIP device (there is no CPU fallback)")
-    res = {"tool": "reorder_bench", "timing": "host clock around blocking calls, median", "reps": args.reps,
-           "warmup": args.warmup, "workloads": {}}
-    for name in args.workloads.split(","):
-        res["workloads"][name] = run(name, args.reps, args.warmup)
-    with open(args.out, "w") as f:                          # only after every gate has passed
-        json.dump(res, f, indent=1)
-        f.write("\n")
-    print(json.dumps(res))
+    need_device("reorder_bench")
+    finish("reorder_bench", args, {name: run(name, args.reps, args.warmup) for name in args.workloads.split(",")})
 
 
 if __name__ == "__main__":
