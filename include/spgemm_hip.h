@@ -317,6 +317,54 @@ int spgemm_hip_debug_fail_next(spgemm_handle* h, int count);
 int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const float* dVal,
                    int flags, int** dIA, int** dJA, float** dA, int* nnzOut);
 
+/* ---- the text in front of that step: edge lines "from to [value]" -> device COO, a file -> device CSR ---------------------
+ * Replaces, for float values and line-oriented files, the text half of COO::readSNAPFile (nlibs/COO.cc:48-158): the lines
+ * are cut and converted by kernels, with the conversions sscanf("%d%d%f") performs, bit for bit.  A line holding a number
+ * the device scanner does not promise to convert like the C library (csrc/edge_scan.hpp: 19 or more digits in an index;
+ * inf / nan / hex; more than 2^53 in the digits or a decimal exponent beyond +-22; a value half-way between two floats) is
+ * "slow": the host parses exactly those lines with strtol / strtol / strtof and stores their triplets.
+ * The counting rule is the reference's: at most `declared` lines are read (declared < 0 is 0), reading stops at the first
+ * line with fewer than two fields, entries = min(declared, lines, first such line); a missing value is 1.0; lines at or
+ * beyond `declared` are never parsed.  A line ends at '\n'; a NUL byte inside a line ends that line's string; a last line
+ * without '\n' counts.  (fgets cuts lines at 1024 characters in the reference; here, as in COO::readSNAPFile of the
+ * mirror, a line ends at its newline.)
+ * Not covered (they stay on the host loader): symmetric MatrixMarket files (a token stream, not lines), QValue double,
+ * texts above 2 GiB.
+ * h == NULL = the default handle; a call returns after the device work has completed; st may be NULL.  Argument checks
+ * (a null output, null text with nbytes > 0, an unknown flag bit, a misaligned device text -> SPGEMM_ERR_ARG;
+ * nbytes > INT32_MAX -> SPGEMM_ERR_OVERFLOW) run before any device is touched.  On any error the outputs are NULL, the
+ * counts 0, nothing stays allocated, the handle stays usable. */
+#define SPGEMM_EDGES_ONE_BASED 1   /* MatrixMarket: both indices minus 1 */
+#define SPGEMM_EDGES_TRANSPOSE 2   /* isTrans: row = second number, col = first */
+typedef struct spgemm_edge_stats {
+  long long lines;          /* lines in the text */
+  long long first_bad_line; /* -1 if none among the lines looked at */
+  int entries, slow_lines;  /* slow_lines: parsed on the host */
+  float ms_upload, ms_split, ms_parse, ms_slow, ms_total;   /* wall clock: text to the device; count + scan + line starts;
+                               the parse kernel; the slow lines; all of it (hip_read_edge_file: without the file read and
+                               without hip_coo_to_csr) */
+} spgemm_edge_stats;
+
+/* pure host, no device: banner / comment lines / size line, as readSNAPFile reads them (nlibs/COO.cc:56-128).  The first
+ * line, if it starts with '%' and has 5 tokens, is a MatrixMarket banner (*one_based = 1; *symmetric = its 5th token is
+ * "symmetric", any case).  Lines starting with '#' or '%' are skipped; the next line holds 2 numbers (rows = cols = a,
+ * declared = b) or 3 (rows, cols, declared); *data_offset = the byte behind that line.  No such line -> SPGEMM_ERR_INPUT
+ * (the reference exits).  An empty text or only comments: sizes and offset zero, SPGEMM_OK. */
+int hip_edge_text_header(const char* text, size_t nbytes, int* rows, int* cols, int* declared,
+                         int* one_based, int* symmetric, size_t* data_offset);
+/* dText: the edge lines in DEVICE memory, 16-byte aligned (not modified).  *dRow, *dCol, *dVal: library pool arrays with
+ * room for *entries triplets in line order (release with spgemm_hip_free; never NULL on success). */
+int hip_parse_edge_lines(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
+                         int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st);
+/* the same for HOST text (any alignment): uploaded through the pinned lanes hip_CSR_SpMM uses */
+int hip_parse_edge_text (spgemm_handle* h, const char* text,  size_t nbytes, int declared, int flags,
+                         int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st);
+/* readSNAPFile(path, isTrans) + hip_coo_to_csr(cooFlags) with the triplets never on the host: reads the file once, parses
+ * its header, hip_parse_edge_text on the rest (ONE_BASED from the banner, TRANSPOSE from isTrans), hip_coo_to_csr.
+ * A symmetric MatrixMarket file -> SPGEMM_ERR_INPUT; an unreadable file -> SPGEMM_ERR_ARG. */
+int hip_read_edge_file  (spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
+                         int** dIA, int** dJA, float** dA, int* nnz, spgemm_edge_stats* st);
+
 /* ---- workload statistics ----------------------------------------------------
  * std::vector<int> flopsStats(IA, JA, IB, JB, m) (nlibs/tools/stats.cc:29-55, pushToStats :3-12): 13 buckets of the
  * per-row product count of A*B; bucket i counts rows with 2^(i-1) < flops <= 2^i, bucket 0 rows with flops <= 1,

@@ -1,7 +1,7 @@
-// What the device CSR format headers share (coo, reorder, compare, pcsr, bcsr, mcsr): the call prologue and the per-call
+// What the device CSR format headers share (coo, reorder, compare, pcsr, bcsr, mcsr, edges): the call prologue and the per-call
 // Scratch, the validation of a CSR with its single flag read-back, the library's scan with its 64-bit total, the stable
 // LSD radix sort, the entry-dealing helpers (row search, tile rows, lower bound) and the staged tile copy.
-// Included in spgemm_hip.hip ahead of the six headers (uses its pool / error helpers and the k_scan_* kernels).
+// Included in spgemm_hip.hip ahead of those headers (uses its pool / error helpers and the k_scan_* kernels).
 #pragma once
 
 namespace csrdev {

@@ -275,3 +275,34 @@ CSR COO::toGpuCSR(int flags) const {
   if (rc) { printf("%s\n", spgemm_hip_last_error()); exit(EXIT_FAILURE); }
   return d;
 }
+
+// text -> device CSR with the parse on the device (hip_read_edge_file).  Only the banner says whether the file is a
+// symmetric MatrixMarket file, so its first line is probed first; such a file takes the host path.
+spgemm_edge_stats COO::lastGpuParse = {};
+
+CSR COO::readSNAPFileToGpuCSR(const char fname[], bool isTrans, int flags) {
+  FILE* fp = fopen(fname, "rb");
+  if (!fp) { printf("Failed to open file %s\n", fname); exit(-1); }
+  char first[1024];
+  const size_t got = fread(first, 1, sizeof(first), fp);
+  fclose(fp);
+  const char* nl = (const char*)memchr(first, '\n', got);
+  int r = 0, c = 0, declared = 0, oneBased = 0, symmetric = 0;
+  size_t off = 0;
+  (void)hip_edge_text_header(first, nl ? (size_t)(nl - first) + 1 : got, &r, &c, &declared, &oneBased, &symmetric, &off);
+  lastGpuParse = spgemm_edge_stats{};
+  if (symmetric) {
+    COO coo;
+    coo.readSNAPFile(fname, isTrans);
+    CSR d = coo.toGpuCSR(flags);
+    coo.dispose();
+    return d;
+  }
+  CSR d;
+  if (hip_read_edge_file(NULL, fname, isTrans ? 1 : 0, flags, &d.rows, &d.cols, &d.rowPtr, &d.colInd, &d.values, &d.nnz,
+                         &lastGpuParse)) {
+    printf("%s: %s\n", fname, spgemm_hip_last_error());
+    exit(EXIT_FAILURE);
+  }
+  return d;
+}

@@ -3,6 +3,7 @@
 #ifndef SMF_COO_H_
 #define SMF_COO_H_
 #include "CSR.h"
+#include "../../../include/spgemm_hip.h"   // spgemm_edge_stats
 
 class COO {
  public:
@@ -27,5 +28,10 @@ class COO {
   // the same three steps on the device in one call (hip_coo_to_csr): upload the triplets in file order, get a
   // DEVICE CSR back.  flags: SPGEMM_COO_DEDUPE | SPGEMM_COO_SELF_LOOPS | SPGEMM_COO_ROW_NORMALISE | SPGEMM_COO_ABS
   CSR toGpuCSR(int flags) const;
+  // readSNAPFile + toGpuCSR(flags) with the text parsed on the device (hip_read_edge_file): the file goes up as text, a
+  // DEVICE CSR comes back, the triplets never exist on the host.  A symmetric MatrixMarket file (a token stream) takes
+  // the host path above.  lastGpuParse: the latest device parse (zeroed by the host path).
+  static CSR readSNAPFileToGpuCSR(const char fname[], bool isTrans, int flags);
+  static spgemm_edge_stats lastGpuParse;
 };
 #endif

@@ -2124,7 +2124,12 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // ------------------------------------------------------------------------------------------------
 #include "mcsr_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the six headers above
+// ------------------------------------------------------------------------------------------------
+// edge-list text -> COO triplets: the parse in front of hip_coo_to_csr
+// ------------------------------------------------------------------------------------------------
+#include "edges_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the seven headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@ Mirrors (reference file:line):
                               struct BCSR                      nlibs/BCSR.h:6-64, nlibs/BCSR.cc:3-116
   MCSR.from_csr(dM, r, c, blockRows, blockCols) / to_csr / nonzero_density
                               struct MCSR                      nlibs/MCSR.h:6-9, nlibs/MCSR.cc:58-92
+  edge_text_header(data) / parse_edge_text(data, declared) / read_edge_file(path, isTrans, flags)
+                              COO::readSNAPFile (the text)     nlibs/COO.cc:48-158   (float values; parsed on the device)
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -65,6 +67,7 @@ EXPORTS = [
     "hip_pcsr_spmm", "hip_pcsr_spmm_f64",
     "hip_csr_to_bcsr", "hip_csr_to_bcsr_f64", "hip_bcsr_to_csr", "hip_bcsr_to_csr_f64",
     "hip_csr_to_mcsr", "hip_csr_to_mcsr_f64", "hip_mcsr_to_csr", "hip_mcsr_to_csr_f64",
+    "hip_edge_text_header", "hip_parse_edge_lines", "hip_parse_edge_text", "hip_read_edge_file",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -88,6 +91,16 @@ class CsrDiff(C.Structure):
                 ("first_only_row", C.c_int), ("beyond", C.c_longlong), ("first_beyond_row", C.c_int),
                 ("max_abs_err", C.c_double), ("max_rel_err", C.c_double), ("max_abs_only_a", C.c_double),
                 ("max_abs_only_b", C.c_double), ("sum_sq", C.c_double)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class EdgeStats(C.Structure):
+    """spgemm_edge_stats: what hip_parse_edge_lines / hip_parse_edge_text / hip_read_edge_file report"""
+    _fields_ = [("lines", C.c_longlong), ("first_bad_line", C.c_longlong), ("entries", C.c_int), ("slow_lines", C.c_int),
+                ("ms_upload", C.c_float), ("ms_split", C.c_float), ("ms_parse", C.c_float), ("ms_slow", C.c_float),
+                ("ms_total", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -208,6 +221,11 @@ def lib():
         L.hip_mcsr_to_csr.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] * 2 + \
             [C.c_double] + [C.POINTER(C.c_void_p)] * 3 + [_I]
         L.hip_mcsr_to_csr_f64.argtypes = L.hip_mcsr_to_csr.argtypes
+        L.hip_edge_text_header.argtypes = [C.c_char_p, C.c_size_t, _I, _I, _I, _I, _I, C.POINTER(C.c_size_t)]
+        edge_out = [C.POINTER(C.c_void_p)] * 3 + [_I, C.POINTER(EdgeStats)]
+        L.hip_parse_edge_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + edge_out
+        L.hip_parse_edge_text.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int] + edge_out
+        L.hip_read_edge_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _I, _I] + edge_out
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1483,3 +1501,92 @@ class MCSR:
         if self.remainder is not None:
             self.remainder.deviceDispose()
             self.remainder = None
+
+
+# ---------------------------------------------------------------------------------------------
+# edge-list text (include/spgemm_hip.h "the text in front of that step"): lines "from to [value]" -> device COO, a file
+# -> device CSR; the text half of COO::readSNAPFile (nlibs/COO.cc:48-158) on the device
+# ---------------------------------------------------------------------------------------------
+EDGES_ONE_BASED, EDGES_TRANSPOSE = 1, 2
+
+
+def _edge_bytes(data, what):
+    """the text as bytes; anything that is not bytes-like is refused before any device work"""
+    if isinstance(data, str) or not isinstance(data, (bytes, bytearray, memoryview)):
+        raise SpgemmError(f"{what}: the text must be bytes, not {type(data).__name__}")
+    return bytes(data)
+
+
+def _edge_flags(flags):
+    flags = int(flags)
+    if flags & ~(EDGES_ONE_BASED | EDGES_TRANSPOSE):
+        raise SpgemmError(f"unknown edge flags 0x{flags:x}: EDGES_ONE_BASED | EDGES_TRANSPOSE")
+    return flags
+
+
+def edge_text_header(data):
+    """hip_edge_text_header (pure host): the banner, comment lines and size line of a SNAP / MatrixMarket text ->
+    {rows, cols, declared, one_based, symmetric, data_offset}.  A text without a size line raises."""
+    data = _edge_bytes(data, "edge_text_header")
+    rows, cols, declared, one, sym, off = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    _check(lib().hip_edge_text_header(data, len(data), C.byref(rows), C.byref(cols), C.byref(declared), C.byref(one),
+                                      C.byref(sym), C.byref(off)), "hip_edge_text_header")
+    return {"rows": rows.value, "cols": cols.value, "declared": declared.value, "one_based": bool(one.value),
+            "symmetric": bool(sym.value), "data_offset": int(off.value)}
+
+
+def parse_edge_lines_raw(handle, dText, nbytes, declared, flags=0):
+    """hip_parse_edge_lines on a raw device pointer (16-byte aligned text) -> (dRow, dCol, dVal, entries, stats dict);
+    the three arrays come from the library pool (release with dev_free)."""
+    flags = _edge_flags(flags)
+    out, st = _CsrOut(), EdgeStats()
+    _check(lib().hip_parse_edge_lines(_hp(handle), C.c_void_p(dText), int(nbytes), int(declared), flags, *out.refs(),
+                                      C.byref(st)), "hip_parse_edge_lines")
+    return out.values() + (st.as_dict(),)
+
+
+class EdgeTriplets:
+    """device COO triplets in line order, as hip_parse_edge_text leaves them: row, col (int32) and val (float32) device
+    pointers, their count `entries` and the call's `stats`"""
+
+    def __init__(self, row, col, val, entries, stats):
+        self.row, self.col, self.val, self.entries, self.stats = row, col, val, int(entries), stats
+
+    def download(self):
+        """-> (row, col, val) numpy arrays of `entries` elements"""
+        return (d2h(self.row, self.entries, np.int32), d2h(self.col, self.entries, np.int32),
+                d2h(self.val, self.entries, np.float32))
+
+    def dispose(self):
+        for p in (self.row, self.col, self.val):
+            dev_free(p)
+        self.row = self.col = self.val = None
+
+
+def parse_edge_text(data, declared, one_based=False, transpose=False, handle=None):
+    """hip_parse_edge_text: host bytes holding edge lines -> EdgeTriplets on the device.  At most `declared` lines are
+    read; one_based subtracts 1 from both indices (MatrixMarket), transpose swaps them (isTrans)."""
+    data = _edge_bytes(data, "parse_edge_text")
+    flags = (EDGES_ONE_BASED if one_based else 0) | (EDGES_TRANSPOSE if transpose else 0)
+    out, st = _CsrOut(), EdgeStats()
+    _check(lib().hip_parse_edge_text(_hp(handle), data, len(data), int(declared), flags, *out.refs(), C.byref(st)),
+           "hip_parse_edge_text")
+    r, c, v, n = out.values()
+    return EdgeTriplets(r, c, v, n, st.as_dict())
+
+
+def read_edge_file(path, isTrans=True, flags=COO_DEDUPE, handle=None):
+    """hip_read_edge_file: COO::readSNAPFile(path, isTrans) + hip_coo_to_csr(flags) without the triplets ever on the host
+    -> device `CSR` (its .edge_stats: the parse's stats).  A symmetric MatrixMarket file raises (use the host loader)."""
+    if not isinstance(path, (str, bytes, os.PathLike)):
+        raise SpgemmError(f"read_edge_file: path must be a str, bytes or os.PathLike, not {type(path).__name__}")
+    flags = int(flags)
+    if flags & ~(COO_DEDUPE | COO_SELF_LOOPS | COO_ROW_NORMALISE | COO_ABS):
+        raise SpgemmError(f"unknown COO flags 0x{flags:x}")
+    out, st, rows, cols = _CsrOut(), EdgeStats(), C.c_int(), C.c_int()
+    _check(lib().hip_read_edge_file(_hp(handle), os.fsencode(path), int(bool(isTrans)), flags, C.byref(rows), C.byref(cols),
+                                    *out.refs(), C.byref(st)), "hip_read_edge_file")
+    ia, ja, av, nnz = out.values()
+    M = CSR(av, ja, ia, rows.value, cols.value, nnz, True)
+    M.edge_stats = st.as_dict()
+    return M
