@@ -302,6 +302,14 @@ int spgemm_hip_rmcl_devices_used(void);
  * tests make one rank of a multi-rank group fail) */
 int spgemm_hip_debug_fail_next(spgemm_handle* h, int count);
 
+/* test hook: how the latest product on this handle split its rows of more than 4096 products (n > 262144 columns, float)
+ * between the direct kernel, which keeps only a row's repeated columns in its table, and the multi-pass hash kernel; the
+ * re-hits a row may log and still take the direct kernel; the ints of one block's region of the re-hit log (0: no log yet).
+ * SPGEMM_BIGDIRECT=0 (read at handle creation) sends every such row to the hash kernel, and so does a product with fewer such
+ * rows than SPGEMM_BD_MINROWS (default: the number of CUs; the tests set 1); SPGEMM_RLREGION=<ints> fixes the region size
+ * (tests fill a region with it). */
+int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows, int* fallback_rows, int* rehit_cap, int* region_ints);
+
 /* ---- the step in front of the path: COO -> CSR on device arrays -------------
  * Replaces COO::addSelfLoopIfNeeded (nlibs/COO.cc:160-188), COO::makeOrdered / orderedAndDuplicatesRemoving
  * (nlibs/COO.cc:222-266: std::sort on (row,col), duplicates summed), COO::toCSR (nlibs/COO.cc:268-291),

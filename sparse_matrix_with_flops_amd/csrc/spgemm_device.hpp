@@ -1565,6 +1565,9 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
 //              LDS float array addressed by rank (no probing, sorted output)
 //   numeric B: any n: 128 KB LDS hash table; rows with more distinct columns than one table holds take
 //              several passes, each pass owning the columns of one hash class
+//   numeric C: n > BIG_WC, rows whose repeated columns the symbolic pass logged: 8 waves per row, a small table for
+//              the repeated columns only, every other product stored straight to C (k_num_bigdirect); the rows it
+//              cannot take stay with numeric B
 // ------------------------------------------------------------------------------------------------
 #ifndef SMF_BIG_NW
 #define SMF_BIG_NW 16
@@ -1588,11 +1591,25 @@ constexpr int BH_CAP = 11264;                  // distinct columns per hash pass
 constexpr int BH_CAP_MAX = 12288;              // SPGEMM_BHCAP may raise the cap to this (load 0.74)
 constexpr int BH_SPILL = 1 << 18;              // (col,val) pairs a multi-pass row may park in HBM per block (2 MB)
 constexpr int BH_MAXCLS = 32;                  // hash classes (passes) with their own parking region
+// direct big-row kernel (k_num_bigdirect): the symbolic pass logs every product that lands on a column its row has already
+// seen (a "re-hit"); only those columns get a table slot, every other product is stored straight to C.
+#ifndef SMF_BD_U
+#define SMF_BD_U 4
+#endif
+constexpr int BD_U = SMF_BD_U;                  // rounds in flight per wave (read-only probes: no CAS chains to keep short)
+constexpr int BD_MIN_SLOTS = 1024;             // smallest table of a row (a row without re-hits still sweeps it)
+// re-hits a row may log and still take the direct kernel with a table of S slots: the distinct repeated columns are at most
+// the re-hits, so the table is never more than 7/8 full and a probe always meets an empty slot
+__host__ __device__ constexpr int bd_cap(int S) { return S / 8 * 7; }
+constexpr int RL_ROW_BUDGET = 2048;            // log ints per big row when the workspace is sized (see grow_rehit_log)
+constexpr int RL_MIN_REGION = 1 << 15;         // ... and the smallest region of a block
 
 struct BigSymShared {
   unsigned bitmap[SYM_WORDS];
   WalkStageN<BIG_NW> st;
   int red[BIG_NW];
+  int logCnt;                    // LOG: re-hits of the current row so far; the row's region ran out (or the row passed rlCap)
+  int logOvf;
 };
 constexpr int BIG_GROUPS = BIG_WORDS / WAVE;   // 128 groups of 64 bitmap words
 constexpr int BIG_GPW = BIG_GROUPS / BIG_NW;   // 8 groups per wave, interleaved (dense column ranges spread over all waves)
@@ -1629,17 +1646,30 @@ __device__ __forceinline__ int block_sum_16(int v, int* red) {
 }
 
 // saveBitmaps: device buffer of saveCap row slots x BIG_WORDS words (may be null / 0); only used when n <= BIG_WC
+// LOG (n > BIG_WC, for k_num_bigdirect): the bitmap update returns the old word, and a product whose bit was already set is a
+// RE-HIT of its column.  Every wave compacts the re-hit columns of a trip (ballot + rank) and appends them to the block's
+// own region of rlLog (rlRegion ints per block, filled front to back over the block's rows).  Row q of the bin (queue order)
+// gets rlMeta[q] = {first log entry (index into rlLog), re-hits}; the count is -1 when the row logged more than rlCap
+// entries or the region had no room left -- such a row leaves the region as it found it.  A column hit k times is logged
+// k-1 times, nothing is deduplicated.  Rows that will not take the direct kernel (count -1, or q >= rlRows: no metadata
+// slot) are appended to fbList, *fbCount counts them.  The row's IC entry is the popcount either way.
+template <bool LOG>
 __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__ binPtr, int bin,
                                                          const int* __restrict__ rowIds,
                                                          const int* __restrict__ IA, const int2* __restrict__ SBL,
                                                          const int* __restrict__ JB,
                                                          int n, int* __restrict__ IC,
                                                          unsigned* __restrict__ saveBitmaps, int saveCap,
-                                                         int* __restrict__ qctr) {
+                                                         int* __restrict__ qctr,
+                                                         int2* __restrict__ rlMeta, int rlRows, int* __restrict__ rlLog,
+                                                         int rlRegion, int rlCap, int* __restrict__ fbList,
+                                                         int* __restrict__ fbCount) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   BigSymShared& sh = *reinterpret_cast<BigSymShared*>(smem_raw);
   const int tid = threadIdx.x;
   const int first = binPtr[bin], count = binPtr[bin + 1] - first;
+  int cursor = 0;                                      // LOG: ints of this block's region in use (block-uniform)
+  int* const myLog = LOG ? rlLog + (size_t)blockIdx.x * (size_t)rlRegion : nullptr;
   // the next row is dequeued and its metadata requested before this row's work starts: the dependent chain
   // queue -> rowIds -> IA (three memory round trips) hides behind the row instead of preceding it
   int q = next_row(qctr, &sh.red[0]);
@@ -1650,21 +1680,54 @@ __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__
     const int row = cur.row;
     const int as = cur.as, ae = cur.ae;
     int total = 0;
+    const bool logging = LOG && q < rlRows;            // block-uniform
+    const int room = logging ? min(rlCap, rlRegion - cursor) : 0;
+    int logged = 0, logOvf = 0;
     for (int w0 = 0; w0 < n; w0 += SYM_WC) {
       const int wc = min(SYM_WC, n - w0);
       const int words = (wc + 31) >> 5;
       const int words4 = (words + 3) & ~3;             // the bitmap is cleared and counted four words at a time
       for (int i = tid * 4; i < words4; i += BIG_THREADS * 4) *reinterpret_cast<uint4*>(&sh.bitmap[i]) = make_uint4(0u, 0u, 0u, 0u);
+      if (LOG && w0 == 0 && tid == 0) { sh.logCnt = 0; sh.logOvf = 0; }
       __syncthreads();
       for_each_product<BIG_NW, BIG_U, false>(sh.st, as, ae, SBL, nullptr, JB, nullptr,
                                              [&](const bool (&act)[BIG_U], const int (&col)[BIG_U], const float (&)[BIG_U], int) {
+        bool rehit[BIG_U];
 #pragma unroll
         for (int u = 0; u < BIG_U; ++u) {            // predicated by value: OR-ing 0 changes nothing
           const int c = col[u] - w0;
           const bool ok = act[u] && (unsigned)c < (unsigned)wc;
-          atomicOr(ok ? &sh.bitmap[c >> 5] : reinterpret_cast<unsigned*>(&sh.st.dummy[lane_id()]), ok ? 1u << (c & 31) : 0u);
+          const unsigned bit = ok ? 1u << (c & 31) : 0u;
+          if constexpr (LOG) {
+            const unsigned old = atomicOr(ok ? &sh.bitmap[c >> 5] : reinterpret_cast<unsigned*>(&sh.st.dummy[lane_id()]), bit);
+            rehit[u] = (old & bit) != 0u;              // bit = 0 for a lane without a product
+          } else {
+            atomicOr(ok ? &sh.bitmap[c >> 5] : reinterpret_cast<unsigned*>(&sh.st.dummy[lane_id()]), bit);
+            rehit[u] = false;
+          }
+        }
+        if constexpr (LOG) if (logging) {              // block-uniform
+          unsigned long long mk[BIG_U];
+          int tot = 0;
+#pragma unroll
+          for (int u = 0; u < BIG_U; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
+          if (tot) {                                   // wave-uniform
+            int base = 0;
+            if (lane_id() == 0) base = atomicAdd(&sh.logCnt, tot);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + tot > room) {                   // wave-uniform: no room (or a row for the fallback kernel anyway)
+              if (lane_id() == 0) sh.logOvf = 1;
+            } else {
+#pragma unroll
+              for (int u = 0; u < BIG_U; ++u) {        // cursor + base + tot <= cursor + room <= rlRegion
+                if (rehit[u]) myLog[cursor + base + mask_rank(mk[u])] = col[u];
+                base += __popcll(mk[u]);
+              }
+            }
+          }
         }
       });
+      if constexpr (LOG) { logged = sh.logCnt; logOvf = sh.logOvf; }   // after the walk's closing barrier; reset only behind block_sum_16's
       int mine = 0;
       for (int i = tid * 4; i < words4; i += BIG_THREADS * 4) {
         const uint4 v4 = *reinterpret_cast<const uint4*>(&sh.bitmap[i]);
@@ -1678,6 +1741,14 @@ __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__
       __syncthreads();
     }
     if (tid == 0) IC[row] = total;
+    if constexpr (LOG) {
+      const bool direct = logging && !logOvf;          // then logged <= room <= rlCap
+      if (tid == 0) {
+        if (q < rlRows) rlMeta[q] = make_int2((int)(blockIdx.x * (unsigned)rlRegion) + cursor, direct ? logged : -1);
+        if (!direct) fbList[atomicAdd(fbCount, 1)] = row;
+      }
+      if (direct) cursor += logged;
+    }
     cur = nxt;
     q = qn;
   }
@@ -1994,6 +2065,149 @@ __global__ __launch_bounds__(BIG_THREADS) void k_num_bighash(const int* __restri
     atomicAdd(&g_stamps[9], 1ull);
   }
 #endif
+}
+
+// numeric C (n > BIG_WC, rows whose re-hits k_sym_big<true> logged): one block of NW waves per row, a table of at most S
+// (key, value) slots that holds ONLY the row's repeated columns.  The log is inserted first, every key with the value bits
+// of -0.0f (the additive identity: a column hit twice ends as exactly a + b, as in k_num_bighash).  Then the products are
+// walked once and probe READ-ONLY: a hit adds its value under EXEC; a miss -- the probe meets an empty slot -- is a product
+// whose column occurs once in the row, and goes straight to JC/C at a position drawn from the row's counter (ballot rank +
+// one LDS atomic per wave and trip).  The table sweep then emits the repeated columns on the same counter.  A row is taken
+// only if 0 <= re-hits <= cap < S, so the table can never fill up; every other row of the bin is skipped here and is in
+// the fallback list k_num_bighash runs over.  The queue is the bin's own (largest rows first).
+template <int NW, int S>
+struct BigDirectShared {
+  slot_t tab[S];
+  WalkStageN<NW> st;
+  int red[NW];
+  int emitted;
+};
+struct DirectMeta { RowMeta m; int ls, lc; };            // + first log entry, re-hits (-1: not a row of this kernel)
+__device__ __forceinline__ DirectMeta load_meta_direct(const int* rows, int q, int count, const int* IA, const int* IC,
+                                                       const int2* rlMeta, int rlRows, int cap) {
+  DirectMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
+  if (q < count && q < rlRows) {
+    const int2 lm = rlMeta[q];
+    if (lm.y >= 0 && lm.y <= cap) { d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC); }
+  }
+  return d;
+}
+
+template <int NW, int S>
+__global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restrict__ binPtr, int bin,
+                                                             const int* __restrict__ rowIds,
+                                                             const int* __restrict__ IA, const int2* __restrict__ SBL,
+                                                             const float* __restrict__ VA,
+                                                             const int* __restrict__ JB,
+                                                             const float* __restrict__ VB,
+                                                             const int* __restrict__ IC, int* __restrict__ JC,
+                                                             float* __restrict__ C, int* __restrict__ err,
+                                                             int* __restrict__ qctr, const int2* __restrict__ rlMeta,
+                                                             int rlRows, const int* __restrict__ rlLog) {
+  static_assert(S % (WAVE * NW) == 0 && BD_MIN_SLOTS % (WAVE * NW) == 0, "every wave sweeps whole 64-slot steps");
+  constexpr int T = WAVE * NW;
+  constexpr int CAP = bd_cap(S);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  BigDirectShared<NW, S>& sh = *reinterpret_cast<BigDirectShared<NW, S>*>(smem_raw);
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  const int first = binPtr[bin], count = binPtr[bin + 1] - first;
+  if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
+  int q = next_row(qctr, &sh.red[0]);                 // one row ahead, as in k_sym_big
+  DirectMeta cur = load_meta_direct(rowIds + first, q, count, IA, IC, rlMeta, rlRows, CAP);
+  while (q < count) {
+    const int qn = next_row(qctr, &sh.red[0]);
+    const DirectMeta nxt = load_meta_direct(rowIds + first, qn, count, IA, IC, rlMeta, rlRows, CAP);
+    if (cur.lc >= 0) {                                 // block-uniform
+      const int as = cur.m.as, ae = cur.m.ae;
+      const int outBase = cur.m.x0, outEnd = cur.m.x1;
+      const int want = outEnd - outBase;
+      const int lc = cur.lc;
+      // four slots per logged re-hit when that fits (the clear and the sweep are what a small table saves)
+      const int size = table_size<4>(lc, BD_MIN_SLOTS, S);
+      const int shift = 32 - log2_pow2(size);
+      const int per = size / NW;
+      clear_slots(sh.tab, size, tid, T);
+      if (tid == 0) sh.emitted = 0;
+      __syncthreads();
+      {                                                // the row's log: distinct keys <= lc <= CAP < S, or size >= 4 * lc
+        const int* const lg = rlLog + cur.ls;
+        const unsigned mask = (unsigned)size - 1u;
+        for (int i = tid; i < lc; i += T) {
+          const int c = lg[i];
+          const slot_t mine = make_slot(c, -0.0f);
+          unsigned h = ((unsigned)c * 2654435761u) >> shift;
+          for (int probe = 0; probe < size; ++probe) {
+            const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, mine);
+            if (old == EMPTY_SLOT || slot_key(old) == c) break;
+            h = (h + 1u) & mask;
+          }
+        }
+      }
+      __syncthreads();
+      int* const JCrow = JC + outBase;
+      float* const Crow = C + outBase;
+      const unsigned lim = (unsigned)max(want, 0);     // every store stays inside the row's own range
+      for_each_product<NW, BD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
+                                       [&](const bool (&act)[BD_U], const int (&col)[BD_U], const float (&val)[BD_U], int) {
+        char* const base = reinterpret_cast<char*>(sh.tab);
+        const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
+        const int maskB = size * 8 - 1;
+        int hB[BD_U], hitB[BD_U];                       // byte offsets; dumB = "done" / "no hit"
+        bool miss[BD_U];
+#pragma unroll
+        for (int u = 0; u < BD_U; ++u) {
+          const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
+          hB[u] = act[u] ? (int)(h * 8u) : dumB;
+          hitB[u] = dumB;
+          miss[u] = false;
+        }
+        for (int probe = 0;;) {                         // the keys do not change during the walk: plain reads
+          int key[BD_U];
+#pragma unroll
+          for (int u = 0; u < BD_U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
+          ++probe;
+          int pendBits = 0;
+#pragma unroll
+          for (int u = 0; u < BD_U; ++u) {
+            const bool pend = hB[u] != dumB;
+            const bool hit = pend && key[u] == col[u];
+            const bool emp = pend && key[u] == EMPTY_KEY;
+            hitB[u] = hit ? hB[u] : hitB[u];
+            miss[u] = miss[u] || emp;
+            hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the insert above
+            pendBits |= hB[u] ^ dumB;
+          }
+          if (ballot64(pendBits != 0) == 0ull) break;
+          if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
+        }
+#pragma unroll
+        for (int u = 0; u < BD_U; ++u)
+          if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
+        unsigned long long mk[BD_U];
+        int tot = 0;
+#pragma unroll
+        for (int u = 0; u < BD_U; ++u) { mk[u] = ballot64(miss[u]); tot += __popcll(mk[u]); }
+        if (tot) {                                      // wave-uniform
+          int pos = 0;
+          if (lane == 0) pos = atomicAdd(&sh.emitted, tot);
+          pos = __builtin_amdgcn_readfirstlane(pos);
+#pragma unroll
+          for (int u = 0; u < BD_U; ++u) {
+            const unsigned o = (unsigned)(pos + mask_rank(mk[u]));
+            if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+            pos += __popcll(mk[u]);
+          }
+        }
+      });
+      // (the walk ends with a barrier behind its last LDS atomics)
+      emit_claimed<S / NW / WAVE>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
+      __syncthreads();
+      if (tid == 0 && sh.emitted != want) atomicOr(err, ERRF_COUNT_MISMATCH);
+      __syncthreads();
+    }
+    cur = nxt;
+    q = qn;
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -221,7 +221,7 @@ struct HostMirror {                 // one small device block + its pinned host 
   // work-queue heads of the block-per-row kernels (zeroed with the rest per call).  One 128-byte line EACH: the kernels
   // of a phase run side by side and every dequeue is an atomic on its word -- eight words in one line (next to binPtr /
   // slotBase, which every block reads when it starts) made all of them queue up behind one another in the L2.
-  alignas(128) int qctr[8 * 32];
+  alignas(128) int qctr[9 * 32];
   alignas(128) int qpad_;
   int slotBase[NSLOTS + 1];         // first position of every layout slot in rowIds, [NSLOTS] = m (k_bin_scan)
   unsigned long long totalP;
@@ -231,6 +231,10 @@ struct HostMirror {                 // one small device block + its pinned host 
   int nBatches;
   alignas(128) int chainTicket;
   alignas(128) int chainPad_;
+  // big rows of a logging symbolic pass (k_sym_big<true>) that stay with k_num_bighash: {0, rows}, read by that kernel as
+  // the "bin" of the fallback list (spgemm_handle::bigFallback)
+  alignas(128) int fbBin[2];
+  alignas(128) int fbPad_;
 };
 
 struct spgemm_handle {
@@ -280,6 +284,24 @@ struct spgemm_handle {
   int spill_blocks = 0;
   int bhCap = BH_CAP;
   int bhMargin = 125;                // parking region per hash class, % of products/npass (SPGEMM_BHMARGIN; tests force overflows)
+  // direct big-row kernel (n > BIG_WC, float): the symbolic pass logs the re-hit columns of the big rows into rlLog (numCU
+  // regions of rl_region ints) and {first entry, count} per row of the bin into rlMeta (rl_rows slots).  Sized from the
+  // previous calls like the bitmaps above (grow_rehit_log): a call that finds no workspace, too few metadata slots or a
+  // full region sends those rows down k_num_bighash.
+  bool bigDirect = true;             // SPGEMM_BIGDIRECT=0: every big row takes k_num_bighash (A/B runs; keeps the fallback tested)
+  int bdCfg = 1;                     // SPGEMM_BD_CFG: waves x table slots of k_num_bigdirect {0: 4x4096, 1: 8x4096, 2: 4x8192, 3: 8x8192,
+                                     // 4: 16x4096}; 1 measured best (three blocks per CU; profiles/README.md)
+  int bdMinRows = 0;                 // SPGEMM_BD_MINROWS: calls with fewer rows in the last bin keep k_num_bighash for all of them.  Default: the
+                                     // CU count -- below it every row has a CU to itself in either kernel and the second launch costs more
+                                     // than it saves (web surrogate: the bin 0.018 -> 0.023 ms); the tests set 1
+  int rlRegionEnv = 0;               // SPGEMM_RLREGION: ints per block region instead of the computed size (tests fill a region)
+  int2* rlMeta = nullptr;
+  int rl_rows = 0;
+  int* rlLog = nullptr;
+  int rl_region = 0;
+  int* bigFallback = nullptr;        // rows of the fallback list (workspace block, one int per row of A)
+  bool bdLogged = false;             // the pending / current product's symbolic pass logged (launch_symbolic)
+  bool bdRan = false;                // the latest numeric launch used k_num_bigdirect
   int h1sym = 32;                    // blocks per CU of the wave-per-row symbolic kernel (SPGEMM_H1SYM, experiments)
   int h1num = 24;                    // ... of the wave-per-row numeric kernel on its 512-slot tables (SPGEMM_H1NUM)
   spgemm_stats stats;
@@ -295,7 +317,7 @@ static std::map<int, int> g_handles_on;          // device -> live handles (the 
 
 // the workspace blocks sized by the row count: where each pointer lives and its bytes for `cap` rows
 struct WsBlock { void** ptr; size_t bytes; };
-static std::array<WsBlock, 9> ws_blocks(spgemm_handle* h, size_t cap) {
+static std::array<WsBlock, 10> ws_blocks(spgemm_handle* h, size_t cap) {
   const size_t nblk = (cap + K1_THREADS - 1) / K1_THREADS;
   const size_t ntile = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE + 1;
   return {{{(void**)&h->rowFlops, sizeof(int) * cap},
@@ -305,6 +327,7 @@ static std::array<WsBlock, 9> ws_blocks(spgemm_handle* h, size_t cap) {
            {(void**)&h->rowIds, sizeof(int) * cap},
            {(void**)&h->tileSum, sizeof(unsigned long long) * ntile},
            {(void**)&h->blockP, sizeof(unsigned long long) * nblk},
+           {(void**)&h->bigFallback, sizeof(int) * cap},
            {(void**)&h->batchStart, sizeof(int) * (3 * cap + 64)},
            {(void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)}}};
 }
@@ -333,6 +356,21 @@ static int ws_ensure(spgemm_handle* h, int m) {
   h->cap_m = (int)std::min<size_t>(cap, 0x7fffffff);
   return SPGEMM_OK;
 }
+
+// k_num_bigdirect's geometry as compile-time constants: f(waves, table slots)
+template <class F>
+static auto with_bd_cfg(int cfg, F f) {
+  typedef std::integral_constant<int, 4> W4; typedef std::integral_constant<int, 8> W8; typedef std::integral_constant<int, 16> W16;
+  typedef std::integral_constant<int, 4096> S4; typedef std::integral_constant<int, 8192> S8;
+  switch (cfg) {
+    case 0: return f(W4(), S4());
+    case 1: return f(W8(), S4());
+    case 2: return f(W4(), S8());
+    case 4: return f(W16(), S4());
+    default: return f(W8(), S8());
+  }
+}
+static int bd_cap_of(int cfg) { return bd_cap(cfg == 2 || cfg == 3 ? 8192 : 4096); }
 
 // an integer knob of the handle from the environment; a value outside [lo, hi] is ignored
 static void env_int(const char* name, int lo, int hi, int* field) {
@@ -373,6 +411,11 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   env_int("SPGEMM_H1NUM", 1, 32, &h->h1num);
   env_int("SPGEMM_BHMARGIN", 10, 400, &h->bhMargin);
   env_int("SPGEMM_BHCAP", 1024, BH_CAP_MAX, &h->bhCap);
+  { int v = 1; env_int("SPGEMM_BIGDIRECT", 0, 1, &v); h->bigDirect = v != 0; }
+  env_int("SPGEMM_BD_CFG", 0, 4, &h->bdCfg);
+  h->bdMinRows = h->numCU;
+  env_int("SPGEMM_BD_MINROWS", 1, 1 << 30, &h->bdMinRows);
+  env_int("SPGEMM_RLREGION", 64, 1 << 24, &h->rlRegionEnv);
   env_int("SPGEMM_PATH", 0, 2, &h->pathMode);
   env_int("SPGEMM_CHAIN_CFG", INT_MIN, INT_MAX, &h->chainCfg);   // unchecked: chain_cfg() maps anything else to 0
   { int u = h->U; env_int("SPGEMM_U", 2, 8, &u); if (u == 2 || u == 4 || u == 8) h->U = u; }
@@ -390,7 +433,11 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   memset(&h->stats, 0, sizeof(h->stats));
   { std::lock_guard<std::mutex> lk(g_count_mu); ++g_handles_on[device]; }
   // the big-row kernels use more than the default 64 KB of dynamic LDS
-  HIPCHK(hipFuncSetAttribute((const void*)k_sym_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
+  HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
+  HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
+  HIPCHK(with_bd_cfg(h->bdCfg, [&](auto nw, auto slots) {
+    return hipFuncSetAttribute((const void*)k_num_bigdirect<nw, slots>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)sizeof(BigDirectShared<nw, slots>)); }));
   HIPCHK(hipFuncSetAttribute((const void*)k_num_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigNumShared)));
   HIPCHK(hipFuncSetAttribute((const void*)k_num_bighash, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigHashShared)));
   *out = h;
@@ -405,6 +452,8 @@ extern "C" int spgemm_hip_destroy(spgemm_handle* h) {
   ws_free(h);
   hipFree(h->bigBitmaps);
   hipFree(h->spill);
+  hipFree(h->rlMeta);
+  hipFree(h->rlLog);
   hipFree(h->sbl);
   hipFree(h->dsmall);
   hipHostFree(h->hsmall);
@@ -434,6 +483,18 @@ extern "C" int spgemm_hip_handle_device(const spgemm_handle* h) { return h ? h->
 
 // test hook: the next `count` symbolic phases / fused R-MCL steps on this handle return SPGEMM_ERR_INTERNAL before they queue
 // anything (how the tests make ONE rank of a multi-rank group fail: every rank must then leave the step with an error)
+// test hook: how the latest product on this handle split its rows of more than 4096 products between k_num_bigdirect and
+// k_num_bighash (n > BIG_WC only; the counts are those of the mirror the call read last), and the two sizes that decide it
+extern "C" int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows, int* fallback_rows, int* rehit_cap, int* region_ints) {
+  if (!h || !direct_rows || !fallback_rows || !rehit_cap || !region_ints) return fail(SPGEMM_ERR_ARG, "null argument");
+  const int nbig = h->mirror.binPtr[NBINS] - h->mirror.binPtr[NBINS - 1];
+  *fallback_rows = h->bdRan ? h->mirror.fbBin[1] : nbig;
+  *direct_rows = nbig - *fallback_rows;
+  *rehit_cap = bd_cap_of(h->bdCfg);
+  *region_ints = h->rl_region;
+  return SPGEMM_OK;
+}
+
 extern "C" int spgemm_hip_debug_fail_next(spgemm_handle* h, int count) {
   if (!h) return fail(SPGEMM_ERR_ARG, "null handle");
   h->failNext = count;
@@ -639,8 +700,10 @@ static int launch_classify(spgemm_handle* h, const int* dIA, const int* dJA, con
 // symbolic pass over bins 2..8 (bins 0/1 were preset by K1).  Bin sizes are not known on the host
 // here (no sync): grids are capped by the CU count and every block strides / dequeues over its bin.
 static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
-                           int m, int n, const int* rowIds, int* dIC, int minBin = 0, bool skipH1A = false) {
+                           int m, int n, const int* rowIds, int* dIC, int minBin = 0, bool skipH1A = false, bool logBig = false) {
   const int2* sbl = h->sbl;
+  // logBig: a float product's big rows may take k_num_bigdirect -- the symbolic kernel logs their re-hit columns
+  h->bdLogged = logBig && h->bigDirect && n > BIG_WC && m > 0;
   if (m <= 0) return SPGEMM_OK;
   clear_stale_hip_error();
   const int* bp = h->dsmall->binPtr;
@@ -649,8 +712,16 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
   const int cu = h->numCU;
   fork_streams(h);
   { hipStream_t st = h->side[3]; KTimer t(h, SPGEMM_K_SYM_BIG, st);
-    hipLaunchKernelGGL(k_sym_big, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
-                       rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32); }
+    // (the grid never exceeds the CU count: rlLog has one region per CU)
+    if (h->bdLogged)
+      hipLaunchKernelGGL(k_sym_big<true>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
+                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
+                         h->rlMeta, h->rlLog ? h->rl_rows : 0, h->rlLog, h->rl_region, bd_cap_of(h->bdCfg), h->bigFallback,
+                         &h->dsmall->fbBin[1]);
+    else
+      hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
+                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
+                         (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr); }
   if (minBin <= 7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_SYM_HASH8, st);
     LAUNCH_U(k_sym_hash, 8, 8192, dim3(clampi(m, 1, cu * 3)), dim3(512), st, bp, 7, rowIds, dIA,
              sbl, dJB, h->rowFlops, dIC, err, qc + 1 * 32); }
@@ -710,8 +781,13 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
       hipLaunchKernelGGL(k_num_big, dim3(clampi(rows(8, 9), 1, cu)), dim3(BIG_THREADS), sizeof(BigNumShared), st,
                          bp, 8, rowIds, dIA, sbl, dA, dJB, dB, n, dIC, dJC, dC, err, h->bigBitmaps, h->bm_cap,
                          qc + 4 * 32);
-    } else { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);
+    } else { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);   // both launches of the direct path are timed under this id
       const int blocks = clampi(rows(8, 9), 1, cu);
+      // rows whose re-hits the symbolic pass logged take k_num_bigdirect, the others are in the fallback list (its length is
+      // on the device only: the launch is sized by the bin); the fused R-MCL step keeps k_num_bighash for all of them
+      // (and so does a call with only a few such rows: bdMinRows)
+      const bool direct = h->bdLogged && !pcnt && rows(8, 9) >= h->bdMinRows;
+      h->bdRan = direct;
       if (blocks > h->spill_blocks) {                  // parking space of multi-pass rows: 1 MB per block, kept
         hipFree(h->spill);
         h->spill = nullptr;
@@ -720,8 +796,17 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
         else (void)hipGetLastError();                  // without it those rows walk once per pass
       }
       hipLaunchKernelGGL(k_num_bighash, dim3(blocks), dim3(BIG_THREADS), sizeof(BigHashShared), st,
-                         bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 4 * 32, h->rowFlops,
-                         h->spill_blocks >= blocks ? h->spill : (int2*)nullptr, BH_SPILL, h->bhCap, h->bhMargin); }
+                         direct ? h->dsmall->fbBin : bp, direct ? 0 : 8, direct ? h->bigFallback : rowIds, dIA, sbl, dA, dJB,
+                         dB, dIC, dJC, dC, err, qc + 4 * 32, h->rowFlops,
+                         h->spill_blocks >= blocks ? h->spill : (int2*)nullptr, BH_SPILL, h->bhCap, h->bhMargin);
+      if (direct && h->rlLog)                          // (no workspace yet: every row is in the fallback list)
+        with_bd_cfg(h->bdCfg, [&](auto nw, auto slots) {
+          const int lds = (int)sizeof(BigDirectShared<nw, slots>);
+          const int perCU = std::max(1, std::min((160 * 1024) / lds, 32 / (int)nw));
+          hipLaunchKernelGGL((k_num_bigdirect<nw, slots>), dim3(clampi(rows(8, 9), 1, cu * perCU)), dim3(WAVE * nw), lds, st,
+                             bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 8 * 32,
+                             (const int2*)h->rlMeta, h->rl_rows, (const int*)h->rlLog);
+          return 0; }); }
     if (pcnt) hipLaunchKernelGGL(k_rmcl_fix_rows, dim3(clampi(rows(8, 9), 1, cu * 8)), dim3(256), 0, st,
                                  bp, 8, 9, rowIds, dIC, dJC, dC, pcnt);
   }
@@ -894,7 +979,7 @@ static int finish_symbolic(spgemm_handle* h, int m, int* nnzCp) {
 
 // phase 1: classify + symbolic + scan are queued with ev[0..3] around them, then finish_symbolic
 static int symbolic_phase(spgemm_handle* h, const int* dIA, const int* dJA, int nnzA, const int* dIB, const int* dJB,
-                          int m, int k, int n, const PreClass* pre, int* dIC, int* nnzCp) {
+                          int m, int k, int n, const PreClass* pre, int* dIC, int* nnzCp, bool logBig = true) {
   (void)k;
   if (h->failNext > 0) { --h->failNext; return fail(SPGEMM_ERR_INTERNAL, "forced failure (spgemm_hip_debug_fail_next)"); }
   hipStream_t s = h->stream;
@@ -910,7 +995,7 @@ static int symbolic_phase(spgemm_handle* h, const int* dIA, const int* dJA, int 
     CHK(launch_classify(h, dIA, dJA, dIB, m, nnzA, dIC));
   }
   hipEventRecord(h->ev[1], s);
-  CHK(launch_symbolic(h, dIA, dJB, m, n, h->cur_rowIds, dIC));
+  CHK(launch_symbolic(h, dIA, dJB, m, n, h->cur_rowIds, dIC, 0, false, logBig));
   hipEventRecord(h->ev[2], s);
   if (m > 0) CHK(launch_scan(h, dIC, m, &h->dsmall->nnzC64));
   else HIPCHK(hipMemsetAsync(dIC, 0, sizeof(int), s));
@@ -927,6 +1012,29 @@ static void grow_bitmaps(spgemm_handle* h, int n) {
     const int cap = nbig + nbig / 4 + 16;
     if (hipMalloc((void**)&h->bigBitmaps, (size_t)cap * BIG_WORDS * sizeof(unsigned)) == hipSuccess) h->bm_cap = cap;
     else { h->bm_cap = 0; (void)hipGetLastError(); }
+  }
+}
+
+// room for the big rows' re-hit log next time (direct kernel only).  Size: one metadata slot per big row seen (+25 %), and
+// RL_ROW_BUDGET = 2048 log ints per big row, dealt evenly to one region per CU: on the headline matrix a big row logs 930
+// re-hits on average (median 816, p99 2285) and the dynamic queue hands a block rows in proportion to their work, so a
+// region holds about twice what its block logs.  A row that finds its region full takes the fallback kernel: never wrong.
+static void grow_rehit_log(spgemm_handle* h, int n) {
+  const int nbig = h->mirror.binPtr[NBINS] - h->mirror.binPtr[NBINS - 1];
+  if (!h->bigDirect || n <= BIG_WC || nbig <= h->rl_rows || nbig < h->bdMinRows) return;   // (too few rows: the log would not be used)
+  hipFree(h->rlMeta); hipFree(h->rlLog);
+  h->rlMeta = nullptr; h->rlLog = nullptr; h->rl_rows = 0; h->rl_region = 0;
+  const int cap = nbig + nbig / 4 + 16;
+  const long long perBlock = ((long long)cap + h->numCU - 1) / h->numCU * RL_ROW_BUDGET;
+  long long region = h->rlRegionEnv > 0 ? h->rlRegionEnv : std::max<long long>(RL_MIN_REGION, perBlock);
+  region = std::min<long long>(region, (1ll << 30) / h->numCU);           // entry indices stay ints
+  if (hipMalloc((void**)&h->rlMeta, (size_t)cap * sizeof(int2)) == hipSuccess &&
+      hipMalloc((void**)&h->rlLog, (size_t)region * (size_t)h->numCU * sizeof(int)) == hipSuccess) {
+    h->rl_rows = cap; h->rl_region = (int)region;
+  } else {
+    (void)hipGetLastError();
+    hipFree(h->rlMeta); hipFree(h->rlLog);
+    h->rlMeta = nullptr; h->rlLog = nullptr;
   }
 }
 
@@ -1041,7 +1149,7 @@ static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
   collect_kernel_times(h, false);
-  if (isFloat) grow_bitmaps(h, n);
+  if (isFloat) { grow_bitmaps(h, n); grow_rehit_log(h, n); }
   return done(SPGEMM_OK);
 }
 
@@ -1064,7 +1172,8 @@ static int finish_exact(spgemm_handle* h, const Product<V>& p, int nnzC, int* dI
 template <class V>
 static int two_phase(spgemm_handle* h, const Product<V>& p, const PreClass* pre, int* dIC, const Result<V>& out) {
   int nnzC = 0;
-  if (int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, pre, dIC, &nnzC)) { pool().release(dIC); return rc; }
+  // (a double product's numeric kernels have no use for the big rows' re-hit log)
+  if (int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, pre, dIC, &nnzC, std::is_same<V, float>::value)) { pool().release(dIC); return rc; }
   return finish_exact(h, p, nnzC, dIC, out);
 }
 
@@ -1105,7 +1214,7 @@ static int one_shot_front(spgemm_handle* h, const Product<float>& p, const OptIn
       hipEventRecord(h->evMid, s) != hipSuccess)
     return fail(SPGEMM_ERR_HIP, "classification copy failed: %s", hipGetErrorString(hipGetLastError()));
   if (o.wb2) CHK(launch_wbatch<WB_SYM>(h, p.m, p.IA, nullptr, p.JB, nullptr, dIC, nullptr, nullptr, 0));
-  CHK(launch_symbolic(h, p.IA, p.JB, p.m, p.n, h->cur_rowIds, dIC, o.minBin, o.skipH1A));
+  CHK(launch_symbolic(h, p.IA, p.JB, p.m, p.n, h->cur_rowIds, dIC, o.minBin, o.skipH1A, true));
   hipEventRecord(h->ev[2], s);
   if (!o.chain) CHK(launch_scan(h, dIC, p.m, &h->dsmall->nnzC64));
   hipEventRecord(h->ev[3], s);
@@ -1149,6 +1258,7 @@ static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInP
   }
   publish_stats(h, hm, StatsForm::OneShot);
   grow_bitmaps(h, p.n);
+  grow_rehit_log(h, p.n);
   h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = (long long)hm.nnzC64;
   *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = (int)hm.nnzC64;
   return SPGEMM_OK;
@@ -1783,9 +1893,10 @@ static int rmcl_size_rows_by_products(spgemm_handle* h, const CsrView& A, const 
   const int nbig = mid.binPtr[NBINS] - mid.binPtr[NBINS - 1];
   if (nbig > 0) {
     KTimer t(h, SPGEMM_K_SYM_BIG, s);
-    hipLaunchKernelGGL(k_sym_big, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
+    h->bdLogged = false;
+    hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
                        h->dsmall->binPtr, 8, h->cur_rowIds, A.I, h->sbl, B.J, n, dIC, h->bigBitmaps, h->bm_cap,
-                       h->dsmall->qctr + 0 * 32);
+                       h->dsmall->qctr + 0 * 32, (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr);
     if (hipGetLastError() != hipSuccess) return rmcl_hipfail("symbolic launch");
   }
   return SPGEMM_OK;

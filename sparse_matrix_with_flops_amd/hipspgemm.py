@@ -58,7 +58,7 @@ EXPORTS = [
     "hip_sharded_spmm_info", "hip_sharded_spmm_destroy", "hip_gpuRmclIter_sharded", "spgemm_hip_host_api_stats",
     "hip_sharded_spmm_handle", "spgemm_hip_rccl_available", "spgemm_hip_pool_trim",
     "hip_sharded_rmcl_create", "hip_sharded_rmcl_run", "hip_sharded_rmcl_continue", "hip_sharded_rmcl_result", "hip_sharded_rmcl_iter_nnz",
-    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
+    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_debug_bigrow_paths", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
     "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
     "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
     "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
@@ -253,6 +253,8 @@ def lib():
         L.hip_sharded_rmcl_info.argtypes = [C.c_void_p, _I]
         L.hip_sharded_rmcl_destroy.argtypes = [C.c_void_p]
         L.spgemm_hip_debug_fail_next.argtypes = [C.c_void_p, C.c_int]
+        if hasattr(L, "spgemm_hip_debug_bigrow_paths"):      # (an older library loaded through SPGEMM_LIB for an A/B run has none)
+            L.spgemm_hip_debug_bigrow_paths.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
         L.spgemm_hip_handle_device.argtypes = [C.c_void_p]
         L.free = C.CDLL(None).free
         L.free.argtypes = [C.c_void_p]
@@ -368,6 +370,13 @@ class Handle:
     def fail_next(self, count=1):
         """test hook: the next `count` symbolic phases / fused R-MCL steps on this handle fail"""
         _check(lib().spgemm_hip_debug_fail_next(self._h, int(count)), "spgemm_hip_debug_fail_next")
+
+    def bigrow_paths(self):
+        """test hook: rows of the latest product's last bin that took the direct kernel / the multi-pass hash kernel, the
+        re-hit cap of the direct kernel and the ints of one block's log region"""
+        v = [C.c_int(0) for _ in range(4)]
+        _check(lib().spgemm_hip_debug_bigrow_paths(self._h, *[C.byref(x) for x in v]), "spgemm_hip_debug_bigrow_paths")
+        return {"direct": v[0].value, "fallback": v[1].value, "cap": v[2].value, "region": v[3].value}
 
     def close(self):
         if self._h and self._own:
