@@ -310,6 +310,20 @@ int spgemm_hip_debug_fail_next(spgemm_handle* h, int count);
  * (tests fill a region with it). */
 int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows, int* fallback_rows, int* rehit_cap, int* region_ints);
 
+/* test hook: the same for the rows of 513-4096 products (any n, float): `rows` of the latest product on this handle, how many
+ * took the direct kernel (rows without a repeated column, which are expanded, included) and how many the hash kernel of
+ * their bin, and the re-hits a row may log and still go direct.  SPGEMM_MIDDIRECT=0 (read at handle creation) keeps the hash
+ * kernels for all of them; so does a handle's first call with such rows, which only measures the log it needs, and each of
+ * the two bins (513-2048, 2049-4096) when it has fewer rows than SPGEMM_MD_MINROWS (default: 4 x the number of CUs; the
+ * tests set 1).
+ * SPGEMM_MD_CFG=0..3 picks waves x table slots of the direct kernel for both bins (4x1024, 8x1024, 4x2048, 8x2048; the cap is
+ * 7/8 of the slots; default: 4x1024 for 513-2048 products, 8x1024 above), SPGEMM_MD_CAP=<re-hits> lowers the cap and SPGEMM_MRLOG=<ints> fixes the size of the log (tests run it out of
+ * space with the two). */
+int spgemm_hip_debug_midrow_paths(spgemm_handle* h, int* rows, int* direct_rows, int* fallback_rows, int* rehit_cap);
+/* ... and the log behind it: re-hits logged by the rows that went direct (the sum of products - nnz over those rows), ints
+ * of log space the call's symbolic pass reserved or would have reserved, ints the log had. */
+int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, long long* reserved, long long* capacity);
+
 /* ---- the step in front of the path: COO -> CSR on device arrays -------------
  * Replaces COO::addSelfLoopIfNeeded (nlibs/COO.cc:160-188), COO::makeOrdered / orderedAndDuplicatesRemoving
  * (nlibs/COO.cc:222-266: std::sort on (row,col), duplicates summed), COO::toCSR (nlibs/COO.cc:268-291),

@@ -208,11 +208,15 @@ __device__ __forceinline__ int hash_insert(int* keys, int size, int shift, int c
 // Returns the number of new keys THIS LANE claimed (the caller reduces over the wave once per row).
 // The dummy words are initialised to DUMMY_KEY (never EMPTY_KEY, never a column), so a CAS that lands there fails
 // and a parked lane needs no masking when the new keys of a round are counted.
+// RH (the logging symbolic kernels): (*rehit)[u] says whether product u ended on its own key ALREADY PRESENT -- a re-hit of its
+// column -- instead of claiming an empty slot.  The LDS serialises the CAS of a wave instruction lane by lane, so of several
+// lanes that bring the same new column in one round exactly one claims it and the others are re-hits: a row's re-hits are
+// its products minus its distinct columns.  (A parked lane reads DUMMY_KEY, never a column.)
 constexpr int DUMMY_KEY = (int)0x80000000;
 
-template <bool POW2 = true, int U>
+template <bool POW2 = true, bool RH = false, int U>
 __device__ __forceinline__ int hash_insert_multi(int* keys, int size, int shift, const bool (&act)[U],
-                                                 const int (&col)[U], int* dummy, int* err) {
+                                                 const int (&col)[U], int* dummy, int* err, bool (*rehit)[U] = nullptr) {
   char* const base = reinterpret_cast<char*>(keys);
   const int dumB = (int)(reinterpret_cast<char*>(dummy) - base);
   const int maskB = size * 4 - 1;
@@ -223,6 +227,7 @@ __device__ __forceinline__ int hash_insert_multi(int* keys, int size, int shift,
     const unsigned hv = (unsigned)col[u] * 2654435761u;
     const unsigned h = POW2 ? hv >> shift : __umulhi(hv, (unsigned)size);
     hB[u] = act[u] ? (int)(h * 4u) : dumB;
+    if constexpr (RH) (*rehit)[u] = false;
   }
   int probe = 0;
   // Bookkeeping on the vector side (round 3; these kernels fill ~55 % of the SCALAR issue slots too): `claimed` is a
@@ -238,6 +243,7 @@ __device__ __forceinline__ int hash_insert_multi(int* keys, int size, int shift,
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       claimed += old[u] == EMPTY_KEY ? 1 : 0;                               // the dummy is never EMPTY_KEY
+      if constexpr (RH) (*rehit)[u] = (*rehit)[u] || old[u] == col[u];
       const bool adv = hB[u] != dumB && old[u] != EMPTY_KEY && old[u] != col[u];
       // power-of-two tables: triangular steps (+1, +2, +3, ...) visit every slot once and break up probe clusters
       const int nh = POW2 ? ((hB[u] + probe * 4) & maskB) : (hB[u] + 4 == size * 4 ? 0 : hB[u] + 4);
@@ -368,19 +374,23 @@ __device__ __forceinline__ void lds_fadd_multi(float* acc, const int (&idx)[U], 
 // keep their one loop.  CH <= 0: the whole trip in one loop.
 // (trips of 4 rounds inserted 2 at a time in the multi-wave kernels: no change; of 8: slower.)
 template <int NW> struct InsChunk { static constexpr int value = NW == 1 ? 1 : 0; };
-template <int CH, int R>
+template <int CH, bool RH = false, int R>
 __device__ __forceinline__ int hash_insert_chunked(int* keys, int size, int shift, const bool (&act)[R], const int (&col)[R],
-                                                   int* dummy, int* err) {
-  if constexpr (CH <= 0 || CH >= R) return hash_insert_multi(keys, size, shift, act, col, dummy, err);
+                                                   int* dummy, int* err, bool (*rehit)[R] = nullptr) {
+  if constexpr (CH <= 0 || CH >= R) return hash_insert_multi<true, RH>(keys, size, shift, act, col, dummy, err, rehit);
   else {
     int claimed = 0;
 #pragma unroll
     for (int c0 = 0; c0 < R; c0 += CH) {
-      bool a_[CH]; int c_[CH];
+      bool a_[CH]; int c_[CH]; bool r_[CH];
 #pragma unroll
-      for (int u = 0; u < CH; ++u) { a_[u] = c0 + u < R ? act[c0 + u < R ? c0 + u : 0] : false; c_[u] = col[c0 + u < R ? c0 + u : 0]; }
-      if (CH == 1 && ballot64(a_[0]) == 0ull) continue;          // a round past the end of the group (5 rounds run as 6, 7 as 8)
-      claimed += hash_insert_multi(keys, size, shift, a_, c_, dummy, err);
+      for (int u = 0; u < CH; ++u) { a_[u] = c0 + u < R ? act[c0 + u < R ? c0 + u : 0] : false; c_[u] = col[c0 + u < R ? c0 + u : 0]; r_[u] = false; }
+      if (!(CH == 1 && ballot64(a_[0]) == 0ull))                 // (else: a round past the end of the group -- 5 rounds run as 6, 7 as 8)
+        claimed += hash_insert_multi<true, RH>(keys, size, shift, a_, c_, dummy, err, RH ? &r_ : nullptr);
+      if constexpr (RH) {
+#pragma unroll
+        for (int u = 0; u < CH; ++u) if (c0 + u < R) (*rehit)[c0 + u] = r_[u];
+      }
     }
     return claimed;
   }
@@ -1334,17 +1344,46 @@ __device__ __forceinline__ PreA load_pre(const RowMeta& mtd, const int2* SBL, co
 // Medium rows (65..4096 products): one block of NW waves per row, LDS key table (symbolic) or
 // key+value table compacted by a table sweep (numeric).
 // ------------------------------------------------------------------------------------------------
-template <int NW, int TBL, int U>
+// LOG (NW > 1, bins 6-7 of a float product, for k_num_middirect): the insert says which products are RE-HITS of a column the
+// row already has.  Every wave compacts the re-hit columns of a trip (ballot + rank + one LDS counter add) and appends them
+// to the row's stretch of the log in HBM; nothing is deduplicated, a column hit k times is logged k-1 times, so a row logs
+// exactly products - IC[row] entries.  Log space: a block reserves CHUNKS of MD_CHUNK ints from one global cursor (one
+// global atomic per chunk, not per row) and fills its chunk front to back over its rows; a row starts only with `cap` ints
+// left in the chunk, so it can run out of room only by passing the cap.  meta[row] = {first log entry, re-hits}; the count
+// is -1 when the row logged more than cap entries or its chunk lies beyond the log's capacity (the cursor keeps counting
+// there: its final value is the space the call would have used, which sizes the log of the handle's next call).  Such rows
+// go to fbList, *fbCount counts them, and they leave their chunk as they found it.
+constexpr int MD_CHUNK = 4096;                 // log ints per reservation: at least two rows at the largest cap (bd_cap(2048) = 1792),
+                                               // about 50 rows of the headline matrix (60 re-hits per row on average)
+struct MidLogArgs {
+  int2* meta;                                  // per ROW ID: {first log entry, re-hits or -1}
+  int* log;
+  long long logCap;                            // ints of `log` (0: none yet -- every row falls back, the demand is still counted)
+  int cap;                                     // re-hits a row may log
+  unsigned long long* cursor;                  // next unreserved int of the log
+  int* fbList;
+  int* fbCount;
+  unsigned long long* logged;                  // sum of the re-hits of the rows that stay direct (test hook)
+};
+
+template <int NW, int TBL, int U, bool LOG = false>
 __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ binPtr, int bin,
                                                          const int* __restrict__ rowIds,
                                                          const int* __restrict__ IA, const int2* __restrict__ SBL,
                                                          const int* __restrict__ JB,
                                                          const int* __restrict__ rowFlops, int* __restrict__ IC,
-                                                         int* __restrict__ err, int* __restrict__ qctr) {
+                                                         int* __restrict__ err, int* __restrict__ qctr, MidLogArgs ml) {
+  static_assert(!LOG || NW > 1, "only the multi-wave kernels log");
   __shared__ __attribute__((aligned(16))) int keys[TBL];
   __shared__ typename WalkSel<NW>::type st;
   __shared__ int cnt_s;
   __shared__ int qslot;
+  __shared__ int logCnt_s, logOvf_s;             // LOG: re-hits of the current row so far; the row passed the cap
+  __shared__ unsigned long long chunk_s;         // LOG: the chunk reserved last
+  // LOG, block-uniform: first int of the block's chunk, ints of it in use (MD_CHUNK: none reserved yet), re-hits of direct rows
+  unsigned long long chunkStart = 0ull;
+  int cursor = MD_CHUNK;
+  unsigned long long loggedSum = 0ull;
   const int tid = threadIdx.x, lane = lane_id();
   if (tid < WAVE) st.dummy[tid] = DUMMY_SLOT;    // (ordered before the first insert by the barrier / wave order below)
   int first = binPtr[bin], count = binPtr[bin + 1] - first;
@@ -1376,11 +1415,48 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
     const int shift = 32 - log2_pow2(size);
     clear_table(keys, nullptr, size, tid, WAVE * NW);
     if (tid == 0) cnt_s = 0;
+    const bool newChunk = LOG && cursor + ml.cap > MD_CHUNK;   // block-uniform: the chunk may not hold another row
+    if constexpr (LOG) if (tid == 0) {
+      logCnt_s = 0; logOvf_s = 0;
+      if (newChunk) chunk_s = atomicAdd(ml.cursor, (unsigned long long)MD_CHUNK);
+    }
     __syncthreads();
+    if constexpr (LOG) if (newChunk) { chunkStart = chunk_s; cursor = 0; }
+    // (chunk_s is written again at the start of a later row, behind this row's barriers)
+    const bool logging = LOG && chunkStart + (unsigned long long)MD_CHUNK <= (unsigned long long)ml.logCap;
+    int* const myLog = LOG && logging ? ml.log + chunkStart + cursor : nullptr;
+    const int room = LOG ? min(ml.cap, MD_CHUNK - cursor) : 0;   // (= cap; the chunk bounds every store whatever cap is)
     int mine = 0;
     for_each_product<NW, U, false>(st, cur.as, cur.ae, SBL, nullptr, JB, nullptr,
                                    [&](const auto& act, const auto& col, const auto& val, int) {
+      if constexpr (!LOG)
       mine += hash_insert_chunked<InsChunk<NW>::value>(keys, size, shift, act, col, reinterpret_cast<int*>(&st.dummy[lane_id()]), err);
+      else {
+        constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
+        bool rehit[R];
+        mine += hash_insert_chunked<InsChunk<NW>::value, true>(keys, size, shift, act, col,
+                                                               reinterpret_cast<int*>(&st.dummy[lane_id()]), err, &rehit);
+        if (logging) {                                   // block-uniform
+          unsigned long long mk[R];
+          int tot = 0;
+#pragma unroll
+          for (int u = 0; u < R; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
+          if (tot) {                                     // wave-uniform
+            int base = 0;
+            if (lane_id() == 0) base = atomicAdd(&logCnt_s, tot);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + tot > room) {                     // wave-uniform: a row for the fallback kernel
+              if (lane_id() == 0) logOvf_s = 1;
+            } else {
+#pragma unroll
+              for (int u = 0; u < R; ++u) {              // cursor + base + tot <= cursor + room <= MD_CHUNK
+                if (rehit[u]) myLog[base + mask_rank(mk[u])] = col[u];
+                base += __popcll(mk[u]);
+              }
+            }
+          }
+        }
+      }
     }, pc, err);
     const int ws = wave_sum(mine);                           // hash_insert_multi counts per lane
     if (NW == 1) {
@@ -1389,12 +1465,24 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
       if (lane == 0 && ws) atomicAdd(&cnt_s, ws);
       __syncthreads();
       if (tid == 0) IC[cur.row] = cnt_s;
+      if constexpr (LOG) {
+        const int logged = logCnt_s;                     // (reset at the start of the next row, behind the barrier below)
+        const int rehits = cur.x0 - cnt_s;               // what the row logs when it has room
+        const bool direct = logging && !logOvf_s;        // then logged <= room <= cap
+        if (tid == 0) {
+          ml.meta[cur.row] = make_int2((int)chunkStart + cursor, direct ? logged : -1);
+          if (!direct) ml.fbList[atomicAdd(ml.fbCount, 1)] = cur.row;
+        }
+        if (direct) { cursor += logged; loggedSum += (unsigned long long)logged; }
+        else if (!logging && rehits >= 0 && rehits <= ml.cap) cursor += rehits;   // no log yet: count the demand
+      }
     }
     __syncthreads();
     cur = nxt;
     if (NW == 1) { nxt = nn; pc = pn; }
     q = qn;
   }
+  if constexpr (LOG) if (tid == 0 && loggedSum) atomicAdd(ml.logged, loggedSum);
 }
 
 template <int NW, int TBL, int U, int PRUNE = 0>      // PRUNE: see k_num_g16
@@ -1486,7 +1574,8 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
       continue;
     }
     if constexpr (NW > 1 && PRUNE == 0) if (want == cur.x2) {
-      // several waves per row, no repeated column (77 % of the rows of 513-1024 products on a power-law matrix): expanded
+      // several waves per row, no repeated column (16 % of the rows of 513-1024 products on the headline power-law matrix,
+      // 13 % and 6 % of the two classes above): expanded
       // like the wave-per-row case, positions from the walk's dense product numbering
       int* const JCrow = JC + off;
       float* const Crow = C + off;
@@ -2201,6 +2290,165 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restri
       });
       // (the walk ends with a barrier behind its last LDS atomics)
       emit_claimed<S / NW / WAVE>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
+      __syncthreads();
+      if (tid == 0 && sh.emitted != want) atomicOr(err, ERRF_COUNT_MISMATCH);
+      __syncthreads();
+    }
+    cur = nxt;
+    q = qn;
+  }
+}
+
+// numeric, bins 6-7 (513-4096 products) of a float product whose symbolic pass logged (k_sym_hash<.., true>): the scheme of
+// k_num_bigdirect with a table of at most S slots (1024: 8 KB, where k_num_hash clears, fills and sweeps 16-64 KB per row).
+// A row is taken with 0 <= re-hits <= cap <= bd_cap(S); rows with count -1 are skipped, they are in the bin's fallback list
+// that k_num_hash runs over.  A row without any repeated column (IC range = products) is expanded as in k_num_hash: no table,
+// positions from the walk's dense numbering, which lives in the table's memory.
+#ifndef SMF_MD_U
+#define SMF_MD_U 4
+#endif
+constexpr int MD_U = SMF_MD_U;                  // rounds in flight per wave, as in k_num_bigdirect (2 measured the same)
+template <int NW, int S>
+struct MidDirectShared {
+  slot_t tab[S];
+  WalkStageN<NW> st;
+  int qslot;
+  int emitted;
+};
+struct MidMeta { RowMeta m; int ls, lc; };              // + first log entry, re-hits (-1: not a row of this kernel)
+__device__ __forceinline__ MidMeta load_meta_mid(const int* rows, int q, int count, const int* IA, const int* IC,
+                                                 const int* rowFlops, const int2* meta, int cap) {
+  MidMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
+  if (q < count) {
+    const int row = rows[q];
+    const int2 lm = meta[row];
+    if (lm.y >= 0 && lm.y <= cap) { d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC, rowFlops); }
+  }
+  return d;
+}
+
+template <int NW, int S>
+__global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restrict__ binPtr, int bin,
+                                                             const int* __restrict__ rowIds,
+                                                             const int* __restrict__ IA, const int2* __restrict__ SBL,
+                                                             const float* __restrict__ VA,
+                                                             const int* __restrict__ JB,
+                                                             const float* __restrict__ VB,
+                                                             const int* __restrict__ IC, int* __restrict__ JC,
+                                                             float* __restrict__ C, int* __restrict__ err,
+                                                             int* __restrict__ qctr, const int* __restrict__ rowFlops,
+                                                             const int2* __restrict__ meta, const int* __restrict__ mlog,
+                                                             long long logCap, int cap) {
+  constexpr int T = WAVE * NW;
+  static_assert(S % T == 0 && S / T <= 8, "every wave sweeps whole 64-slot steps");
+  static_assert(sizeof(WalkNumber<NW>) <= S * sizeof(slot_t), "the numbering of an expanded row lives in the table");
+  __shared__ __attribute__((aligned(16))) MidDirectShared<NW, S> sh;
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  const int first = binPtr[bin], count = binPtr[bin + 1] - first;
+  const int* rows = rowIds + first;
+  cap = min(cap, bd_cap(S));                           // a probe always ends at an empty slot
+  if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
+  constexpr int QB = NW >= 8 ? 2 : 4;                  // rows per dequeue, as in k_num_hash
+  int q = next_row<QB>(qctr, &sh.qslot, -1);
+  MidMeta cur = load_meta_mid(rows, q, count, IA, IC, rowFlops, meta, cap);
+  while (q < count) {
+    const int qn = next_row<QB>(qctr, &sh.qslot, q);
+    const MidMeta nxt = load_meta_mid(rows, qn, count, IA, IC, rowFlops, meta, cap);
+    const int as = cur.m.as, ae = cur.m.ae;
+    const int outBase = cur.m.x0, outEnd = cur.m.x1;
+    const int want = outEnd - outBase;
+    int* const JCrow = JC + outBase;
+    float* const Crow = C + outBase;
+    const unsigned lim = (unsigned)max(want, 0);       // every store stays inside the row's own range
+    // (block-uniform branches; a row's log must lie inside the log whatever the metadata says)
+    const bool mine = cur.lc >= 0 && (long long)cur.ls >= 0 && (long long)cur.ls + cur.lc <= logCap;
+    if (mine && want == cur.m.x2) {
+      for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
+                                       [&](const bool (&act)[MD_U], const int (&col)[MD_U], const float (&val)[MD_U], int p0) {
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+          const unsigned o = (unsigned)(p0 + u * WAVE + lane);
+          if (act[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+        }
+      }, PreA{0, 0, 0.f, false}, err, reinterpret_cast<WalkNumber<NW>*>(sh.tab));
+    } else if (mine) {
+      const int lc = cur.lc;
+      // four slots per logged re-hit when that fits (the clear and the sweep are what a small table saves)
+      const int size = table_size<4>(lc, T, S);
+      const int shift = 32 - log2_pow2(size);
+      const int per = size / NW;
+      clear_slots(sh.tab, size, tid, T);
+      if (tid == 0) sh.emitted = 0;
+      __syncthreads();
+      {                                                // the row's log: distinct keys <= lc <= cap < S, or size >= 4 * lc
+        const int* const lg = mlog + cur.ls;
+        const unsigned mask = (unsigned)size - 1u;
+        for (int i = tid; i < lc; i += T) {
+          const int c = lg[i];
+          const slot_t own = make_slot(c, -0.0f);
+          unsigned h = ((unsigned)c * 2654435761u) >> shift;
+          for (int probe = 0; probe < size; ++probe) {
+            const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, own);
+            if (old == EMPTY_SLOT || slot_key(old) == c) break;
+            h = (h + 1u) & mask;
+          }
+        }
+      }
+      __syncthreads();
+      for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
+                                       [&](const bool (&act)[MD_U], const int (&col)[MD_U], const float (&val)[MD_U], int) {
+        char* const base = reinterpret_cast<char*>(sh.tab);
+        const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
+        const int maskB = size * 8 - 1;
+        int hB[MD_U], hitB[MD_U];                       // byte offsets; dumB = "done" / "no hit"
+        bool miss[MD_U];
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) {
+          const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
+          hB[u] = act[u] ? (int)(h * 8u) : dumB;
+          hitB[u] = dumB;
+          miss[u] = false;
+        }
+        for (int probe = 0;;) {                         // the keys do not change during the walk: plain reads
+          int key[MD_U];
+#pragma unroll
+          for (int u = 0; u < MD_U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
+          ++probe;
+          int pendBits = 0;
+#pragma unroll
+          for (int u = 0; u < MD_U; ++u) {
+            const bool pend = hB[u] != dumB;
+            const bool hit = pend && key[u] == col[u];
+            const bool emp = pend && key[u] == EMPTY_KEY;
+            hitB[u] = hit ? hB[u] : hitB[u];
+            miss[u] = miss[u] || emp;
+            hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the insert above
+            pendBits |= hB[u] ^ dumB;
+          }
+          if (ballot64(pendBits != 0) == 0ull) break;
+          if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
+        }
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u)
+          if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
+        unsigned long long mk[MD_U];
+        int tot = 0;
+#pragma unroll
+        for (int u = 0; u < MD_U; ++u) { mk[u] = ballot64(miss[u]); tot += __popcll(mk[u]); }
+        if (tot) {                                      // wave-uniform
+          int pos = 0;
+          if (lane == 0) pos = atomicAdd(&sh.emitted, tot);
+          pos = __builtin_amdgcn_readfirstlane(pos);
+#pragma unroll
+          for (int u = 0; u < MD_U; ++u) {
+            const unsigned o = (unsigned)(pos + mask_rank(mk[u]));
+            if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+            pos += __popcll(mk[u]);
+          }
+        }
+      });
+      // (the walk ends with s_waitcnt lgkmcnt(0) and a barrier behind its last LDS atomics)
+      emit_claimed<S / T>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
       __syncthreads();
       if (tid == 0 && sh.emitted != want) atomicOr(err, ERRF_COUNT_MISMATCH);
       __syncthreads();

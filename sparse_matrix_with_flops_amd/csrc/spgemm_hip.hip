@@ -221,7 +221,7 @@ struct HostMirror {                 // one small device block + its pinned host 
   // work-queue heads of the block-per-row kernels (zeroed with the rest per call).  One 128-byte line EACH: the kernels
   // of a phase run side by side and every dequeue is an atomic on its word -- eight words in one line (next to binPtr /
   // slotBase, which every block reads when it starts) made all of them queue up behind one another in the L2.
-  alignas(128) int qctr[9 * 32];
+  alignas(128) int qctr[10 * 32];
   alignas(128) int qpad_;
   int slotBase[NSLOTS + 1];         // first position of every layout slot in rowIds, [NSLOTS] = m (k_bin_scan)
   unsigned long long totalP;
@@ -234,6 +234,12 @@ struct HostMirror {                 // one small device block + its pinned host 
   // big rows of a logging symbolic pass (k_sym_big<true>) that stay with k_num_bighash: {0, rows}, read by that kernel as
   // the "bin" of the fallback list (spgemm_handle::bigFallback)
   alignas(128) int fbBin[2];
+  // the same for the rows of bins 6 and 7 that a logging k_sym_hash leaves to k_num_hash: {0, rows} of bin 6, {0, rows} of
+  // bin 7 (lists: spgemm_handle::midFallback); then the log cursor (ints reserved, whether the log had them or not) and the
+  // re-hits logged by the rows that stay direct
+  alignas(128) int fbMid[4];
+  alignas(128) unsigned long long mrCursor;
+  unsigned long long mrLogged[2];   // (bin 6, bin 7)
   alignas(128) int fbPad_;
 };
 
@@ -302,6 +308,27 @@ struct spgemm_handle {
   int* bigFallback = nullptr;        // rows of the fallback list (workspace block, one int per row of A)
   bool bdLogged = false;             // the pending / current product's symbolic pass logged (launch_symbolic)
   bool bdRan = false;                // the latest numeric launch used k_num_bigdirect
+  // direct kernel of bins 6-7 (513-4096 products, float, any n): k_sym_hash<.., true> logs the rows' re-hit columns into mrLog
+  // (mr_cap ints, handed out in chunks from HostMirror::mrCursor) and {first entry, count} into mrMeta[row id].  The log is
+  // sized from the previous call's cursor (grow_midrow_log): a handle's first call with such rows finds none, counts what it
+  // would have used and keeps today's kernels for all of them.
+  bool midDirect = true;             // SPGEMM_MIDDIRECT=0: bins 6-7 keep k_sym_hash / k_num_hash as they were
+  int mdCfg = -1;                    // SPGEMM_MD_CFG: waves x table slots of k_num_middirect {0: 4x1024, 1: 8x1024, 2: 4x2048, 3: 8x2048} for
+                                     // both bins; default: 4x1024 for bin 6 and 8x1024 for bin 7, the waves of their hash kernels
+                                     // (measured: profiles/README.md; four waves are too few for a row of 2049-4096 products when the
+                                     // bin has only one or two rows per resident block)
+  int mdCap = 0;                     // re-hits a row may log: bd_cap(slots), or less with SPGEMM_MD_CAP (tests)
+  int mdMinRows = 0;                 // SPGEMM_MD_MINROWS: a bin with fewer rows keeps k_num_hash for all of them.  Default: 4 x the CU count --
+                                     // below it every row of the bin is resident at once in either kernel, the launch lasts as long as
+                                     // its slowest row, and a row with many re-hits is slower direct than hashed (web surrogate, 862
+                                     // rows of 2049-4096 products with 30-50 % re-hits: 0.033 -> 0.066 ms); the tests set 1
+  long long mrLogEnv = 0;            // SPGEMM_MRLOG: ints of the log instead of the computed size (tests run it out of space)
+  int2* mrMeta = nullptr;            // workspace block, one pair per row of A
+  int* midFallback = nullptr;        // workspace block, two ints per row of A: bin 6's list, then (at cap_m) bin 7's
+  int* mrLog = nullptr;
+  long long mr_cap = 0;
+  bool mdLogged = false;             // the pending / current product's symbolic pass logged bins 6-7
+  bool mdRan[2] = {false, false};    // the latest numeric launch used k_num_middirect for bin 6 / bin 7
   int h1sym = 32;                    // blocks per CU of the wave-per-row symbolic kernel (SPGEMM_H1SYM, experiments)
   int h1num = 24;                    // ... of the wave-per-row numeric kernel on its 512-slot tables (SPGEMM_H1NUM)
   spgemm_stats stats;
@@ -317,7 +344,7 @@ static std::map<int, int> g_handles_on;          // device -> live handles (the 
 
 // the workspace blocks sized by the row count: where each pointer lives and its bytes for `cap` rows
 struct WsBlock { void** ptr; size_t bytes; };
-static std::array<WsBlock, 10> ws_blocks(spgemm_handle* h, size_t cap) {
+static std::array<WsBlock, 12> ws_blocks(spgemm_handle* h, size_t cap) {
   const size_t nblk = (cap + K1_THREADS - 1) / K1_THREADS;
   const size_t ntile = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE + 1;
   return {{{(void**)&h->rowFlops, sizeof(int) * cap},
@@ -328,6 +355,8 @@ static std::array<WsBlock, 10> ws_blocks(spgemm_handle* h, size_t cap) {
            {(void**)&h->tileSum, sizeof(unsigned long long) * ntile},
            {(void**)&h->blockP, sizeof(unsigned long long) * nblk},
            {(void**)&h->bigFallback, sizeof(int) * cap},
+           {(void**)&h->mrMeta, sizeof(int2) * cap},
+           {(void**)&h->midFallback, sizeof(int) * 2 * cap},
            {(void**)&h->batchStart, sizeof(int) * (3 * cap + 64)},
            {(void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)}}};
 }
@@ -371,6 +400,19 @@ static auto with_bd_cfg(int cfg, F f) {
   }
 }
 static int bd_cap_of(int cfg) { return bd_cap(cfg == 2 || cfg == 3 ? 8192 : 4096); }
+// ... and k_num_middirect's
+template <class F>
+static auto with_md_cfg(int cfg, F f) {
+  typedef std::integral_constant<int, 4> W4; typedef std::integral_constant<int, 8> W8;
+  typedef std::integral_constant<int, 1024> S1; typedef std::integral_constant<int, 2048> S2;
+  switch (cfg) {
+    case 1: return f(W8(), S1());
+    case 2: return f(W4(), S2());
+    case 3: return f(W8(), S2());
+    default: return f(W4(), S1());
+  }
+}
+static int md_slots_of(int cfg) { return cfg >= 2 ? 2048 : 1024; }
 
 // an integer knob of the handle from the environment; a value outside [lo, hi] is ignored
 static void env_int(const char* name, int lo, int hi, int* field) {
@@ -416,6 +458,13 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   h->bdMinRows = h->numCU;
   env_int("SPGEMM_BD_MINROWS", 1, 1 << 30, &h->bdMinRows);
   env_int("SPGEMM_RLREGION", 64, 1 << 24, &h->rlRegionEnv);
+  { int v = 1; env_int("SPGEMM_MIDDIRECT", 0, 1, &v); h->midDirect = v != 0; }
+  env_int("SPGEMM_MD_CFG", 0, 3, &h->mdCfg);
+  h->mdCap = bd_cap(md_slots_of(h->mdCfg));
+  env_int("SPGEMM_MD_CAP", 0, h->mdCap, &h->mdCap);
+  h->mdMinRows = 4 * h->numCU;
+  env_int("SPGEMM_MD_MINROWS", 1, 1 << 30, &h->mdMinRows);
+  { int v = 0; env_int("SPGEMM_MRLOG", 1, 1 << 30, &v); h->mrLogEnv = v; }
   env_int("SPGEMM_PATH", 0, 2, &h->pathMode);
   env_int("SPGEMM_CHAIN_CFG", INT_MIN, INT_MAX, &h->chainCfg);   // unchecked: chain_cfg() maps anything else to 0
   { int u = h->U; env_int("SPGEMM_U", 2, 8, &u); if (u == 2 || u == 4 || u == 8) h->U = u; }
@@ -454,6 +503,7 @@ extern "C" int spgemm_hip_destroy(spgemm_handle* h) {
   hipFree(h->spill);
   hipFree(h->rlMeta);
   hipFree(h->rlLog);
+  hipFree(h->mrLog);
   hipFree(h->sbl);
   hipFree(h->dsmall);
   hipHostFree(h->hsmall);
@@ -492,6 +542,26 @@ extern "C" int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows,
   *direct_rows = nbig - *fallback_rows;
   *rehit_cap = bd_cap_of(h->bdCfg);
   *region_ints = h->rl_region;
+  return SPGEMM_OK;
+}
+
+// ... and its rows of 513-4096 products (bins 6-7) between k_num_middirect (expanded rows included) and k_num_hash
+extern "C" int spgemm_hip_debug_midrow_paths(spgemm_handle* h, int* rows, int* direct_rows, int* fallback_rows, int* rehit_cap) {
+  if (!h || !rows || !direct_rows || !fallback_rows || !rehit_cap) return fail(SPGEMM_ERR_ARG, "null argument");
+  *rows = h->mirror.binPtr[8] - h->mirror.binPtr[6];
+  *fallback_rows = 0;
+  for (int b = 0; b < 2; ++b) *fallback_rows += h->mdRan[b] ? h->mirror.fbMid[2 * b + 1] : h->mirror.binPtr[7 + b] - h->mirror.binPtr[6 + b];
+  *direct_rows = *rows - *fallback_rows;
+  *rehit_cap = h->mdCap;
+  return SPGEMM_OK;
+}
+// ... with the log behind it: re-hits logged by the direct rows, ints the call reserved (or would have), ints the log had
+extern "C" int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, long long* reserved, long long* capacity) {
+  if (!h || !logged || !reserved || !capacity) return fail(SPGEMM_ERR_ARG, "null argument");
+  *logged = 0;
+  for (int b = 0; b < 2; ++b) if (h->mdRan[b]) *logged += (long long)h->mirror.mrLogged[b];
+  *reserved = h->mdLogged ? (long long)h->mirror.mrCursor : 0;
+  *capacity = h->mr_cap;
   return SPGEMM_OK;
 }
 
@@ -704,6 +774,8 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
   const int2* sbl = h->sbl;
   // logBig: a float product's big rows may take k_num_bigdirect -- the symbolic kernel logs their re-hit columns
   h->bdLogged = logBig && h->bigDirect && n > BIG_WC && m > 0;
+  // ... and its rows of bins 6-7 k_num_middirect, for any n (the plain pipeline with its default rounds in flight only)
+  h->mdLogged = logBig && h->midDirect && m > 0 && minBin == 0 && h->pathMode == 0 && h->U == 2;
   if (m <= 0) return SPGEMM_OK;
   clear_stale_hip_error();
   const int* bp = h->dsmall->binPtr;
@@ -722,20 +794,33 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
       hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
                          rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
                          (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr); }
+  // the logging variants of the two launches below: one log and one cursor for both, a fallback list each
+  auto mid_log = [&](int which) {
+    return MidLogArgs{h->mrMeta, h->mrLog, h->mrLog ? h->mr_cap : 0ll, h->mdCap, &h->dsmall->mrCursor,
+                      h->midFallback + (which ? h->cap_m : 0), &h->dsmall->fbMid[2 * which + 1], &h->dsmall->mrLogged[which]};
+  };
   if (minBin <= 7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_SYM_HASH8, st);
+    if (h->mdLogged)
+      hipLaunchKernelGGL((k_sym_hash<8, 8192, 2, true>), dim3(clampi(m, 1, cu * 3)), dim3(512), 0, st, bp, 7, rowIds, dIA,
+                         sbl, dJB, h->rowFlops, dIC, err, qc + 1 * 32, mid_log(1));
+    else
     LAUNCH_U(k_sym_hash, 8, 8192, dim3(clampi(m, 1, cu * 3)), dim3(512), st, bp, 7, rowIds, dIA,
-             sbl, dJB, h->rowFlops, dIC, err, qc + 1 * 32); }
+             sbl, dJB, h->rowFlops, dIC, err, qc + 1 * 32, MidLogArgs{}); }
   if (minBin <= 6) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_SYM_HASH4, st);
     // (one launch for both layout slots of bin 6: split like the numeric side it measured 15 % slower)
+    if (h->mdLogged)
+      hipLaunchKernelGGL((k_sym_hash<4, 4096, 2, true>), dim3(clampi(m, 1, cu * 8)), dim3(256), 0, st, bp, 6, rowIds, dIA,
+                         sbl, dJB, h->rowFlops, dIC, err, qc + 2 * 32, mid_log(0));
+    else
     LAUNCH_U(k_sym_hash, 4, 4096, dim3(clampi(m, 1, cu * 8)), dim3(256), st, bp, 6, rowIds, dIA,
-             sbl, dJB, h->rowFlops, dIC, err, qc + 2 * 32); }
+             sbl, dJB, h->rowFlops, dIC, err, qc + 2 * 32, MidLogArgs{}); }
   if (minBin <= 5) { hipStream_t st = h->side[1]; KTimer t(h, SPGEMM_K_SYM_HASH1, st);
     const int* sb = h->dsmall->slotBase;         // bin 5 = two layout slots: table 512 up to 256 products, 1024 above
     if (!skipH1A)
     LAUNCH_U(k_sym_hash, 1, 512, dim3(grid8(m, cu * h->h1sym)), dim3(64), st, sb, SLOT_H1A, rowIds, dIA,
-             sbl, dJB, h->rowFlops, dIC, err, qc + 3 * 32);
+             sbl, dJB, h->rowFlops, dIC, err, qc + 3 * 32, MidLogArgs{});
     LAUNCH_U(k_sym_hash, 1, 1024, dim3(grid8(m, cu * h->h1sym)), dim3(64), st, sb, SLOT_H1B, rowIds, dIA,
-             sbl, dJB, h->rowFlops, dIC, err, qc + 3 * 32); }
+             sbl, dJB, h->rowFlops, dIC, err, qc + 3 * 32, MidLogArgs{}); }
   if (minBin <= 4) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_SYM_G16, st);
     hipLaunchKernelGGL((k_sym_g16<128, 4>), dim3(grid8(cdiv(m, 16), cu * 16)), dim3(256), 0, st, bp, 4, 5,
                        rowIds, dIA, sbl, dJB, h->rowFlops, dIC, err); }
@@ -810,10 +895,34 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
     if (pcnt) hipLaunchKernelGGL(k_rmcl_fix_rows, dim3(clampi(rows(8, 9), 1, cu * 8)), dim3(256), 0, st,
                                  bp, 8, 9, rowIds, dIC, dJC, dC, pcnt);
   }
-  if (rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
+  // bins 6-7 of a product whose symbolic pass logged into a log that exists: k_num_middirect over the bin for the rows with
+  // a log, k_num_hash (the larger table of the bin) over the bin's fallback list for the others -- its length is on the
+  // device only, the launch is sized by the bin and a few blocks.  Both launches are timed under the bin's id.  (No log
+  // yet, or a bin of fewer than mdMinRows rows: today's launches run over the bin itself.)
+  const bool mid = h->mdLogged && h->mrLog && !pcnt && minBin <= 6;
+  const bool mid6 = mid && rows(6, 7) >= h->mdMinRows, mid7 = mid && rows(7, 8) >= h->mdMinRows;
+  h->mdRan[0] = mid6; h->mdRan[1] = mid7;
+  auto launch_mid = [&](int bin, int nrows, int* qd, hipStream_t st) {
+    with_md_cfg(h->mdCfg >= 0 ? h->mdCfg : bin == 7 ? 1 : 0, [&](auto nw, auto slots) {
+      const int lds = (int)sizeof(MidDirectShared<nw, slots>);
+      const int perCU = std::max(1, std::min((160 * 1024) / lds, 32 / (int)nw));
+      hipLaunchKernelGGL((k_num_middirect<nw, slots>), dim3(clampi(nrows, 1, cu * perCU)), dim3(WAVE * nw), 0, st,
+                         bp, bin, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qd, (const int*)h->rowFlops,
+                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, h->mdCap);
+      return 0; });
+  };
+  if (mid7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
+    launch_mid(7, rows(7, 8), qc + 9 * 32, st);
+    LAUNCH_U(k_num_hash, 8, 8192, dim3(clampi(rows(7, 8), 1, cu * 2)), dim3(512), st, h->dsmall->fbMid + 2, 0,
+             (const int*)(h->midFallback + h->cap_m), dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 5 * 32, h->rowFlops, (int*)nullptr); }
+  if (mid6) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
+    launch_mid(6, rows(6, 7), qc + 6 * 32, st);
+    LAUNCH_U(k_num_hash, 4, 4096, dim3(clampi(rows(6, 7), 1, cu * 4)), dim3(256), st, h->dsmall->fbMid, 0,
+             (const int*)h->midFallback, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 7 * 32, h->rowFlops, (int*)nullptr); }
+  if (!mid7 && rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
     LAUNCH_NUM(8, 8192, dim3(clampi(rows(7, 8), 1, cu * 2)), dim3(512), st, bp, 7,
              rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 5 * 32, h->rowFlops); }
-  if (rows(6, 7) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
+  if (!mid6 && rows(6, 7) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
     const int* sb = h->dsmall->slotBase;
     const int* hs_ = h->mirror.slotBase;
     const int na = hs_[SLOT_H4A + 1] - hs_[SLOT_H4A], nb = hs_[SLOT_H4B + 1] - hs_[SLOT_H4B];
@@ -1038,6 +1147,21 @@ static void grow_rehit_log(spgemm_handle* h, int n) {
   }
 }
 
+// room for the re-hit log of bins 6-7 next time: what this call's symbolic pass reserved from the cursor -- or would have,
+// had the log been there -- plus a quarter, since the dynamic queue deals the rows to the blocks differently every time and
+// every block leaves the tail of its last chunk unused.  (Headline matrix: 4.1 M re-hits in 68 K rows.)
+static void grow_midrow_log(spgemm_handle* h) {
+  const int* hb = h->mirror.binPtr;
+  if (!h->mdLogged || std::max(hb[7] - hb[6], hb[8] - hb[7]) < h->mdMinRows) return;   // (too few rows: the log would not be used)
+  const long long used = (long long)std::min<unsigned long long>(h->mirror.mrCursor, 1ull << 30);
+  if (used == 0 || (h->mrLog && (h->mrLogEnv > 0 || used <= h->mr_cap))) return;
+  hipFree(h->mrLog);
+  h->mrLog = nullptr; h->mr_cap = 0;
+  const long long want = h->mrLogEnv > 0 ? h->mrLogEnv : std::min<long long>(used + used / 4 + 16 * MD_CHUNK, 1ll << 30);
+  if (hipMalloc((void**)&h->mrLog, (size_t)want * sizeof(int)) == hipSuccess) h->mr_cap = want;
+  else (void)hipGetLastError();
+}
+
 // ---- double values (spgemm_f64_device.hpp): the numeric phase only; classification, symbolic pass and scan are the
 // float pipeline's.  One launch per bin, on the side streams launch_numeric uses, each timed into its bin's slot of
 // spgemm_stats.ms_kernel.  Rows of bin 8 wider than the multi-pass LDS kernel takes get device-memory tables: their largest
@@ -1149,7 +1273,7 @@ static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
   collect_kernel_times(h, false);
-  if (isFloat) { grow_bitmaps(h, n); grow_rehit_log(h, n); }
+  if (isFloat) { grow_bitmaps(h, n); grow_rehit_log(h, n); grow_midrow_log(h); }
   return done(SPGEMM_OK);
 }
 
@@ -1259,6 +1383,7 @@ static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInP
   publish_stats(h, hm, StatsForm::OneShot);
   grow_bitmaps(h, p.n);
   grow_rehit_log(h, p.n);
+  grow_midrow_log(h);
   h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = (long long)hm.nnzC64;
   *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = (int)hm.nnzC64;
   return SPGEMM_OK;
@@ -1894,6 +2019,7 @@ static int rmcl_size_rows_by_products(spgemm_handle* h, const CsrView& A, const 
   if (nbig > 0) {
     KTimer t(h, SPGEMM_K_SYM_BIG, s);
     h->bdLogged = false;
+    h->mdLogged = false;
     hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
                        h->dsmall->binPtr, 8, h->cur_rowIds, A.I, h->sbl, B.J, n, dIC, h->bigBitmaps, h->bm_cap,
                        h->dsmall->qctr + 0 * 32, (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr);
