@@ -338,9 +338,15 @@ int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, long long* 
 #define SPGEMM_COO_ABS            8   /* |value|                                                      */
 int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const float* dVal,
                    int flags, int** dIA, int** dJA, float** dA, int* nnzOut);
+/* The same for QValue double (the reference's FDOUBLE build): same flags, errors and outputs.  A run of equal (row,col) is
+ * summed by one lane, left to right in input order, in double (bit-exact with the CPU loop); ABS is fabs of that sum;
+ * ROW_NORMALISE writes the double 1.0 / count (nlibs/CSR.cc:92), not the float quotient widened; an appended self loop is
+ * 1.0.  Nothing on the way narrows to float. */
+int hip_coo_to_csr_f64(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const double* dVal,
+                       int flags, int** dIA, int** dJA, double** dA, int* nnzOut);
 
 /* ---- the text in front of that step: edge lines "from to [value]" -> device COO, a file -> device CSR ---------------------
- * Replaces, for float values and line-oriented files, the text half of COO::readSNAPFile (nlibs/COO.cc:48-158): the lines
+ * Replaces, for line-oriented files, the text half of COO::readSNAPFile (nlibs/COO.cc:48-158): the lines
  * are cut and converted by kernels, with the conversions sscanf("%d%d%f") performs, bit for bit.  A line holding a number
  * the device scanner does not promise to convert like the C library (csrc/edge_scan.hpp: 19 or more digits in an index;
  * inf / nan / hex; more than 2^53 in the digits or a decimal exponent beyond +-22; a value half-way between two floats) is
@@ -350,8 +356,13 @@ int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRo
  * beyond `declared` are never parsed.  A line ends at '\n'; a NUL byte inside a line ends that line's string; a last line
  * without '\n' counts.  (fgets cuts lines at 1024 characters in the reference; here, as in COO::readSNAPFile of the
  * mirror, a line ends at its newline.)
- * Not covered (they stay on the host loader): symmetric MatrixMarket files (a token stream, not lines), QValue double,
- * texts above 2 GiB.
+ * The _f64 entries do the same for QValue double (sscanf("%d%d%lf"), nlibs/COO.cc:101-105,132-136) with strtod's 64 bits.
+ * Their value scanner reads the same tokens and converts, exactly and without a floating-point operation, every value
+ * with at most 19 significant digits (leading zeros not counted) and |e10| <= 27, e10 = exponent - fraction digits: zero
+ * digits are +-0.0, the rest is w * 5^e10 * 2^e10 rounded once to nearest-even in 128-bit integers.  20 or more digits, a
+ * larger |e10|, inf / nan / hex are slow and go through strtod on the host.  A float midpoint or a 17-digit value is fast
+ * there.
+ * Not covered (they stay on the host loader): symmetric MatrixMarket files (a token stream, not lines), texts above 2 GiB.
  * h == NULL = the default handle; a call returns after the device work has completed; st may be NULL.  Argument checks
  * (a null output, null text with nbytes > 0, an unknown flag bit, a misaligned device text -> SPGEMM_ERR_ARG;
  * nbytes > INT32_MAX -> SPGEMM_ERR_OVERFLOW) run before any device is touched.  On any error the outputs are NULL, the
@@ -378,14 +389,25 @@ int hip_edge_text_header(const char* text, size_t nbytes, int* rows, int* cols, 
  * room for *entries triplets in line order (release with spgemm_hip_free; never NULL on success). */
 int hip_parse_edge_lines(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
                          int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st);
+/* double values: the fast class above (<= 19 significant digits, |e10| <= 27; the rest through strtod on the host), a
+ * missing value is 1.0; the triplets stay in line order, nothing is summed here */
+int hip_parse_edge_lines_f64(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
+                             int** dRow, int** dCol, double** dVal, int* entries, spgemm_edge_stats* st);
 /* the same for HOST text (any alignment): uploaded through the pinned lanes hip_CSR_SpMM uses */
 int hip_parse_edge_text (spgemm_handle* h, const char* text,  size_t nbytes, int declared, int flags,
                          int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st);
+/* double values from HOST text: the same fast class; line order, nothing summed */
+int hip_parse_edge_text_f64 (spgemm_handle* h, const char* text,  size_t nbytes, int declared, int flags,
+                             int** dRow, int** dCol, double** dVal, int* entries, spgemm_edge_stats* st);
 /* readSNAPFile(path, isTrans) + hip_coo_to_csr(cooFlags) with the triplets never on the host: reads the file once, parses
  * its header, hip_parse_edge_text on the rest (ONE_BASED from the banner, TRANSPOSE from isTrans), hip_coo_to_csr.
  * A symmetric MatrixMarket file -> SPGEMM_ERR_INPUT; an unreadable file -> SPGEMM_ERR_ARG. */
 int hip_read_edge_file  (spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
                          int** dIA, int** dJA, float** dA, int* nnz, spgemm_edge_stats* st);
+/* double values: hip_parse_edge_text_f64 (its fast class: <= 19 significant digits, |e10| <= 27) + hip_coo_to_csr_f64
+ * (duplicates summed left to right in input = line order, in double) */
+int hip_read_edge_file_f64(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
+                           int** dIA, int** dJA, double** dA, int* nnz, spgemm_edge_stats* st);
 
 /* ---- workload statistics ----------------------------------------------------
  * std::vector<int> flopsStats(IA, JA, IB, JB, m) (nlibs/tools/stats.cc:29-55, pushToStats :3-12): 13 buckets of the

@@ -13,6 +13,10 @@
 // the entry's value, over exactly the bits the shape needs.  Stable order = input order inside a run of equal
 // (row,col), so duplicates are summed left to right like the CPU loop (bit-exact floats; a run is summed by one lane,
 // which is what keeps the order -- a pair repeated very many times serialises that lane).
+// Generic over the value type V.  The sort's payload is one int: for float it is the value's bits, so the emit step reads
+// keys and values in order; a double does not fit, so for double the payload is the entry's INDEX (nnz + k for the k-th
+// appended self loop) and the emit step gathers dVal[index], an index >= nnz standing for 1.0.  Sums, |.| and 1/count are
+// computed in V.
 // Uses csr_common_device.hpp (the radix sort, scan, Scratch, call prologue).
 #pragma once
 
@@ -34,21 +38,33 @@ __global__ void k_missing_flags(int rows, const unsigned char* __restrict__ hasD
   if (r < rows) miss[r] = hasDiag[r] ? 0 : 1;
 }
 
+// the payload of entry i (i >= nnz: an appended self loop, value 1.0) and the value a sorted payload stands for
+__device__ __forceinline__ int payload_of(const float* __restrict__ val, int nnz, int i) {
+  return __float_as_int(i < nnz ? val[i] : 1.0f);
+}
+__device__ __forceinline__ int payload_of(const double*, int, int i) { return i; }
+__device__ __forceinline__ float value_of(const float*, int, int payload) { return __int_as_float(payload); }
+__device__ __forceinline__ double value_of(const double* __restrict__ val, int nnz, int payload) {
+  return (unsigned)payload < (unsigned)nnz ? val[payload] : 1.0;
+}
+
 // keys of the original entries and of the appended self loops: (row << colBits) | col, same order as row * cols + col
-// without a 64-bit division on the way back.  The payload that travels with a key through the (stable) sort is the
-// entry's VALUE: the emit step then reads keys and values in order instead of gathering values through an index.
+// without a 64-bit division on the way back.  The payload that travels with a key through the (stable) sort is, for
+// float, the entry's VALUE: the emit step then reads keys and values in order instead of gathering values through an
+// index.  For double it is the index (see the top of the file).
+template <class V>
 __global__ void k_make_keys(int nnz, int rows, int colBits, const int* __restrict__ ri, const int* __restrict__ ci,
-                            const float* __restrict__ val, const int* __restrict__ missPos, const int* __restrict__ miss,
+                            const V* __restrict__ val, const int* __restrict__ missPos, const int* __restrict__ miss,
                             unsigned long long* __restrict__ keys, int* __restrict__ payload) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < nnz) {
     keys[i] = ((unsigned long long)(unsigned)ri[i] << colBits) | (unsigned)ci[i];
-    payload[i] = __float_as_int(val[i]);
+    payload[i] = payload_of(val, nnz, i);
   }
   if (miss && i < rows && miss[i]) {            // self loop (i,i,1.0) appended behind the input, in row order
     const int p = nnz + missPos[i];
     keys[p] = ((unsigned long long)(unsigned)i << colBits) | (unsigned)i;
-    payload[p] = __float_as_int(1.0f);
+    payload[p] = payload_of(val, nnz, p);
   }
 }
 
@@ -58,18 +74,19 @@ __global__ void k_heads(int n, const unsigned long long* __restrict__ keys, int 
 }
 
 // one thread per output entry (= head of a run of equal keys): column and summed value (input order inside a run)
+template <class V>
 __global__ void k_emit(int n, int colBits, const unsigned long long* __restrict__ keys, const int* __restrict__ payload,
-                       const int* __restrict__ head, const int* __restrict__ pos,
-                       int dedupe, int useAbs, int* __restrict__ JA, float* __restrict__ A) {
+                       const int* __restrict__ head, const int* __restrict__ pos, const V* __restrict__ val, int nnz,
+                       int dedupe, int useAbs, int* __restrict__ JA, V* __restrict__ A) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !head[i]) return;
   const unsigned long long k = keys[i];
-  float s = __int_as_float(payload[i]);
+  V s = value_of(val, nnz, payload[i]);
   if (dedupe)
-    for (int j = i + 1; j < n && keys[j] == k; ++j) s += __int_as_float(payload[j]);
+    for (int j = i + 1; j < n && keys[j] == k; ++j) s += value_of(val, nnz, payload[j]);
   const int o = pos[i];
   JA[o] = (int)(k & ((1ull << colBits) - 1ull));
-  A[o] = useAbs ? fabsf(s) : s;
+  A[o] = useAbs ? (V)fabs(s) : s;                // fabs of a float is exact in double and back
 }
 
 // rowPtr straight from the sorted keys: IA[r] = output position of the first key of row r or later (binary search, one
@@ -81,24 +98,23 @@ __global__ void k_row_starts(int rows, int n, int colBits, const unsigned long l
   IA[r] = pos[first_at_least(keys, 0, n, (unsigned long long)(unsigned)r << colBits)];
 }
 
-__global__ void k_row_normalise(int rows, const int* __restrict__ IA, float* __restrict__ A) {
+template <class V>
+__global__ void k_row_normalise(int rows, const int* __restrict__ IA, V* __restrict__ A) {
   const int r = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4), gl = threadIdx.x & 15;
   if (r >= rows) return;
   const int s = IA[r], e = IA[r + 1];
-  const float w = (float)(1.0 / (double)(e - s));  // double division, narrowed (nlibs/CSR.cc:88-95)
+  const V w = (V)(1.0 / (double)(e - s));          // double division, narrowed for float (nlibs/CSR.cc:88-95)
   for (int p = s + gl; p < e; p += 16) A[p] = w;
 }
 
-}  // namespace coo
-
-extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol,
-                              const float* dVal, int flags, int** dIA, int** dJA, float** dA, int* nnzOut) {
+template <class V>
+static int coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const V* dVal,
+                      int flags, int** dIA, int** dJA, V** dA, int* nnzOut) {
   if (!dIA || !dJA || !dA || !nnzOut) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *dIA = nullptr; *dJA = nullptr; *dA = nullptr; *nnzOut = 0;
   if (rows < 0 || cols < 0 || nnz < 0) return fail(SPGEMM_ERR_ARG, "negative size");
   if (nnz > 0 && (!dRow || !dCol || !dVal)) return fail(SPGEMM_ERR_ARG, "COO arrays null with nnz=%d", nnz);
   if ((flags & SPGEMM_COO_SELF_LOOPS) && rows != cols) return fail(SPGEMM_ERR_ARG, "self loops need a square matrix");
-  using namespace coo;
   hipStream_t s;
   CHK(enter(h, &s));
   const int dedupe = (flags & SPGEMM_COO_DEDUPE) ? 1 : 0;
@@ -112,7 +128,7 @@ extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, con
   unsigned long long *keyA = nullptr, *keyB = nullptr, *tile = nullptr;
   int* bhist = nullptr;                          // digit-major per-block histograms / offsets of the radix passes
   int *IA = nullptr, *JA = nullptr;
-  float* A = nullptr;
+  V* A = nullptr;
   const int colBits = std::max(1, bits_of(cols - 1));      // key = (row << colBits) | col
   const int keyBits = std::max(1, bits_of(rows - 1) + colBits);
   // scratch of the scans: tile sums of the longest array scanned below (entries, rows + 1, or 256 x radix blocks)
@@ -144,7 +160,7 @@ extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, con
   CSR_HIP(hipMemsetAsync(IA, 0, sizeof(int) * ((size_t)rows + 1), s));
   if (total == 0) {
     CSR_ALLOC(&JA, sizeof(int), true);
-    CSR_ALLOC(&A, sizeof(float), true);
+    CSR_ALLOC(&A, sizeof(V), true);
     CSR_HIP(hipStreamSynchronize(s));
     *dIA = IA; *dJA = JA; *dA = A; *nnzOut = 0;
     return sc.done(SPGEMM_OK);
@@ -155,7 +171,7 @@ extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, con
   CSR_ALLOC(&idxA, sizeof(int) * (size_t)total);
   CSR_ALLOC(&idxB, sizeof(int) * (size_t)total);
   CSR_ALLOC(&bhist, sizeof(int) * ((size_t)cdiv(total, RS_TILE) * RS_RADIX + 1));
-  hipLaunchKernelGGL(k_make_keys, grid256(std::max(nnz, loops ? rows : 0)), dim3(256), 0, s, nnz, rows, colBits, dRow, dCol,
+  hipLaunchKernelGGL(k_make_keys<V>, grid256(std::max(nnz, loops ? rows : 0)), dim3(256), 0, s, nnz, rows, colBits, dRow, dCol,
                      dVal, missPos, loops ? miss : (int*)nullptr, keyA, idxA);
   radix_sort_bits(s, total, 0, keyBits, keyA, keyB, idxA, idxB, bhist, tile);
   CSR_HIP(hipGetLastError());
@@ -169,16 +185,28 @@ extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, con
   const int outN = (int)nheads;
   // (4) emit columns / values / row counts, scan the counts, optional row normalisation
   CSR_ALLOC(&JA, sizeof(int) * (size_t)std::max(outN, 1), true);
-  CSR_ALLOC(&A, sizeof(float) * (size_t)std::max(outN, 1), true);
-  hipLaunchKernelGGL(k_emit, grid256(total), dim3(256), 0, s, total, colBits, keyA, idxA, head, pos, dedupe,
+  CSR_ALLOC(&A, sizeof(V) * (size_t)std::max(outN, 1), true);
+  hipLaunchKernelGGL(k_emit<V>, grid256(total), dim3(256), 0, s, total, colBits, keyA, idxA, head, pos, dVal, nnz, dedupe,
                      (flags & SPGEMM_COO_ABS) ? 1 : 0, JA, A);
   hipLaunchKernelGGL(k_row_starts, grid256((long long)rows + 1), dim3(256), 0, s, rows, total, colBits, keyA, pos, IA);
   if ((flags & SPGEMM_COO_ROW_NORMALISE) && rows > 0)
-    hipLaunchKernelGGL(k_row_normalise, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, rows, IA, A);
+    hipLaunchKernelGGL(k_row_normalise<V>, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, s, rows, IA, A);
   CSR_HIP(hipGetLastError());
   CSR_HIP(hipStreamSynchronize(s));
   *dIA = IA; *dJA = JA; *dA = A; *nnzOut = outN;
   return sc.done(SPGEMM_OK);
+}
+
+}  // namespace coo
+
+extern "C" int hip_coo_to_csr(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol,
+                              const float* dVal, int flags, int** dIA, int** dJA, float** dA, int* nnzOut) {
+  return coo::coo_to_csr<float>(h, rows, cols, nnz, dRow, dCol, dVal, flags, dIA, dJA, dA, nnzOut);
+}
+
+extern "C" int hip_coo_to_csr_f64(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol,
+                                  const double* dVal, int flags, int** dIA, int** dJA, double** dA, int* nnzOut) {
+  return coo::coo_to_csr<double>(h, rows, cols, nnz, dRow, dCol, dVal, flags, dIA, dJA, dA, nnzOut);
 }
 
 // ------------------------------------------------------------------------------------------------

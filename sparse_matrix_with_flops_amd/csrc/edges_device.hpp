@@ -1,6 +1,6 @@
 // Edge-list text -> COO triplets on the device: the parse in front of hip_coo_to_csr.
 //
-// Replaces, for float values and line-oriented files, the text half of COO::readSNAPFile (nlibs/COO.cc:48-158): the size
+// Replaces, for line-oriented files, the text half of COO::readSNAPFile (nlibs/COO.cc:48-158): the size
 // line is read on the host (hip_edge_text_header), the edge lines "from to [value]" are cut and converted here.
 //   k_edges_count    '\n' bytes per EDGE_TILE bytes of text (16-byte loads, compared byte-wise)
 //   (the library's scan over the tile counts)
@@ -9,6 +9,8 @@
 // A line the scanner calls slow (edge_scan.hpp: what it does not promise to convert like strtol / strtof) is appended to a
 // device list; the host parses exactly those lines with strtol / strtol / strtof and stores their triplets.  A line with
 // fewer than two fields stops the reading as in the reference: entries = min(declared, lines, first such line).
+// The parse and everything behind it is generic over the value type V: float (QValue float, strtof) or double (FDOUBLE,
+// strtod, the entries named _f64).  Counting and cutting the lines does not depend on V.
 // Uses csr_common_device.hpp (Scratch, the call prologue, the scan).
 #pragma once
 
@@ -26,6 +28,21 @@ constexpr int EDGE_TILE = 4096;            // bytes of text per block of the cou
 constexpr int EDGE_STAGE = 8192;           // LDS bytes k_edges_parse stages a block's 256 lines in (32 per line)
 constexpr unsigned NO_BAD_LINE = 0xffffffffu;
 static_assert(EDGE_TILE == EDGE_THREADS * 16, "one 16-byte load per lane");
+
+// what differs between the two value types: the scanner's bit pattern, 1.0 (a missing value), the host's conversion
+template <class V> struct EdgeValue;
+template <> struct EdgeValue<float> {
+  using Bits = uint32_t;
+  static constexpr Bits ONE = 0x3f800000u;
+  static __device__ __forceinline__ float of_bits(Bits b) { return __uint_as_float(b); }
+  static float host(const char* s, char** e) { return strtof(s, e); }
+};
+template <> struct EdgeValue<double> {
+  using Bits = uint64_t;
+  static constexpr Bits ONE = 0x3ff0000000000000ull;
+  static __device__ __forceinline__ double of_bits(Bits b) { return __longlong_as_double((long long)b); }
+  static double host(const char* s, char** e) { return strtod(s, e); }
+};
 
 // bit i set: byte off + i of the text is '\n'.  off is a multiple of 16 and the text base 16-byte aligned; the 16 bytes
 // that hold the end of the text are read one by one under the bound.
@@ -88,10 +105,11 @@ __global__ __launch_bounds__(EDGE_THREADS) void k_edges_starts(const unsigned ch
 // from the 16-byte boundary below its start when that fits EDGE_STAGE, else every lane reads its line from global
 // memory (a line of any length).  No byte outside [0, nbytes) is read: the 16 bytes holding the end of the text are
 // copied one by one.
+template <class V>
 __global__ __launch_bounds__(EDGE_THREADS) void k_edges_parse(const unsigned char* __restrict__ text, int nbytes,
                                                               const unsigned* __restrict__ starts, int cap, int flags,
                                                               int* __restrict__ dRow, int* __restrict__ dCol,
-                                                              float* __restrict__ dVal, unsigned* __restrict__ ctl,
+                                                              V* __restrict__ dVal, unsigned* __restrict__ ctl,
                                                               int* __restrict__ slowList) {
   __shared__ __attribute__((aligned(16))) unsigned char stage[EDGE_STAGE];
   const int tid = threadIdx.x;
@@ -120,9 +138,9 @@ __global__ __launch_bounds__(EDGE_THREADS) void k_edges_parse(const unsigned cha
   if (b < s0 || e < b || e > s1) { atomicOr(&ctl[2], 1u); return; }
   const int len = (int)(e - b);
   int from = 0, to = 0;
-  uint32_t vbits = 0x3f800000u;                                // a missing value is 1.0f
-  const int got = staged ? edgescan::edge_scan_line(stage + (b - a0), len, &from, &to, &vbits)
-                         : edgescan::edge_scan_line(text + b, len, &from, &to, &vbits);
+  typename EdgeValue<V>::Bits vbits = EdgeValue<V>::ONE;      // a missing value is 1.0
+  const int got = staged ? edgescan::edge_scan_line_as(stage + (b - a0), len, &from, &to, &vbits)
+                         : edgescan::edge_scan_line_as(text + b, len, &from, &to, &vbits);
   if (got == edgescan::EDGE_SLOW) {
     slowList[atomicAdd(&ctl[1], 1u)] = (int)k;
   } else if (got < 2) {
@@ -132,7 +150,7 @@ __global__ __launch_bounds__(EDGE_THREADS) void k_edges_parse(const unsigned cha
     const bool tr = (flags & SPGEMM_EDGES_TRANSPOSE) != 0;
     dRow[k] = tr ? to : from;
     dCol[k] = tr ? from : to;
-    dVal[k] = __uint_as_float(vbits);
+    dVal[k] = EdgeValue<V>::of_bits(vbits);
   }
 }
 
@@ -154,16 +172,19 @@ __global__ void k_edges_slow_pack(int n, const unsigned* __restrict__ spans, con
   for (unsigned j = 0; j < len; ++j) packed[o + j] = text[b + j];
 }
 
+template <class V>
 __global__ void k_edges_slow_store(int n, const int* __restrict__ at, const int* __restrict__ r, const int* __restrict__ c,
-                                   const float* __restrict__ v, int* __restrict__ dRow, int* __restrict__ dCol,
-                                   float* __restrict__ dVal) {
+                                   const V* __restrict__ v, int* __restrict__ dRow, int* __restrict__ dCol,
+                                   V* __restrict__ dVal) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   dRow[at[i]] = r[i]; dCol[at[i]] = c[i]; dVal[at[i]] = v[i];
 }
 
-// parse_edge of nlibs/COO.cc, the conversions sscanf("%d%d%f") performs: what a slow line is parsed with
-static int host_parse_edge(const char* s, int* from, int* to, float* val) {
+// parse_edge of nlibs/COO.cc, the conversions sscanf("%d%d%f") performs ("%d%d%lf" under FDOUBLE): what a slow line is
+// parsed with
+template <class V>
+static int host_parse_edge(const char* s, int* from, int* to, V* val) {
   char* e = nullptr;
   const long a = strtol(s, &e, 10);
   if (e == s) return 0;
@@ -172,7 +193,7 @@ static int host_parse_edge(const char* s, int* from, int* to, float* val) {
   if (e == s2) return 1;
   *from = (int)a; *to = (int)b;
   const char* s3 = e;
-  const float v = strtof(s3, &e);
+  const V v = EdgeValue<V>::host(s3, &e);
   if (e == s3) return 2;
   *val = v;
   return 3;
@@ -192,8 +213,9 @@ static int check_edge_args(const void* text, size_t nbytes, int flags) {
 // The device work behind both entries.  dText: the text on the device (16-byte aligned); hText: the same bytes on the
 // host, or null (then the slow lines, and only they, are copied back).  Fills st's lines / first_bad_line / entries /
 // slow_lines / ms_split / ms_parse / ms_slow.
+template <class V>
 static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hText, int nbytes, int declared, int flags,
-                       int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st) {
+                       int** dRow, int** dCol, V** dVal, int* entries, spgemm_edge_stats* st) {
   Scratch sc;
   auto t0 = std::chrono::steady_clock::now();
   long long lines = 0;
@@ -213,10 +235,10 @@ static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hT
   }
   const int cap = (int)std::min<long long>(std::max(declared, 0), lines);
   int *R = nullptr, *C = nullptr;
-  float* V = nullptr;
+  V* W = nullptr;
   CSR_ALLOC(&R, sizeof(int) * (size_t)std::max(cap, 1), true);
   CSR_ALLOC(&C, sizeof(int) * (size_t)std::max(cap, 1), true);
-  CSR_ALLOC(&V, sizeof(float) * (size_t)std::max(cap, 1), true);
+  CSR_ALLOC(&W, sizeof(V) * (size_t)std::max(cap, 1), true);
   long long firstBad = -1;
   int nslow = 0;
   float msSplit = 0.f, msParse = 0.f, msSlow = 0.f;
@@ -234,8 +256,8 @@ static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hT
     CSR_HIP(hipStreamSynchronize(s));
     msSplit = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(k_edges_parse, dim3(cdiv(cap, EDGE_THREADS)), dim3(EDGE_THREADS), 0, s, dText, nbytes, starts, cap, flags,
-                       R, C, V, ctl, slowList);
+    hipLaunchKernelGGL(k_edges_parse<V>, dim3(cdiv(cap, EDGE_THREADS)), dim3(EDGE_THREADS), 0, s, dText, nbytes, starts, cap,
+                       flags, R, C, W, ctl, slowList);
     CSR_HIP(hipGetLastError());
     unsigned hctl[3] = {NO_BAD_LINE, 0u, 0u};
     CSR_HIP(hipMemcpyAsync(hctl, ctl, sizeof(hctl), hipMemcpyDeviceToHost, s));
@@ -272,15 +294,15 @@ static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hT
       }
       // (3) exactly parse_edge on each; the good ones go back as {line, row, col, value}
       std::vector<int> at, hr, hc;
-      std::vector<float> hv;
+      std::vector<V> hv;
       std::string line;
       for (int i = 0; i < nslow; ++i) {
         const unsigned len = spans[2 * (size_t)i + 1];
         const char* p = hText ? hText + spans[2 * (size_t)i] : (const char*)packed.data() + offs[i];
         line.assign(p, len);
         int from = 0, to = 0;
-        float val = 1.0f;
-        const int got = host_parse_edge(line.c_str(), &from, &to, &val);
+        V val = 1;
+        const int got = host_parse_edge<V>(line.c_str(), &from, &to, &val);
         if (got < 2) { if (firstBad < 0 || list[i] < firstBad) firstBad = list[i]; continue; }
         if (flags & SPGEMM_EDGES_ONE_BASED) { from = (int)((unsigned)from - 1u); to = (int)((unsigned)to - 1u); }
         const bool tr = (flags & SPGEMM_EDGES_TRANSPOSE) != 0;
@@ -288,16 +310,16 @@ static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hT
       }
       if (const int n = (int)at.size()) {
         int *dAt = nullptr, *dR = nullptr, *dC = nullptr;
-        float* dV = nullptr;
+        V* dV = nullptr;
         CSR_ALLOC(&dAt, sizeof(int) * (size_t)n);
         CSR_ALLOC(&dR, sizeof(int) * (size_t)n);
         CSR_ALLOC(&dC, sizeof(int) * (size_t)n);
-        CSR_ALLOC(&dV, sizeof(float) * (size_t)n);
+        CSR_ALLOC(&dV, sizeof(V) * (size_t)n);
         CSR_HIP(hipMemcpyAsync(dAt, at.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
         CSR_HIP(hipMemcpyAsync(dR, hr.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
         CSR_HIP(hipMemcpyAsync(dC, hc.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, s));
-        CSR_HIP(hipMemcpyAsync(dV, hv.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_edges_slow_store, grid256(n), dim3(256), 0, s, n, dAt, dR, dC, dV, R, C, V);
+        CSR_HIP(hipMemcpyAsync(dV, hv.data(), sizeof(V) * (size_t)n, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_edges_slow_store<V>, grid256(n), dim3(256), 0, s, n, dAt, dR, dC, dV, R, C, W);
         CSR_HIP(hipGetLastError());
         CSR_HIP(hipStreamSynchronize(s));
       }
@@ -312,11 +334,12 @@ static int parse_lines(hipStream_t s, const unsigned char* dText, const char* hT
     st->lines = lines; st->first_bad_line = firstBad; st->entries = n; st->slow_lines = nslow;
     st->ms_split = msSplit; st->ms_parse = msParse; st->ms_slow = msSlow;
   }
-  *dRow = R; *dCol = C; *dVal = V; *entries = n;
+  *dRow = R; *dCol = C; *dVal = W; *entries = n;
   return sc.done(SPGEMM_OK);
 }
 
-static bool null_outputs(int** a, int** b, float** c, int* n, spgemm_edge_stats* st) {
+template <class V>
+static bool null_outputs(int** a, int** b, V** c, int* n, spgemm_edge_stats* st) {
   if (st) memset(st, 0, sizeof(*st));
   if (st) st->first_bad_line = -1;
   if (!a || !b || !c || !n) return true;
@@ -362,9 +385,12 @@ extern "C" int hip_edge_text_header(const char* text, size_t nbytes, int* rows, 
   return SPGEMM_OK;
 }
 
-extern "C" int hip_parse_edge_lines(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
-                                    int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st) {
-  using namespace edges;
+// ---- the three entries, for V = float and V = double ---------------------------------------------------------------------
+namespace edges {
+
+template <class V>
+static int parse_edge_lines_entry(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags, int** dRow,
+                                  int** dCol, V** dVal, int* entries, spgemm_edge_stats* st) {
   if (null_outputs(dRow, dCol, dVal, entries, st)) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   CHK(check_edge_args(dText, nbytes, flags));
   if ((uintptr_t)dText & 15u) return fail(SPGEMM_ERR_ARG, "the device text is not 16-byte aligned");
@@ -372,14 +398,14 @@ extern "C" int hip_parse_edge_lines(spgemm_handle* h, const char* dText, size_t 
   hipStream_t s;
   CHK(enter(h, &s));
   const auto t0 = std::chrono::steady_clock::now();
-  const int rc = parse_lines(s, (const unsigned char*)dText, nullptr, (int)nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+  const int rc = parse_lines<V>(s, (const unsigned char*)dText, nullptr, (int)nbytes, declared, flags, dRow, dCol, dVal, entries, st);
   if (st && rc == SPGEMM_OK) st->ms_total = ms_since(t0);
   return rc;
 }
 
-extern "C" int hip_parse_edge_text(spgemm_handle* h, const char* text, size_t nbytes, int declared, int flags,
-                                   int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st) {
-  using namespace edges;
+template <class V>
+static int parse_edge_text_entry(spgemm_handle* h, const char* text, size_t nbytes, int declared, int flags, int** dRow,
+                                 int** dCol, V** dVal, int* entries, spgemm_edge_stats* st) {
   if (null_outputs(dRow, dCol, dVal, entries, st)) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   CHK(check_edge_args(text, nbytes, flags));
   if (nbytes > (size_t)INT32_MAX) return fail(SPGEMM_ERR_OVERFLOW, "%zu bytes of text: offsets are 32-bit", nbytes);
@@ -392,15 +418,24 @@ extern "C" int hip_parse_edge_text(spgemm_handle* h, const char* text, size_t nb
   CopyJob job{(void*)text, (void*)dText, nbytes};
   if (int rc = copy_pageable(h->device, &job, 1, true)) return sc.done(rc);
   const float msUpload = ms_since(t0);
-  const int rc = parse_lines(s, dText, text, (int)nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+  const int rc = parse_lines<V>(s, dText, text, (int)nbytes, declared, flags, dRow, dCol, dVal, entries, st);
   if (st && rc == SPGEMM_OK) { st->ms_upload = msUpload; st->ms_total = ms_since(t0); }
   sc.done(SPGEMM_OK);                                   // the text copy goes back to the pool either way
   return rc;
 }
 
-extern "C" int hip_read_edge_file(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
-                                  int** dIA, int** dJA, float** dA, int* nnz, spgemm_edge_stats* st) {
-  using namespace edges;
+static int coo_to_csr_of(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const float* dVal,
+                         int flags, int** dIA, int** dJA, float** dA, int* nnzOut) {
+  return hip_coo_to_csr(h, rows, cols, nnz, dRow, dCol, dVal, flags, dIA, dJA, dA, nnzOut);
+}
+static int coo_to_csr_of(spgemm_handle* h, int rows, int cols, int nnz, const int* dRow, const int* dCol, const double* dVal,
+                         int flags, int** dIA, int** dJA, double** dA, int* nnzOut) {
+  return hip_coo_to_csr_f64(h, rows, cols, nnz, dRow, dCol, dVal, flags, dIA, dJA, dA, nnzOut);
+}
+
+template <class V>
+static int read_edge_file_entry(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
+                                int** dIA, int** dJA, V** dA, int* nnz, spgemm_edge_stats* st) {
   if (null_outputs(dIA, dJA, dA, nnz, st) || !rows || !cols) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *rows = *cols = 0;
   if (!path) return fail(SPGEMM_ERR_ARG, "path is null");
@@ -427,10 +462,39 @@ extern "C" int hip_read_edge_file(spgemm_handle* h, const char* path, int isTran
   if (symmetric) return fail(SPGEMM_ERR_INPUT, "%s is a symmetric MatrixMarket file, a token stream: use the host loader", path);
   const int flags = (oneBased ? SPGEMM_EDGES_ONE_BASED : 0) | (isTrans ? SPGEMM_EDGES_TRANSPOSE : 0);
   int *dR = nullptr, *dC = nullptr, n = 0;
-  float* dV = nullptr;
-  CHK(hip_parse_edge_text(h, text + off, len - off, declared, flags, &dR, &dC, &dV, &n, st));
-  const int rc = hip_coo_to_csr(h, r, c, n, dR, dC, dV, cooFlags, dIA, dJA, dA, nnz);
+  V* dV = nullptr;
+  CHK(parse_edge_text_entry<V>(h, text + off, len - off, declared, flags, &dR, &dC, &dV, &n, st));
+  const int rc = coo_to_csr_of(h, r, c, n, dR, dC, dV, cooFlags, dIA, dJA, dA, nnz);
   pool().release(dR); pool().release(dC); pool().release(dV);
   if (rc == SPGEMM_OK) { *rows = r; *cols = c; }
   return rc;
+}
+
+}  // namespace edges
+
+extern "C" int hip_parse_edge_lines(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
+                                    int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st) {
+  return edges::parse_edge_lines_entry<float>(h, dText, nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+}
+extern "C" int hip_parse_edge_lines_f64(spgemm_handle* h, const char* dText, size_t nbytes, int declared, int flags,
+                                        int** dRow, int** dCol, double** dVal, int* entries, spgemm_edge_stats* st) {
+  return edges::parse_edge_lines_entry<double>(h, dText, nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+}
+
+extern "C" int hip_parse_edge_text(spgemm_handle* h, const char* text, size_t nbytes, int declared, int flags,
+                                   int** dRow, int** dCol, float** dVal, int* entries, spgemm_edge_stats* st) {
+  return edges::parse_edge_text_entry<float>(h, text, nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+}
+extern "C" int hip_parse_edge_text_f64(spgemm_handle* h, const char* text, size_t nbytes, int declared, int flags,
+                                       int** dRow, int** dCol, double** dVal, int* entries, spgemm_edge_stats* st) {
+  return edges::parse_edge_text_entry<double>(h, text, nbytes, declared, flags, dRow, dCol, dVal, entries, st);
+}
+
+extern "C" int hip_read_edge_file(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
+                                  int** dIA, int** dJA, float** dA, int* nnz, spgemm_edge_stats* st) {
+  return edges::read_edge_file_entry<float>(h, path, isTrans, cooFlags, rows, cols, dIA, dJA, dA, nnz, st);
+}
+extern "C" int hip_read_edge_file_f64(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
+                                      int** dIA, int** dJA, double** dA, int* nnz, spgemm_edge_stats* st) {
+  return edges::read_edge_file_entry<double>(h, path, isTrans, cooFlags, rows, cols, dIA, dJA, dA, nnz, st);
 }

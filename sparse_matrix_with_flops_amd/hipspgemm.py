@@ -18,7 +18,7 @@ Mirrors (reference file:line):
   MCSR.from_csr(dM, r, c, blockRows, blockCols) / to_csr / nonzero_density
                               struct MCSR                      nlibs/MCSR.h:6-9, nlibs/MCSR.cc:58-92
   edge_text_header(data) / parse_edge_text(data, declared) / read_edge_file(path, isTrans, flags)
-                              COO::readSNAPFile (the text)     nlibs/COO.cc:48-158   (float values; parsed on the device)
+                              COO::readSNAPFile (the text)     nlibs/COO.cc:48-158   (parsed on the device; dtype= picks the value type)
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -68,6 +68,7 @@ EXPORTS = [
     "hip_csr_to_bcsr", "hip_csr_to_bcsr_f64", "hip_bcsr_to_csr", "hip_bcsr_to_csr_f64",
     "hip_csr_to_mcsr", "hip_csr_to_mcsr_f64", "hip_mcsr_to_csr", "hip_mcsr_to_csr_f64",
     "hip_edge_text_header", "hip_parse_edge_lines", "hip_parse_edge_text", "hip_read_edge_file",
+    "hip_coo_to_csr_f64", "hip_parse_edge_lines_f64", "hip_parse_edge_text_f64", "hip_read_edge_file_f64",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -166,6 +167,7 @@ def lib():
         L.spgemm_hip_kernel_name.argtypes = [C.c_int]
         L.hip_coo_to_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I]
+        L.hip_coo_to_csr_f64.argtypes = L.hip_coo_to_csr.argtypes
         L.hip_flopsStats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         L.spgemm_hip_memcpy_d2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.hip_rmcl_prune.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + \
@@ -226,6 +228,9 @@ def lib():
         L.hip_parse_edge_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int] + edge_out
         L.hip_parse_edge_text.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_int] + edge_out
         L.hip_read_edge_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _I, _I] + edge_out
+        L.hip_parse_edge_lines_f64.argtypes = L.hip_parse_edge_lines.argtypes
+        L.hip_parse_edge_text_f64.argtypes = L.hip_parse_edge_text.argtypes
+        L.hip_read_edge_file_f64.argtypes = L.hip_read_edge_file.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -819,27 +824,37 @@ def resultsComparison(hC, rC, hv, hqueue, rel=1e-6):
             for r in rep]
 
 
-def coo_to_csr_raw(handle, rows, cols, nnz, dRow, dCol, dVal, flags):
-    """hip_coo_to_csr on raw device pointers -> (dIA, dJA, dA, nnz) from the library pool (release with dev_free)."""
+def _coo_to_csr(dtype, handle, rows, cols, nnz, dRow, dCol, dVal, flags):
     out = _CsrOut()
-    _check(lib().hip_coo_to_csr(_hp(handle), int(rows), int(cols), int(nnz), *_ptrs(dRow, dCol, dVal), int(flags), *out.refs()),
-           "hip_coo_to_csr")
+    _call("hip_coo_to_csr", dtype, _hp(handle), int(rows), int(cols), int(nnz), *_ptrs(dRow, dCol, dVal), int(flags), *out.refs())
     return out.values()
 
 
-def coo_to_csr(rows, cols, ri, ci, v, flags, handle=None):
+def coo_to_csr_raw(handle, rows, cols, nnz, dRow, dCol, dVal, flags):
+    """hip_coo_to_csr on raw device pointers -> (dIA, dJA, dA, nnz) from the library pool (release with dev_free)."""
+    return _coo_to_csr(np.float32, handle, rows, cols, nnz, dRow, dCol, dVal, flags)
+
+
+def coo_to_csr_raw_f64(handle, rows, cols, nnz, dRow, dCol, dVal, flags):
+    """coo_to_csr_raw with float64 values in and out (hip_coo_to_csr_f64)."""
+    return _coo_to_csr(np.float64, handle, rows, cols, nnz, dRow, dCol, dVal, flags)
+
+
+def coo_to_csr(rows, cols, ri, ci, v, flags, handle=None, dtype=np.float32):
     """Host COO arrays in, device CSR out (COO::toCSR and friends, on the device): returns a device `CSR`.
-    flags: COO_DEDUPE | COO_SELF_LOOPS | COO_ROW_NORMALISE | COO_ABS (rmclInit = SELF_LOOPS | ROW_NORMALISE)."""
+    flags: COO_DEDUPE | COO_SELF_LOOPS | COO_ROW_NORMALISE | COO_ABS (rmclInit = SELF_LOOPS | ROW_NORMALISE).
+    dtype: np.float32, or np.float64 for a double device CSR (hip_coo_to_csr_f64)."""
+    dtype = _value_dtype(dtype)
     ri = np.ascontiguousarray(ri, dtype=np.int32)
     ci = np.ascontiguousarray(ci, dtype=np.int32)
-    v = np.ascontiguousarray(v, dtype=np.float32)
+    v = np.ascontiguousarray(v, dtype=dtype)
     dr, dc, dv = h2d(ri), h2d(ci), h2d(v)
     try:
-        ia, ja, av, n = coo_to_csr_raw(handle, rows, cols, len(ri), dr, dc, dv, flags)
+        ia, ja, av, n = _coo_to_csr(dtype, handle, rows, cols, len(ri), dr, dc, dv, flags)
     finally:
         for p in (dr, dc, dv):
             dev_free(p)
-    return CSR(av, ja, ia, rows, cols, n, True)
+    return CSR(av, ja, ia, rows, cols, n, True, dtype=dtype)
 
 
 def _csr_permute(dtype, handle, m, n, nnz, IA, JA, VA, rowSrc=None, colMap=None):
@@ -1557,27 +1572,37 @@ def edge_text_header(data):
             "symmetric": bool(sym.value), "data_offset": int(off.value)}
 
 
-def parse_edge_lines_raw(handle, dText, nbytes, declared, flags=0):
-    """hip_parse_edge_lines on a raw device pointer (16-byte aligned text) -> (dRow, dCol, dVal, entries, stats dict);
-    the three arrays come from the library pool (release with dev_free)."""
+def _parse_edge_lines(dtype, handle, dText, nbytes, declared, flags):
     flags = _edge_flags(flags)
     out, st = _CsrOut(), EdgeStats()
-    _check(lib().hip_parse_edge_lines(_hp(handle), C.c_void_p(dText), int(nbytes), int(declared), flags, *out.refs(),
-                                      C.byref(st)), "hip_parse_edge_lines")
+    _call("hip_parse_edge_lines", dtype, _hp(handle), C.c_void_p(dText), int(nbytes), int(declared), flags, *out.refs(),
+          C.byref(st))
     return out.values() + (st.as_dict(),)
 
 
-class EdgeTriplets:
-    """device COO triplets in line order, as hip_parse_edge_text leaves them: row, col (int32) and val (float32) device
-    pointers, their count `entries` and the call's `stats`"""
+def parse_edge_lines_raw(handle, dText, nbytes, declared, flags=0):
+    """hip_parse_edge_lines on a raw device pointer (16-byte aligned text) -> (dRow, dCol, dVal, entries, stats dict);
+    the three arrays come from the library pool (release with dev_free)."""
+    return _parse_edge_lines(np.float32, handle, dText, nbytes, declared, flags)
 
-    def __init__(self, row, col, val, entries, stats):
+
+def parse_edge_lines_raw_f64(handle, dText, nbytes, declared, flags=0):
+    """parse_edge_lines_raw with float64 values (hip_parse_edge_lines_f64)."""
+    return _parse_edge_lines(np.float64, handle, dText, nbytes, declared, flags)
+
+
+class EdgeTriplets:
+    """device COO triplets in line order, as hip_parse_edge_text leaves them: row, col (int32) and val (`dtype`: float32
+    or float64) device pointers, their count `entries` and the call's `stats`"""
+
+    def __init__(self, row, col, val, entries, stats, dtype=np.float32):
         self.row, self.col, self.val, self.entries, self.stats = row, col, val, int(entries), stats
+        self.dtype = _value_dtype(dtype)
 
     def download(self):
         """-> (row, col, val) numpy arrays of `entries` elements"""
         return (d2h(self.row, self.entries, np.int32), d2h(self.col, self.entries, np.int32),
-                d2h(self.val, self.entries, np.float32))
+                d2h(self.val, self.entries, self.dtype))
 
     def dispose(self):
         for p in (self.row, self.col, self.val):
@@ -1585,30 +1610,33 @@ class EdgeTriplets:
         self.row = self.col = self.val = None
 
 
-def parse_edge_text(data, declared, one_based=False, transpose=False, handle=None):
+def parse_edge_text(data, declared, one_based=False, transpose=False, handle=None, dtype=np.float32):
     """hip_parse_edge_text: host bytes holding edge lines -> EdgeTriplets on the device.  At most `declared` lines are
-    read; one_based subtracts 1 from both indices (MatrixMarket), transpose swaps them (isTrans)."""
+    read; one_based subtracts 1 from both indices (MatrixMarket), transpose swaps them (isTrans).  dtype: np.float32, or
+    np.float64 for double values (hip_parse_edge_text_f64)."""
     data = _edge_bytes(data, "parse_edge_text")
+    dtype = _value_dtype(dtype)
     flags = (EDGES_ONE_BASED if one_based else 0) | (EDGES_TRANSPOSE if transpose else 0)
     out, st = _CsrOut(), EdgeStats()
-    _check(lib().hip_parse_edge_text(_hp(handle), data, len(data), int(declared), flags, *out.refs(), C.byref(st)),
-           "hip_parse_edge_text")
+    _call("hip_parse_edge_text", dtype, _hp(handle), data, len(data), int(declared), flags, *out.refs(), C.byref(st))
     r, c, v, n = out.values()
-    return EdgeTriplets(r, c, v, n, st.as_dict())
+    return EdgeTriplets(r, c, v, n, st.as_dict(), dtype)
 
 
-def read_edge_file(path, isTrans=True, flags=COO_DEDUPE, handle=None):
+def read_edge_file(path, isTrans=True, flags=COO_DEDUPE, handle=None, dtype=np.float32):
     """hip_read_edge_file: COO::readSNAPFile(path, isTrans) + hip_coo_to_csr(flags) without the triplets ever on the host
-    -> device `CSR` (its .edge_stats: the parse's stats).  A symmetric MatrixMarket file raises (use the host loader)."""
+    -> device `CSR` (its .edge_stats: the parse's stats).  A symmetric MatrixMarket file raises (use the host loader).
+    dtype: np.float32, or np.float64 for a double device CSR (hip_read_edge_file_f64)."""
+    dtype = _value_dtype(dtype)
     if not isinstance(path, (str, bytes, os.PathLike)):
         raise SpgemmError(f"read_edge_file: path must be a str, bytes or os.PathLike, not {type(path).__name__}")
     flags = int(flags)
     if flags & ~(COO_DEDUPE | COO_SELF_LOOPS | COO_ROW_NORMALISE | COO_ABS):
         raise SpgemmError(f"unknown COO flags 0x{flags:x}")
     out, st, rows, cols = _CsrOut(), EdgeStats(), C.c_int(), C.c_int()
-    _check(lib().hip_read_edge_file(_hp(handle), os.fsencode(path), int(bool(isTrans)), flags, C.byref(rows), C.byref(cols),
-                                    *out.refs(), C.byref(st)), "hip_read_edge_file")
+    _call("hip_read_edge_file", dtype, _hp(handle), os.fsencode(path), int(bool(isTrans)), flags, C.byref(rows), C.byref(cols),
+          *out.refs(), C.byref(st))
     ia, ja, av, nnz = out.values()
-    M = CSR(av, ja, ia, rows.value, cols.value, nnz, True)
+    M = CSR(av, ja, ia, rows.value, cols.value, nnz, True, dtype=dtype)
     M.edge_stats = st.as_dict()
     return M
