@@ -686,6 +686,62 @@ int hip_mcsr_to_csr_f64(spgemm_handle* h, int m, int n, int r, int c, int blockR
                         int nnzR, const int* dIR, const int* dJR, const double* dR, double drop_tol,
                         int** dIC, int** dJC, double** dC, int* nnzC);
 
+/* ---- dense matrix: a CSR written out as a dense array, a dense array as a CSR, and the dense product ----------------------
+ * All matrix pointers are device pointers, the counts are host memory; h == NULL = the default handle; a call returns
+ * after the device work has completed; CSR outputs come from the library pool (release with spgemm_hip_free).  Argument
+ * checks (a null output, a negative size, a count > 0 with null arrays, ld below the columns, a rule outside {0, 1}, a
+ * negative or NaN tol, C overlapping A or B -> SPGEMM_ERR_ARG) run before any device is touched.  Every value that
+ * becomes an address (rowPtr, the columns) is validated by a read-only pass whose flag the host reads before it is used:
+ * bad input -> SPGEMM_ERR_INPUT with a message.  On any error the outputs are NULL or untouched, nothing stays allocated,
+ * the handle stays usable.
+ *
+ * A dense matrix is row-major with a leading dimension in elements: cell (i, j) is at i * ld + j, ld >= columns; the
+ * cells [i][columns..ld) are padding that no call reads or writes.  Every dense offset is computed in 64 bits, so
+ * rows * ld may exceed 2^31. */
+#define SPGEMM_DENSE_KEEP_REFERENCE 0   /* keep unless (double)v < tol; tol = 1e-8 is CSR::initWithDenseMatrix */
+#define SPGEMM_DENSE_KEEP_ABS       1   /* keep when fabs((double)v) > tol: the rule of hip_bcsr_to_csr */
+
+/* DenseMatrix::DenseMatrix(const CSR&) (nlibs/DenseMatrix.h:6-21): zero-fill, then values[i * cols + col] = val in storage
+ * order.  dD is the CALLER's m x ld buffer -- the one place where the library writes into memory it did not allocate, so
+ * that a tensor another framework owns (its data_ptr()) is filled in place, without a copy out of the pool.  Every cell
+ * [i][0..n) receives a value: +0.0 where no entry lands.  Values are moved, not computed: NaN payloads, -0.0 and denormals
+ * keep their bits.  A's rows need not be sorted; of a repeated (row, col) the last in storage order stays, as the
+ * reference's sequential loop leaves it (deterministic: no two stores aim at one cell).  rowPtr and the columns are
+ * validated before anything is written: a bad rowPtr or a column outside [0, n) -> SPGEMM_ERR_INPUT, dD untouched.
+ * m == 0, n == 0 and nnz == 0 are valid. */
+int hip_csr_to_dense(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                     float* dD, long long ld);
+int hip_csr_to_dense_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                         double* dD, long long ld);
+
+/* CSR::initWithDenseMatrix (nlibs/CSR.h:54-82; its known-answer vectors: tests/CSR_test.cc:65-87): row i of the result
+ * holds the kept cells of dense row i in ascending column order; kept values keep their bits.
+ *   SPGEMM_DENSE_KEEP_REFERENCE  a cell is dropped when (double)v < tol.  With tol = 1e-8 this is the reference, exactly:
+ *                                negative values are dropped; NaN is kept (NaN < tol is false); float(1e-8) is dropped
+ *                                (promoted to double it is 9.99999993922529e-09, below 1e-8), the next float up is kept.
+ *   SPGEMM_DENSE_KEEP_ABS        a cell is kept when fabs((double)v) > tol: NaN is dropped, negatives are kept; tol = 0
+ *                                keeps every nonzero non-NaN cell.
+ * More than INT32_MAX kept cells -> SPGEMM_ERR_OVERFLOW, decided from the 64-bit total of the count pass before any
+ * output is allocated.  For a CSR with column-sorted rows, no repeated column and no dropped value,
+ * hip_dense_to_csr(hip_csr_to_dense(A)) is A bit for bit.  m == 0 or n == 0: rowPtr all zero, *nnzC = 0. */
+int hip_dense_to_csr(spgemm_handle* h, int m, int n, const float* dD, long long ld, int rule, double tol,
+                     int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_dense_to_csr_f64(spgemm_handle* h, int m, int n, const double* dD, long long ld, int rule, double tol,
+                         int** dIC, int** dJC, double** dC, int* nnzC);
+
+/* C[m x n] = A[m x k] * B[k x n]: the cblas_dgemm(RowMajor, NoTrans, NoTrans, alpha 1, beta 0) of
+ * correctTests/dense-somp.cc, on the matrix cores.  C is fully overwritten in [i][0..n); its padding is untouched.
+ * C overlapping A or B (by address range) -> SPGEMM_ERR_ARG.  k == 0 gives all +0.0.  Zeros are multiplied like any
+ * other value: unlike the SpGEMM, which never forms a product with an absent entry, 0 * inf gives NaN here.
+ * Every C[i][j] is one accumulator over ascending k, starting from +0.0.
+ *   float   c = fmaf(A[i][k], B[k][j], c) for k = 0 .. K-1, then fmaf(+0.0, +0.0, c) up to the next multiple of 32:
+ *           bit for bit this host loop (the trailing steps change nothing but a -0.0 sum, which becomes +0.0).
+ *   double  no order of rounding is promised; |C[i][j] - exact| <= k * 2^-53 * sum_k |A[i][k]| * |B[k][j]|. */
+int hip_dense_gemm(spgemm_handle* h, int m, int n, int k, const float* dA, long long lda, const float* dB, long long ldb,
+                   float* dC, long long ldc);
+int hip_dense_gemm_f64(spgemm_handle* h, int m, int n, int k, const double* dA, long long lda, const double* dB,
+                       long long ldb, double* dC, long long ldc);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

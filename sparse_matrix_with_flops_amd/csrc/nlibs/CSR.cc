@@ -21,6 +21,32 @@ static void hip_or_die(int rc, const char* what) {
   if (rc != SPGEMM_OK) { printf("%s: %s\n", what, spgemm_hip_last_error()); exit(EXIT_FAILURE); }
 }
 
+void CSR::initWithDenseMatrix(const QValue* dvalues, const int rows, const int cols) {
+  this->rows = rows; this->cols = cols;
+  const size_t cells = (size_t)rows * cols;
+  std::vector<size_t> kept;
+  rowPtr = (int*)malloc(((size_t)rows + 1) * sizeof(int));
+  rowPtr[0] = 0;
+  for (size_t at = 0; at < cells; ++at) {
+    if (!(dvalues[at] < 1e-8)) kept.push_back(at);
+    if ((at + 1) % cols == 0) rowPtr[(at + 1) / cols] = (int)kept.size();
+  }
+  if (cols == 0) for (int i = 1; i <= rows; ++i) rowPtr[i] = 0;
+  nnz = (int)kept.size();
+  colInd = (int*)malloc(std::max<size_t>(kept.size(), 1) * sizeof(int));
+  values = (QValue*)malloc(std::max<size_t>(kept.size(), 1) * sizeof(QValue));
+  for (size_t t = 0; t < kept.size(); ++t) { colInd[t] = (int)(kept[t] % cols); values[t] = dvalues[kept[t]]; }
+}
+
+CSR CSR::gpuInitWithDenseMatrix(const QValue* dvalues, const int rows, const int cols, int rule, double tol) {
+  CSR dC;
+  hip_or_die(hip_dense_to_csr(0, rows, cols, dvalues, cols, rule, tol, &dC.rowPtr, &dC.colInd, &dC.values, &dC.nnz),
+             "gpuInitWithDenseMatrix");
+  dC.rows = rows;
+  dC.cols = cols;
+  return dC;
+}
+
 CSR CSR::deepCopy() const {
   int* rp = (int*)must_malloc(sizeof(int) * ((size_t)rows + 1), "rowPtr");
   int* ci = (int*)must_malloc(sizeof(int) * (size_t)nnz, "colInd");

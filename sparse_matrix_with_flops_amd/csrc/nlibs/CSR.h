@@ -18,6 +18,12 @@ struct CSR {
   CSR(QValue* v, int* ci, int* rp, int r, int c, int nz) { init(v, ci, rp, r, c, nz); }
   void init(QValue* v, int* ci, int* rp, int r, int c, int nz) { values = v; colInd = ci; rowPtr = rp; rows = r; cols = c; nnz = nz; }
 
+  // nlibs/CSR.h:54-82: the cells of a rows x cols row-major array that are not below 1e-8, row by row (negative values
+  // and zeros are dropped, NaN stays: NaN < 1e-8 is false); arrays malloc()ed
+  void initWithDenseMatrix(const QValue* dvalues, const int rows, const int cols);
+  // the same walk on a DEVICE array (hip_dense_to_csr) -> device CSR; rule / tol as in include/spgemm_hip.h, the defaults
+  // are the reference's.  Exits on error.
+  static CSR gpuInitWithDenseMatrix(const QValue* dvalues, const int rows, const int cols, int rule = 0, double tol = 1e-8);
   CSR deepCopy() const;                 // nlibs/CSR.cc:97-106
   void makeOrdered();                   // nlibs/CSR.cc:73-86: sort every row by (col, value)
   void toAbs();                         // nlibs/CSR.h:152-158

@@ -2366,7 +2366,12 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // ------------------------------------------------------------------------------------------------
 #include "edges_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the seven headers above
+// ------------------------------------------------------------------------------------------------
+// dense matrix: CSR -> dense, dense -> CSR, the dense product
+// ------------------------------------------------------------------------------------------------
+#include "dense_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the eight headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

@@ -69,9 +69,12 @@ EXPORTS = [
     "hip_csr_to_mcsr", "hip_csr_to_mcsr_f64", "hip_mcsr_to_csr", "hip_mcsr_to_csr_f64",
     "hip_edge_text_header", "hip_parse_edge_lines", "hip_parse_edge_text", "hip_read_edge_file",
     "hip_coo_to_csr_f64", "hip_parse_edge_lines_f64", "hip_parse_edge_text_f64", "hip_read_edge_file_f64",
+    "hip_csr_to_dense", "hip_csr_to_dense_f64", "hip_dense_to_csr", "hip_dense_to_csr_f64",
+    "hip_dense_gemm", "hip_dense_gemm_f64",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
+DENSE_KEEP_REFERENCE, DENSE_KEEP_ABS = 0, 1
 VALUE_DTYPES = (np.float32, np.float64)
 XCHG_AUTO, XCHG_RCCL, XCHG_PEER, XCHG_HOST = 0, 1, 2, 3
 XCHG_NAMES = {0: "auto", 1: "rccl", 2: "peer", 3: "host"}
@@ -231,6 +234,14 @@ def lib():
         L.hip_parse_edge_lines_f64.argtypes = L.hip_parse_edge_lines.argtypes
         L.hip_parse_edge_text_f64.argtypes = L.hip_parse_edge_text.argtypes
         L.hip_read_edge_file_f64.argtypes = L.hip_read_edge_file.argtypes
+        L.hip_csr_to_dense.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_longlong]
+        L.hip_csr_to_dense_f64.argtypes = L.hip_csr_to_dense.argtypes
+        L.hip_dense_to_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_double] + \
+            [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_dense_to_csr_f64.argtypes = L.hip_dense_to_csr.argtypes
+        L.hip_dense_gemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_longlong] * 3
+        L.hip_dense_gemm_f64.argtypes = L.hip_dense_gemm.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1538,6 +1549,108 @@ class MCSR:
         if self.remainder is not None:
             self.remainder.deviceDispose()
             self.remainder = None
+
+
+# ---------------------------------------------------------------------------------------------
+# dense matrix (include/spgemm_hip.h "dense matrix"): CSR -> dense, dense -> CSR, the dense product
+# ---------------------------------------------------------------------------------------------
+def csr_to_dense_raw(handle, m, n, nnz, IA, JA, VA, D, ld, dtype=np.float32):
+    """hip_csr_to_dense (float32) / _f64 on raw device pointers: fills the caller's m x ld row-major buffer D in [i][0..n)
+    (+0.0 where no entry lands, the last of a repeated (row, col) stays); the padding [i][n..ld) is not written."""
+    _call("hip_csr_to_dense", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA, D), int(ld))
+
+
+def dense_to_csr_raw(handle, m, n, D, ld, rule=DENSE_KEEP_REFERENCE, tol=1e-8, dtype=np.float32):
+    """hip_dense_to_csr / _f64 -> (dIC, dJC, dC, nnz) from the library pool: row i = the kept cells of dense row i in
+    ascending column order.  DENSE_KEEP_REFERENCE drops a cell when value < tol (CSR::initWithDenseMatrix at 1e-8: NaN is
+    kept, negatives go), DENSE_KEEP_ABS keeps it when fabs(value) > tol; both compare in double."""
+    out = _CsrOut()
+    _call("hip_dense_to_csr", dtype, _hp(handle), int(m), int(n), C.c_void_p(D), int(ld), int(rule), float(tol), *out.refs())
+    return out.values()
+
+
+def dense_gemm_raw(handle, m, n, k, A, lda, B, ldb, Cd, ldc, dtype=np.float32):
+    """hip_dense_gemm / _f64: C[m x n] = A[m x k] * B[k x n] on row-major device arrays (alpha 1, beta 0, no transposes)."""
+    _call("hip_dense_gemm", dtype, _hp(handle), int(m), int(n), int(k), C.c_void_p(A), int(lda), C.c_void_p(B), int(ldb),
+          C.c_void_p(Cd), int(ldc))
+
+
+class DenseMatrix:
+    """Mirror of the reference's `struct DenseMatrix` (nlibs/DenseMatrix.h) on a device array: rows x cols values,
+    row-major with leading dimension ld (= cols for everything made here).  Fields values (device pointer), rows, cols,
+    ld, dtype."""
+
+    def __init__(self, dM=None, handle=None):
+        """DenseMatrix(const CSR&) on a device CSR: zero-fill, then every entry in storage order (the last of a repeated
+        column stays)"""
+        self.values, self.rows, self.cols, self.ld, self.dtype = None, 0, 0, 0, np.dtype(np.float32)
+        if dM is None:
+            return
+        assert dM.on_device
+        self._alloc(dM.rows, dM.cols, dM.dtype)
+        try:
+            csr_to_dense_raw(handle, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, dM.values, self.values, self.ld, self.dtype)
+        except SpgemmError:
+            self.dispose()
+            raise
+
+    def _alloc(self, rows, cols, dtype):
+        rows, cols = int(rows), int(cols)
+        if rows < 0 or cols < 0:
+            raise SpgemmError(f"negative shape {rows}x{cols}")
+        self.dtype = np.dtype(_value_dtype(dtype))
+        self.rows, self.cols, self.ld = rows, cols, cols
+        self.values = dev_alloc(rows * cols * self.dtype.itemsize)
+
+    @staticmethod
+    def zeros(rows, cols, dtype=np.float32):
+        return DenseMatrix.from_host(np.zeros((int(rows), int(cols)), _value_dtype(dtype)))
+
+    @staticmethod
+    def from_host(array):
+        """a 2-D float32 / float64 numpy array, uploaded row-major"""
+        array = np.asarray(array)
+        if array.ndim != 2:
+            raise SpgemmError(f"a dense matrix is 2-D, got {array.ndim} dimensions")
+        d = DenseMatrix()
+        d._alloc(array.shape[0], array.shape[1], array.dtype)
+        flat = np.ascontiguousarray(array)
+        if flat.nbytes:
+            _check(lib().spgemm_hip_memcpy_h2d(C.c_void_p(d.values), flat.ctypes.data_as(C.c_void_p), flat.nbytes), "h2d")
+        return d
+
+    def to_csr(self, rule=DENSE_KEEP_REFERENCE, tol=1e-8, handle=None):
+        """CSR::initWithDenseMatrix on the device -> device CSR; the defaults are the reference's rule"""
+        ic, jc, cv, nnz = dense_to_csr_raw(handle, self.rows, self.cols, self.values, self.ld, rule, tol, self.dtype)
+        return CSR(cv, jc, ic, self.rows, self.cols, nnz, True, dtype=self.dtype)
+
+    def matmul(self, other, handle=None):
+        """self * other -> a new DenseMatrix.  Another value type or an inner dimension that does not match raises before
+        any device work."""
+        if not isinstance(other, DenseMatrix):
+            raise SpgemmError("matmul takes a DenseMatrix")
+        if other.dtype != self.dtype:
+            raise SpgemmError(f"mixed value types: {self.dtype} times {other.dtype}")
+        if self.cols != other.rows:
+            raise SpgemmError(f"shape mismatch: {self.rows}x{self.cols} times {other.rows}x{other.cols}")
+        out = DenseMatrix()
+        out._alloc(self.rows, other.cols, self.dtype)
+        try:
+            dense_gemm_raw(handle, self.rows, other.cols, self.cols, self.values, self.ld, other.values, other.ld,
+                           out.values, out.ld, self.dtype)
+        except SpgemmError:
+            out.dispose()
+            raise
+        return out
+
+    def download(self):
+        """-> rows x cols numpy array (the padding of a wider ld is left behind)"""
+        flat = d2h(self.values, self.rows * self.ld, self.dtype)
+        return flat.reshape(self.rows, self.ld)[:, :self.cols].copy() if self.rows else flat.reshape(0, self.cols)
+
+    def dispose(self):
+        dev_free(self.values)
+        self.values = None
 
 
 # ---------------------------------------------------------------------------------------------
