@@ -409,6 +409,60 @@ int hip_read_edge_file  (spgemm_handle* h, const char* path, int isTrans, int co
 int hip_read_edge_file_f64(spgemm_handle* h, const char* path, int isTrans, int cooFlags, int* rows, int* cols,
                            int** dIA, int** dJA, double** dA, int* nnz, spgemm_edge_stats* st);
 
+/* ---- the way out: a device CSR as edge-list text, written on the device -------------------------------------------------
+ * The inverse of the parse above and the replacement of the download plus CSR::output's single-threaded
+ * printf("%d\t%d\t%.6lf\n") loop (nlibs/CSR.cc): one line "row SEP col SEP value\n" per entry, in CSR order, sized,
+ * placed and written by kernels (csrc/edges_write_device.hpp) through a formatter shared with the host
+ * (csrc/edge_print.hpp), byte for byte what snprintf writes.
+ *   SPGEMM_EDGE_FMT_FIXED6     "%d\t%d\t%.6lf\n", the line of CSR::output.  On the device: +-0 and every finite |x| < 1e15.
+ *   SPGEMM_EDGE_FMT_ROUNDTRIP  "%d %d %.9g\n" (float) / "%d %d %.17g\n" (double): reading the text back gives the same bits.
+ *                              On the device: +-0 and every finite 1e-15 <= |x| < 1e17.
+ * Every other value (inf, nan, outside the class) is "slow": the host formats exactly those entries with snprintf and the
+ * device puts their bytes in place.  flags: SPGEMM_EDGES_ONE_BASED prints both indices plus 1, SPGEMM_EDGES_TRANSPOSE prints
+ * "col row value" -- the flags hip_parse_edge_* undoes them with.  The _f64 entries take double values.
+ * h == NULL = the default handle; a call returns after its work has completed; st may be NULL.  Argument checks (a null
+ * output, a null CSR array with m > 0, an unknown fmt, flags or header, row0 > row1 or outside [0, m] -> SPGEMM_ERR_ARG)
+ * run before any device is touched; a rowPtr that is not monotone from 0 -> SPGEMM_ERR_INPUT.  On any error the outputs
+ * are NULL / 0, the stats zero, nothing stays allocated, the handle stays usable. */
+#define SPGEMM_EDGE_FMT_FIXED6    0
+#define SPGEMM_EDGE_FMT_ROUNDTRIP 1
+typedef struct spgemm_edge_write_stats {
+  long long entries, bytes;      /* lines written; bytes of text (hip_write_edge_file: the header included) */
+  long long slow_entries;        /* formatted on the host */
+  int slabs;                     /* pieces the text was produced in (1 outside hip_write_edge_file) */
+  float ms_length, ms_scan, ms_write;   /* device time of the length pass, the scan (with its read-back), the write pass */
+  float ms_slow, ms_download, ms_file, ms_total;   /* wall clock: the slow entries; text to the host; fwrite + fclose (runs
+                                    beside the next slab's formatting); all of it */
+} spgemm_edge_write_stats;
+
+/* pure host, no device, the counterpart of hip_edge_text_header.  header 0: nothing (*nbytes = 0); 1: the size line
+ * "rows cols entries\n" readSNAPFile reads; 2: "%%MatrixMarket matrix coordinate real general\n" and the size line (the
+ * lines behind it are then one-based).  buf too small (or NULL with header != 0), an unknown header, a negative size ->
+ * SPGEMM_ERR_ARG.  64 + 36 bytes always suffice. */
+int hip_edge_text_write_header(char* buf, size_t cap, int header, int rows, int cols, long long entries, size_t* nbytes);
+/* rows [row0, row1) of the m x n device CSR as text in DEVICE memory: *dText is a library pool block of *nbytes bytes
+ * (never NULL on success; release with spgemm_hip_free).  More than INT32_MAX bytes -> SPGEMM_ERR_OVERFLOW. */
+int hip_format_csr_edges    (spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, const float* dA, int row0, int row1,
+                             int fmt, int flags, char** dText, size_t* nbytes, spgemm_edge_write_stats* st);
+int hip_format_csr_edges_f64(spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, const double* dA, int row0, int row1,
+                             int fmt, int flags, char** dText, size_t* nbytes, spgemm_edge_write_stats* st);
+/* the same into a caller's HOST buffer of cap bytes, brought down through the pinned lanes hip_CSR_SpMM uses.  buf == NULL:
+ * only *nbytes, the size to allocate, is computed.  cap below the text's size -> SPGEMM_ERR_ARG. */
+int hip_csr_to_edge_text    (spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, const float* dA, int row0, int row1,
+                             int fmt, int flags, char* buf, size_t cap, size_t* nbytes, spgemm_edge_write_stats* st);
+int hip_csr_to_edge_text_f64(spgemm_handle* h, int m, int n, const int* dIA, const int* dJA, const double* dA, int row0, int row1,
+                             int fmt, int flags, char* buf, size_t cap, size_t* nbytes, spgemm_edge_write_stats* st);
+/* the whole matrix into the file `path` (created or truncated): the header (0 / 1 / 2 as above, with "m n nnz" whatever
+ * the flags; 2 sets ONE_BASED), then the body in slabs of at most SPGEMM_EDGE_SLAB bytes of text (environment, read per
+ * call; default 64 MiB; a slab is a whole number of lines and may end anywhere inside a row).  A slab is formatted on the
+ * device, brought down through the pinned lanes and handed to a second thread that fwrites it while the next slab is
+ * formatted: device memory is bounded by the slab, and a text above INT32_MAX bytes is more slabs, not an error.
+ * A path that cannot be opened for writing, or a failed write -> SPGEMM_ERR_ARG. */
+int hip_write_edge_file     (spgemm_handle* h, const char* path, int m, int n, const int* dIA, const int* dJA, const float* dA,
+                             int fmt, int flags, int header, spgemm_edge_write_stats* st);
+int hip_write_edge_file_f64 (spgemm_handle* h, const char* path, int m, int n, const int* dIA, const int* dJA, const double* dA,
+                             int fmt, int flags, int header, spgemm_edge_write_stats* st);
+
 /* ---- workload statistics ----------------------------------------------------
  * std::vector<int> flopsStats(IA, JA, IB, JB, m) (nlibs/tools/stats.cc:29-55, pushToStats :3-12): 13 buckets of the
  * per-row product count of A*B; bucket i counts rows with 2^(i-1) < flops <= 2^i, bucket 0 rows with flops <= 1,

@@ -388,6 +388,11 @@ void gpuOutputCSRWrapper(const CSR dA, const char* msg) {
   h.dispose();
 }
 
+void gpuWriteCSRWrapper(const CSR dA, const char* path, int fmt, int header) {
+  hip_or_die(hip_write_edge_file(NULL, path, dA.rows, dA.cols, dA.rowPtr, dA.colInd, dA.values, fmt, 0, header, NULL),
+             "gpuWriteCSRWrapper");
+}
+
 std::vector<int> CSR::nnzStats() const {
   std::vector<int> stats(SPGEMM_NNZ_STATS_LEN, 0);
   for (int r = 0; r < rows; ++r) {

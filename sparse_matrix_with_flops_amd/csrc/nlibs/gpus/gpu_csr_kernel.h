@@ -27,6 +27,10 @@ void gpuShardedRmclIter(const int maxIter, const CSR Mgt, CSR& Mt, int shards);
 // debug dump of a DEVICE CSR (nlibs/gpus/gpu_csr_kernel.h:7, .cu:15-42: message, shape and device pointers, the triples,
 // then the raw rowPtr and colInd/values arrays); the arrays are brought to the host and printed there
 void gpuOutputCSRWrapper(const CSR dA, const char* msg);
+// saving a DEVICE CSR as an edge-list file (what the reference does with toCpuCSR + CSR::output into a file): the lines are
+// formatted on the device (hip_write_edge_file).  fmt: SPGEMM_EDGE_FMT_FIXED6 (CSR::output's line) or _ROUNDTRIP;
+// header: 0 none, 1 the size line readSNAPFile reads, 2 a MatrixMarket banner, one-based lines
+void gpuWriteCSRWrapper(const CSR dA, const char* path, int fmt, int header);
 
 // bool resultsComparison(CSR& hC, CSR& rC, const vector<int>& hv, const int* hqueue) (mindex2-cuda/nGpuSpMM.cc:138-240):
 // hC (result under test) against rC (reference result), whole matrix first, then bin by bin; prints one line per bin

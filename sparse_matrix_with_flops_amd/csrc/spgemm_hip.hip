@@ -2367,11 +2367,16 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 #include "edges_device.hpp"
 
 // ------------------------------------------------------------------------------------------------
+// device CSR -> edge-list text: the way out, the inverse of the parse
+// ------------------------------------------------------------------------------------------------
+#include "edges_write_device.hpp"
+
+// ------------------------------------------------------------------------------------------------
 // dense matrix: CSR -> dense, dense -> CSR, the dense product
 // ------------------------------------------------------------------------------------------------
 #include "dense_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the eight headers above
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the nine headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

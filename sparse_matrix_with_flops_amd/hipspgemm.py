@@ -19,6 +19,8 @@ Mirrors (reference file:line):
                               struct MCSR                      nlibs/MCSR.h:6-9, nlibs/MCSR.cc:58-92
   edge_text_header(data) / parse_edge_text(data, declared) / read_edge_file(path, isTrans, flags)
                               COO::readSNAPFile (the text)     nlibs/COO.cc:48-158   (parsed on the device; dtype= picks the value type)
+  format_csr_edges(dM) / csr_to_edge_text(dM) / write_edge_file(dM, path, fmt, flags, header)
+                              CSR::output (the text)           nlibs/CSR.h:109-168   (formatted on the device; the matrix's dtype)
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -69,6 +71,8 @@ EXPORTS = [
     "hip_csr_to_mcsr", "hip_csr_to_mcsr_f64", "hip_mcsr_to_csr", "hip_mcsr_to_csr_f64",
     "hip_edge_text_header", "hip_parse_edge_lines", "hip_parse_edge_text", "hip_read_edge_file",
     "hip_coo_to_csr_f64", "hip_parse_edge_lines_f64", "hip_parse_edge_text_f64", "hip_read_edge_file_f64",
+    "hip_edge_text_write_header", "hip_format_csr_edges", "hip_format_csr_edges_f64", "hip_csr_to_edge_text",
+    "hip_csr_to_edge_text_f64", "hip_write_edge_file", "hip_write_edge_file_f64",
     "hip_csr_to_dense", "hip_csr_to_dense_f64", "hip_dense_to_csr", "hip_dense_to_csr_f64",
     "hip_dense_gemm", "hip_dense_gemm_f64",
 ]
@@ -105,6 +109,16 @@ class EdgeStats(C.Structure):
     _fields_ = [("lines", C.c_longlong), ("first_bad_line", C.c_longlong), ("entries", C.c_int), ("slow_lines", C.c_int),
                 ("ms_upload", C.c_float), ("ms_split", C.c_float), ("ms_parse", C.c_float), ("ms_slow", C.c_float),
                 ("ms_total", C.c_float)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class EdgeWriteStats(C.Structure):
+    """spgemm_edge_write_stats: what hip_format_csr_edges / hip_csr_to_edge_text / hip_write_edge_file report"""
+    _fields_ = [("entries", C.c_longlong), ("bytes", C.c_longlong), ("slow_entries", C.c_longlong), ("slabs", C.c_int),
+                ("ms_length", C.c_float), ("ms_scan", C.c_float), ("ms_write", C.c_float), ("ms_slow", C.c_float),
+                ("ms_download", C.c_float), ("ms_file", C.c_float), ("ms_total", C.c_float)]
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_}
@@ -234,6 +248,16 @@ def lib():
         L.hip_parse_edge_lines_f64.argtypes = L.hip_parse_edge_lines.argtypes
         L.hip_parse_edge_text_f64.argtypes = L.hip_parse_edge_text.argtypes
         L.hip_read_edge_file_f64.argtypes = L.hip_read_edge_file.argtypes
+        L.hip_edge_text_write_header.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                                 C.POINTER(C.c_size_t)]
+        csr_in = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        wst = [C.POINTER(C.c_size_t), C.POINTER(EdgeWriteStats)]
+        L.hip_format_csr_edges.argtypes = csr_in + [C.c_int] * 4 + [C.POINTER(C.c_void_p)] + wst
+        L.hip_csr_to_edge_text.argtypes = csr_in + [C.c_int] * 4 + [C.c_void_p, C.c_size_t] + wst
+        L.hip_write_edge_file.argtypes = [C.c_void_p, C.c_char_p] + csr_in[1:] + [C.c_int] * 3 + [C.POINTER(EdgeWriteStats)]
+        L.hip_format_csr_edges_f64.argtypes = L.hip_format_csr_edges.argtypes
+        L.hip_csr_to_edge_text_f64.argtypes = L.hip_csr_to_edge_text.argtypes
+        L.hip_write_edge_file_f64.argtypes = L.hip_write_edge_file.argtypes
         L.hip_csr_to_dense.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_longlong]
         L.hip_csr_to_dense_f64.argtypes = L.hip_csr_to_dense.argtypes
@@ -1753,3 +1777,74 @@ def read_edge_file(path, isTrans=True, flags=COO_DEDUPE, handle=None, dtype=np.f
     M = CSR(av, ja, ia, rows.value, cols.value, nnz, True, dtype=dtype)
     M.edge_stats = st.as_dict()
     return M
+
+
+# ---------------------------------------------------------------------------------------------
+# the way out (include/spgemm_hip.h "the way out"): a device CSR -> edge-list text, formatted on the device; what
+# toCpuCSR + CSR::output's printf loop (nlibs/CSR.cc) does on the host
+# ---------------------------------------------------------------------------------------------
+EDGE_FMT_FIXED6, EDGE_FMT_ROUNDTRIP = 0, 1
+EDGE_HEADER_NONE, EDGE_HEADER_SIZES, EDGE_HEADER_MATRIX_MARKET = 0, 1, 2
+
+
+def edge_text_write_header(header, rows, cols, entries):
+    """hip_edge_text_write_header (pure host) -> the header bytes: b"" (0), the size line "rows cols entries" (1), or a
+    MatrixMarket banner and the size line (2)."""
+    buf, n = C.create_string_buffer(128), C.c_size_t()
+    _check(lib().hip_edge_text_write_header(buf, len(buf), int(header), int(rows), int(cols), int(entries), C.byref(n)),
+           "hip_edge_text_write_header")
+    return buf.raw[:n.value]
+
+
+def _edge_write_args(what, dM, row0, row1, fmt, flags, dtype):
+    """what every write call checks before any device work -> (dtype, row0, row1, fmt, flags)"""
+    if not isinstance(dM, CSR) or not dM.on_device:
+        raise SpgemmError(f"{what}: takes a device CSR")
+    dtype = _value_dtype(dM.dtype if dtype is None else dtype)
+    if dtype != dM.dtype:
+        raise SpgemmError(f"{what}: dtype {dtype} does not match the matrix's {dM.dtype}")
+    fmt = int(fmt)
+    if fmt not in (EDGE_FMT_FIXED6, EDGE_FMT_ROUNDTRIP):
+        raise SpgemmError(f"{what}: unknown fmt {fmt}: EDGE_FMT_FIXED6 or EDGE_FMT_ROUNDTRIP")
+    row0, row1 = int(row0), dM.rows if row1 is None else int(row1)
+    if not 0 <= row0 <= row1 <= dM.rows:
+        raise SpgemmError(f"{what}: rows [{row0}, {row1}) of {dM.rows}")
+    return dtype, row0, row1, fmt, _edge_flags(flags)
+
+
+def format_csr_edges(dM, row0=0, row1=None, fmt=EDGE_FMT_FIXED6, flags=0, handle=None, dtype=None):
+    """hip_format_csr_edges: rows [row0, row1) of the device CSR `dM` as text in device memory -> (dText, nbytes, stats
+    dict); dText comes from the library pool (release with dev_free).  dtype: None = the matrix's, else it must match."""
+    dtype, row0, row1, fmt, flags = _edge_write_args("format_csr_edges", dM, row0, row1, fmt, flags, dtype)
+    text, n, st = C.c_void_p(), C.c_size_t(), EdgeWriteStats()
+    _call("hip_format_csr_edges", dtype, _hp(handle), dM.rows, dM.cols, *_ptrs(dM.rowPtr, dM.colInd, dM.values), row0, row1,
+          fmt, flags, C.byref(text), C.byref(n), C.byref(st))
+    return text.value, int(n.value), st.as_dict()
+
+
+def csr_to_edge_text(dM, row0=0, row1=None, fmt=EDGE_FMT_FIXED6, flags=0, handle=None, dtype=None):
+    """hip_csr_to_edge_text: the same text on the host -> (bytes, stats dict): a first call sizes the buffer, a second
+    fills it."""
+    dtype, row0, row1, fmt, flags = _edge_write_args("csr_to_edge_text", dM, row0, row1, fmt, flags, dtype)
+    args = (_hp(handle), dM.rows, dM.cols, *_ptrs(dM.rowPtr, dM.colInd, dM.values), row0, row1, fmt, flags)
+    n, st = C.c_size_t(), EdgeWriteStats()
+    _call("hip_csr_to_edge_text", dtype, *args, None, 0, C.byref(n), None)
+    buf = C.create_string_buffer(max(int(n.value), 1))
+    _call("hip_csr_to_edge_text", dtype, *args, buf, int(n.value), C.byref(n), C.byref(st))
+    return buf.raw[:n.value], st.as_dict()
+
+
+def write_edge_file(dM, path, fmt=EDGE_FMT_FIXED6, flags=0, header=EDGE_HEADER_SIZES, handle=None, dtype=None):
+    """hip_write_edge_file: the device CSR `dM` as an edge-list file -> stats dict.  header: EDGE_HEADER_NONE, _SIZES (the
+    line readSNAPFile reads) or _MATRIX_MARKET (banner, one-based lines).  The body is formatted on the device in slabs
+    (SPGEMM_EDGE_SLAB bytes of text, read per call) and written while the next slab is formatted."""
+    dtype, _, _, fmt, flags = _edge_write_args("write_edge_file", dM, 0, None, fmt, flags, dtype)
+    if not isinstance(path, (str, bytes, os.PathLike)):
+        raise SpgemmError(f"write_edge_file: path must be a str, bytes or os.PathLike, not {type(path).__name__}")
+    header = int(header)
+    if header not in (EDGE_HEADER_NONE, EDGE_HEADER_SIZES, EDGE_HEADER_MATRIX_MARKET):
+        raise SpgemmError(f"write_edge_file: unknown header {header}")
+    st = EdgeWriteStats()
+    _call("hip_write_edge_file", dtype, _hp(handle), os.fsencode(path), dM.rows, dM.cols,
+          *_ptrs(dM.rowPtr, dM.colInd, dM.values), fmt, flags, header, C.byref(st))
+    return st.as_dict()
