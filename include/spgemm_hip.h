@@ -796,6 +796,55 @@ int hip_dense_gemm(spgemm_handle* h, int m, int n, int k, const float* dA, long 
 int hip_dense_gemm_f64(spgemm_handle* h, int m, int n, int k, const double* dA, long long lda, const double* dB,
                        long long ldb, double* dC, long long ldc);
 
+/* ---- clusters from a finished R-MCL result: attractors, connected components, labels -> clusters ----------------------------
+ * The reference stops at the flow matrix Mt (nlibs/qrmcl.cc:136-164); these calls read the clusters out of it on the
+ * device.  Interpretation only: the R-MCL loop is not touched.  All CSR and label arrays are device pointers, the counts
+ * are host memory; h == NULL = the default handle; a call returns after the device work has completed; array outputs
+ * handed out as int** come from the library pool (release with spgemm_hip_free).  Argument checks (m != n, a null
+ * output, a negative size, nnz > 0 with null arrays -> SPGEMM_ERR_ARG) run before any device is touched.  Every value
+ * that becomes an address (rowPtr, the columns, the labels) is validated by a read-only pass whose flag the host reads
+ * before it is used: bad input -> SPGEMM_ERR_INPUT with a message.  On any error the int** outputs are NULL, nothing
+ * stays allocated, the handle stays usable.  Every result is integers and the same on every call. */
+#define SPGEMM_CC_MAX_ROUNDS 64   /* hard cap of hip_csr_connected_components; at most ceil(log2 m) + 1 are needed */
+
+/* Row i of Mt holds the flow out of node i; dParent[i] (caller's int[m]) = the column of the largest value of row i.
+ * The rule does not depend on the storage order of a row (product rows are not column-sorted): an entry (v, c) beats
+ * the best so far (bv, bc) iff v > bv, or v == bv and c < bc, starting from (-inf, INT_MAX).  So: of equal maxima the
+ * smallest column wins; a NaN never wins; -0.0 == +0.0 and the smaller column wins between them; a row of only -inf
+ * gives its smallest column; an empty row and an all-NaN row give dParent[i] = i.  Values are compared in their own
+ * type: the _f64 twin does not pass through float.  m != n -> SPGEMM_ERR_ARG; a bad rowPtr or a column outside [0, n)
+ * -> SPGEMM_ERR_INPUT, dParent untouched.  m == 0 is valid.
+ * hip_rmcl_attractor_lanes: the lanes per row (4, 16 or 64) the kernels use for an m-row matrix with nnz entries. */
+int hip_rmcl_attractors    (spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                            int* dParent);
+int hip_rmcl_attractors_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                            int* dParent);
+int hip_rmcl_attractor_lanes(int m, int nnz);
+
+/* Weakly connected components of a square CSR pattern: every stored entry (i, j) is an undirected edge, values are not
+ * read, self loops and repeated entries are harmless.  dLabel[v] (caller's int[m]) = the smallest vertex id of v's
+ * component: canonical, equal bit for bit to any correct host implementation.  *ncomp = the number of v with
+ * dLabel[v] == v; *rounds (may be NULL) = hook-and-shortcut rounds taken, >= 1 for m > 0, the last of them changed
+ * nothing.  More than SPGEMM_CC_MAX_ROUNDS rounds -> SPGEMM_ERR_INTERNAL (never a spin).  m != n -> SPGEMM_ERR_ARG; a bad
+ * rowPtr or a column outside [0, n) -> SPGEMM_ERR_INPUT, dLabel untouched.  m == 0: *ncomp = 0, *rounds = 0. */
+int hip_csr_connected_components(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, int* dLabel,
+                                 int* ncomp, int* rounds);
+
+/* dLabel must be canonical (label[v] <= v and label[label[v]] == label[v], what hip_csr_connected_components writes):
+ * anything else -> SPGEMM_ERR_INPUT.  Clusters are numbered 0 .. *k - 1 in ascending order of their smallest member.
+ * (*dCluster)[v] = the number of v's cluster, int[m]; (*dClusterPtr)[c] .. [c + 1] = the range of cluster c in
+ * *dMembers, int[*k + 1] with [*k] == m; *dMembers = the vertices cluster by cluster, ascending inside a cluster, int[m].
+ * Cluster sizes are the differences of *dClusterPtr.  m == 0: *k = 0, (*dClusterPtr)[0] = 0. */
+int hip_labels_to_clusters(spgemm_handle* h, int m, const int* dLabel, int* k, int** dCluster, int** dClusterPtr,
+                           int** dMembers);
+
+/* The three chained: attractors of Mt, components of the functional graph i -> dParent[i] (the CSR with rowPtr 0..m),
+ * labels to clusters.  A node joins its attractor; attractors that point at each other form one cluster. */
+int hip_rmcl_clusters    (spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA, int* k,
+                          int** dCluster, int** dClusterPtr, int** dMembers);
+int hip_rmcl_clusters_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA, int* k,
+                          int** dCluster, int** dClusterPtr, int** dMembers);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

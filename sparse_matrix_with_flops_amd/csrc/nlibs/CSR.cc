@@ -393,6 +393,31 @@ void gpuWriteCSRWrapper(const CSR dA, const char* path, int fmt, int header) {
              "gpuWriteCSRWrapper");
 }
 
+std::vector<int> gpuRmclClusters(const CSR& dMt, int* k) {
+  int kk = 0, *dCluster = 0, *dPtr = 0, *dMembers = 0;
+  hip_or_die(hip_rmcl_clusters(NULL, dMt.rows, dMt.cols, dMt.nnz, dMt.rowPtr, dMt.colInd, dMt.values, &kk, &dCluster, &dPtr,
+                               &dMembers), "gpuRmclClusters");
+  std::vector<int> cluster((size_t)dMt.rows);
+  if (dMt.rows > 0) hip_or_die(spgemm_hip_memcpy_d2h(cluster.data(), dCluster, sizeof(int) * cluster.size()), "gpuRmclClusters");
+  spgemm_hip_free(dCluster);
+  spgemm_hip_free(dPtr);
+  spgemm_hip_free(dMembers);
+  if (k) *k = kk;
+  return cluster;
+}
+
+std::vector<int> gpuConnectedComponents(const CSR& dM) {
+  std::vector<int> label((size_t)dM.rows);
+  int* dLabel = 0;
+  int ncomp = 0;
+  hip_or_die(spgemm_hip_malloc((void**)&dLabel, sizeof(int) * (label.size() + 1)), "gpuConnectedComponents");
+  hip_or_die(hip_csr_connected_components(NULL, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, dLabel, &ncomp, NULL),
+             "gpuConnectedComponents");
+  if (dM.rows > 0) hip_or_die(spgemm_hip_memcpy_d2h(label.data(), dLabel, sizeof(int) * label.size()), "gpuConnectedComponents");
+  spgemm_hip_free(dLabel);
+  return label;
+}
+
 std::vector<int> CSR::nnzStats() const {
   std::vector<int> stats(SPGEMM_NNZ_STATS_LEN, 0);
   for (int r = 0; r < rows; ++r) {

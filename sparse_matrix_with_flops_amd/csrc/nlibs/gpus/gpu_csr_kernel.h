@@ -31,6 +31,13 @@ void gpuOutputCSRWrapper(const CSR dA, const char* msg);
 // formatted on the device (hip_write_edge_file).  fmt: SPGEMM_EDGE_FMT_FIXED6 (CSR::output's line) or _ROUNDTRIP;
 // header: 0 none, 1 the size line readSNAPFile reads, 2 a MatrixMarket banner, one-based lines
 void gpuWriteCSRWrapper(const CSR dA, const char* path, int fmt, int header);
+// clusters of a finished R-MCL result (no counterpart in the reference, which stops at Mt: nlibs/qrmcl.cc:136-164), read on
+// the device (include/spgemm_hip.h "clusters from a finished R-MCL result").  DEVICE CSRs in, HOST vectors out.
+// gpuRmclClusters: every node joins the column of the largest value of its row of dMt, attractors that point at each other
+// are one cluster -> per node the number of its cluster, clusters numbered by ascending smallest member; *k = their count.
+// gpuConnectedComponents: per vertex the smallest vertex id of its weakly connected component (pattern of a square dM).
+std::vector<int> gpuRmclClusters(const CSR& dMt, int* k);
+std::vector<int> gpuConnectedComponents(const CSR& dM);
 
 // bool resultsComparison(CSR& hC, CSR& rC, const vector<int>& hv, const int* hqueue) (mindex2-cuda/nGpuSpMM.cc:138-240):
 // hC (result under test) against rC (reference result), whole matrix first, then bin by bin; prints one line per bin

@@ -2376,7 +2376,12 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // ------------------------------------------------------------------------------------------------
 #include "dense_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the nine headers above
+// ------------------------------------------------------------------------------------------------
+// clusters from a finished R-MCL result: attractors, connected components, labels -> clusters
+// ------------------------------------------------------------------------------------------------
+#include "clusters_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the ten headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

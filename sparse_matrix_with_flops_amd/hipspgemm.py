@@ -21,6 +21,8 @@ Mirrors (reference file:line):
                               COO::readSNAPFile (the text)     nlibs/COO.cc:48-158   (parsed on the device; dtype= picks the value type)
   format_csr_edges(dM) / csr_to_edge_text(dM) / write_edge_file(dM, path, fmt, flags, header)
                               CSR::output (the text)           nlibs/CSR.h:109-168   (formatted on the device; the matrix's dtype)
+  rmcl_attractors(dMt) / connected_components(dM) / rmcl_clusters(dMt) -> Clusters
+                              (none: the reference stops at Mt, nlibs/qrmcl.cc:136-164; semantics: tests/clusters_ref.py)
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -75,6 +77,8 @@ EXPORTS = [
     "hip_csr_to_edge_text_f64", "hip_write_edge_file", "hip_write_edge_file_f64",
     "hip_csr_to_dense", "hip_csr_to_dense_f64", "hip_dense_to_csr", "hip_dense_to_csr_f64",
     "hip_dense_gemm", "hip_dense_gemm_f64",
+    "hip_rmcl_attractors", "hip_rmcl_attractors_f64", "hip_rmcl_attractor_lanes", "hip_csr_connected_components",
+    "hip_labels_to_clusters", "hip_rmcl_clusters", "hip_rmcl_clusters_f64",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -266,6 +270,15 @@ def lib():
         L.hip_dense_to_csr_f64.argtypes = L.hip_dense_to_csr.argtypes
         L.hip_dense_gemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p, C.c_longlong] * 3
         L.hip_dense_gemm_f64.argtypes = L.hip_dense_gemm.argtypes
+        L.hip_rmcl_attractors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hip_rmcl_attractors_f64.argtypes = L.hip_rmcl_attractors.argtypes
+        L.hip_rmcl_attractor_lanes.argtypes = [C.c_int, C.c_int]
+        L.hip_csr_connected_components.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   _I, _I]
+        L.hip_labels_to_clusters.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _I] + [C.POINTER(C.c_void_p)] * 3
+        L.hip_rmcl_clusters.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _I] + \
+            [C.POINTER(C.c_void_p)] * 3
+        L.hip_rmcl_clusters_f64.argtypes = L.hip_rmcl_clusters.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -1848,3 +1861,105 @@ def write_edge_file(dM, path, fmt=EDGE_FMT_FIXED6, flags=0, header=EDGE_HEADER_S
     _call("hip_write_edge_file", dtype, _hp(handle), os.fsencode(path), dM.rows, dM.cols,
           *_ptrs(dM.rowPtr, dM.colInd, dM.values), fmt, flags, header, C.byref(st))
     return st.as_dict()
+
+
+# ---------------------------------------------------------------------------------------------
+# clusters (include/spgemm_hip.h "clusters from a finished R-MCL result"): attractors of the flow matrix, connected
+# components, labels -> clusters.  The reference has no counterpart: it stops at Mt.
+# ---------------------------------------------------------------------------------------------
+CC_MAX_ROUNDS = 64
+
+
+def rmcl_attractor_lanes(m, nnz):
+    """hip_rmcl_attractor_lanes (pure host): the lanes per row (4, 16 or 64) the attractor and hook kernels use"""
+    return int(lib().hip_rmcl_attractor_lanes(int(m), int(nnz)))
+
+
+def rmcl_attractors_raw(handle, m, n, nnz, IA, JA, VA, parent, dtype=np.float32):
+    """hip_rmcl_attractors / _f64 on raw device pointers: parent (the caller's int32[m]) = per row the column of the
+    largest value, the smallest such column on a tie, the row itself where nothing wins"""
+    _call("hip_rmcl_attractors", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA, parent))
+
+
+def connected_components_raw(handle, m, n, nnz, IA, JA, label):
+    """hip_csr_connected_components: label (the caller's int32[m]) = the smallest vertex id of each vertex's weakly
+    connected component -> (ncomp, rounds)"""
+    ncomp, rounds = C.c_int(0), C.c_int(0)
+    _check(lib().hip_csr_connected_components(_hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, label), C.byref(ncomp),
+                                              C.byref(rounds)), "hip_csr_connected_components")
+    return ncomp.value, rounds.value
+
+
+def labels_to_clusters_raw(handle, m, label):
+    """hip_labels_to_clusters on canonical device labels -> (k, dCluster, dClusterPtr, dMembers) from the library pool"""
+    k, out = C.c_int(0), _CsrOut(count=False)
+    _check(lib().hip_labels_to_clusters(_hp(handle), int(m), C.c_void_p(label), C.byref(k), *out.refs()),
+           "hip_labels_to_clusters")
+    return (k.value,) + out.values()
+
+
+class Clusters:
+    """what rmcl_clusters / labels_to_clusters leave on the device: `k` clusters numbered by ascending smallest member;
+    cluster (int32[m]: a vertex's cluster), ptr (int32[k + 1]) and members (int32[m]: cluster c's vertices, ascending, are
+    members[ptr[c]:ptr[c + 1]]) are device pointers."""
+
+    def __init__(self, m, k, cluster, ptr, members):
+        self.m, self.k, self.cluster, self.ptr, self.members = int(m), int(k), cluster, ptr, members
+
+    def to_host(self):
+        """-> (cluster, ptr, members) numpy int32 arrays"""
+        return (d2h(self.cluster, self.m, np.int32), d2h(self.ptr, self.k + 1, np.int32), d2h(self.members, self.m, np.int32))
+
+    def dispose(self):
+        for p in (self.cluster, self.ptr, self.members):
+            dev_free(p)
+        self.cluster = self.ptr = self.members = None
+
+
+def _square_device(what, dM):
+    if not isinstance(dM, CSR) or not dM.on_device:
+        raise SpgemmError(f"{what}: takes a device CSR")
+    _need_square(dM, what)
+    return _value_dtype(dM.dtype)
+
+
+def rmcl_attractors(dMt, handle=None):
+    """per node the column its largest flow goes to (hip_rmcl_attractors, the matrix's dtype) -> int32 device pointer of
+    dMt.rows entries (release with dev_free)"""
+    dt = _square_device("rmcl_attractors", dMt)
+    parent = dev_alloc(4 * dMt.rows)
+    try:
+        rmcl_attractors_raw(handle, dMt.rows, dMt.cols, dMt.nnz, dMt.rowPtr, dMt.colInd, dMt.values, parent, dt)
+    except SpgemmError:
+        dev_free(parent)
+        raise
+    return parent
+
+
+def connected_components(dM, handle=None):
+    """weakly connected components of the pattern of a square device CSR -> (labels, ncomp, rounds); labels: int32
+    device pointer of dM.rows entries, the smallest vertex id of each vertex's component (release with dev_free)"""
+    _square_device("connected_components", dM)
+    label = dev_alloc(4 * dM.rows)
+    try:
+        ncomp, rounds = connected_components_raw(handle, dM.rows, dM.cols, dM.nnz, dM.rowPtr, dM.colInd, label)
+    except SpgemmError:
+        dev_free(label)
+        raise
+    return label, ncomp, rounds
+
+
+def labels_to_clusters(label, m, handle=None):
+    """canonical device labels (connected_components) -> Clusters"""
+    k, cluster, ptr, members = labels_to_clusters_raw(handle, m, label)
+    return Clusters(m, k, cluster, ptr, members)
+
+
+def rmcl_clusters(dMt, handle=None):
+    """hip_rmcl_clusters / _f64: the clusters of a finished R-MCL flow matrix (every node joins the column of its largest
+    flow; attractors that point at each other are one cluster) -> Clusters"""
+    dt = _square_device("rmcl_clusters", dMt)
+    k, out = C.c_int(0), _CsrOut(count=False)
+    _call("hip_rmcl_clusters", dt, _hp(handle), dMt.rows, dMt.cols, dMt.nnz, *_ptrs(dMt.rowPtr, dMt.colInd, dMt.values),
+          C.byref(k), *out.refs())
+    return Clusters(dMt.rows, k.value, *out.values())
