@@ -323,6 +323,13 @@ int spgemm_hip_debug_midrow_paths(spgemm_handle* h, int* rows, int* direct_rows,
 /* ... and the log behind it: re-hits logged by the rows that went direct (the sum of products - nnz over those rows), ints
  * of log space the call's symbolic pass reserved or would have reserved, ints the log had. */
 int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, long long* reserved, long long* capacity);
+/* ... and the two direct kernels of the rows of 513-2048 products: how many of the latest product's direct rows took the
+ * wave-per-row kernel (at most 448 re-hits, one wave and a 512-slot table per row) and how many the four-wave kernel (the
+ * rows above that up to the cap).  The kernels count on the device; the call waits for the handle's stream.
+ * SPGEMM_MD_WAVE=0 (read at handle creation) keeps the four-wave kernel for all of them; so does a product with fewer such
+ * rows than SPGEMM_MW_MINROWS (default: 32 x the number of CUs; the tests set 1).  SPGEMM_MW_PERCU=<1..32> sets the waves
+ * of the wave-per-row kernel per CU (default 16). */
+int spgemm_hip_debug_midrow_kernels(spgemm_handle* h, long long* wave_rows, long long* multiwave_rows);
 
 /* ---- the step in front of the path: COO -> CSR on device arrays -------------
  * Replaces COO::addSelfLoopIfNeeded (nlibs/COO.cc:160-188), COO::makeOrdered / orderedAndDuplicatesRemoving

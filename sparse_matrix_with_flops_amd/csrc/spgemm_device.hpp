@@ -1312,6 +1312,11 @@ __device__ __forceinline__ int next_row(int* ctr, int* slot, int prev) {
   return q;
 }
 __device__ __forceinline__ int next_row(int* ctr, int* slot) { return next_row<1>(ctr, slot, -1); }
+// A queue of `count` rows handed out R at a time has ceil(count / R) batches, so blocks beyond that many can never all be
+// needed: they leave before their first dequeue.  The launches over a fallback list are sized by the bin (the list's length is
+// on the device only) and the list is short or empty most of the time: a thousand blocks that each spend one atomic on the
+// queue word to learn that took 0.035 ms per launch on the headline matrix (profiles/README.md, "Mid rows: one wave per row").
+__device__ __forceinline__ bool surplus_block(int count, int R) { return (long long)blockIdx.x * R >= (long long)count; }
 
 // per-row metadata, fetched one row ahead of use so that the dependent rowIds -> IA/IC loads of the
 // next row overlap the current row's work
@@ -1506,6 +1511,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
   constexpr int T = WAVE * NW;
   int first = binPtr[bin], count = binPtr[bin + 1] - first;
   constexpr int QB = NW >= 8 ? 2 : 4;            // rows per dequeue
+  if (NW > 1 && surplus_block(count, QB)) return;
   int stride = (int)gridDim.x;
   if (NW == 1) {                                 // static schedule: XCD-contiguous (see xcd_range)
     const XcdRange xr = xcd_range(count);
@@ -2316,13 +2322,23 @@ struct MidDirectShared {
   int emitted;
 };
 struct MidMeta { RowMeta m; int ls, lc; };              // + first log entry, re-hits (-1: not a row of this kernel)
+// Bin 6 has a second direct kernel, k_num_midwave (one wave per row, a table of MW_SLOTS slots).  THE rule for which of the
+// two takes a row, read by both: the wave kernel takes the rows that logged (lm = the row's {first log entry, re-hits}) at
+// most waveCap <= bd_cap(MW_SLOTS) re-hits and whose log lies inside the log; k_num_middirect keeps the other rows up to
+// its own cap.  waveCap < 0: no wave kernel in this call (bin 7, SPGEMM_MD_WAVE=0, a bin below the row threshold).
+constexpr int MW_SLOTS = 512;
+__device__ __forceinline__ bool midwave_takes(int2 lm, long long logCap, int waveCap) {
+  return lm.y >= 0 && lm.y <= waveCap && lm.x >= 0 && (long long)lm.x + lm.y <= logCap;
+}
 __device__ __forceinline__ MidMeta load_meta_mid(const int* rows, int q, int count, const int* IA, const int* IC,
-                                                 const int* rowFlops, const int2* meta, int cap) {
+                                                 const int* rowFlops, const int2* meta, int cap, long long logCap, int waveCap) {
   MidMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
   if (q < count) {
     const int row = rows[q];
     const int2 lm = meta[row];
-    if (lm.y >= 0 && lm.y <= cap) { d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC, rowFlops); }
+    if (lm.y >= 0 && lm.y <= cap && !midwave_takes(lm, logCap, waveCap)) {
+      d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC, rowFlops);
+    }
   }
   return d;
 }
@@ -2338,7 +2354,8 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
                                                              float* __restrict__ C, int* __restrict__ err,
                                                              int* __restrict__ qctr, const int* __restrict__ rowFlops,
                                                              const int2* __restrict__ meta, const int* __restrict__ mlog,
-                                                             long long logCap, int cap) {
+                                                             long long logCap, int cap, int waveCap,
+                                                             unsigned long long* __restrict__ took) {
   constexpr int T = WAVE * NW;
   static_assert(S % T == 0 && S / T <= 8, "every wave sweeps whole 64-slot steps");
   static_assert(sizeof(WalkNumber<NW>) <= S * sizeof(slot_t), "the numbering of an expanded row lives in the table");
@@ -2347,13 +2364,15 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
   const int first = binPtr[bin], count = binPtr[bin + 1] - first;
   const int* rows = rowIds + first;
   cap = min(cap, bd_cap(S));                           // a probe always ends at an empty slot
-  if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
   constexpr int QB = NW >= 8 ? 2 : 4;                  // rows per dequeue, as in k_num_hash
+  if (surplus_block(count, QB)) return;
+  if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
   int q = next_row<QB>(qctr, &sh.qslot, -1);
-  MidMeta cur = load_meta_mid(rows, q, count, IA, IC, rowFlops, meta, cap);
+  MidMeta cur = load_meta_mid(rows, q, count, IA, IC, rowFlops, meta, cap, logCap, waveCap);
+  int tookRows = 0;                                    // rows of this block that went direct here (test hook)
   while (q < count) {
     const int qn = next_row<QB>(qctr, &sh.qslot, q);
-    const MidMeta nxt = load_meta_mid(rows, qn, count, IA, IC, rowFlops, meta, cap);
+    const MidMeta nxt = load_meta_mid(rows, qn, count, IA, IC, rowFlops, meta, cap, logCap, waveCap);
     const int as = cur.m.as, ae = cur.m.ae;
     const int outBase = cur.m.x0, outEnd = cur.m.x1;
     const int want = outEnd - outBase;
@@ -2362,6 +2381,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
     const unsigned lim = (unsigned)max(want, 0);       // every store stays inside the row's own range
     // (block-uniform branches; a row's log must lie inside the log whatever the metadata says)
     const bool mine = cur.lc >= 0 && (long long)cur.ls >= 0 && (long long)cur.ls + cur.lc <= logCap;
+    tookRows += __builtin_amdgcn_readfirstlane(mine ? 1 : 0);   // (block-uniform: kept in a scalar register)
     if (mine && want == cur.m.x2) {
       for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
                                        [&](const bool (&act)[MD_U], const int (&col)[MD_U], const float (&val)[MD_U], int p0) {
@@ -2456,6 +2476,210 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
     cur = nxt;
     q = qn;
   }
+  if (took && tid == 0 && tookRows) atomicAdd(took, (unsigned long long)tookRows);
+}
+
+// ---- bin 6, one wave per row (k_num_midwave).  The four waves k_num_middirect<4,1024> gives a row of 513-2048 products
+// each run the whole per-row instruction stream -- dequeue, clear, log insert, staging, unit table, claim loop, sweep, twelve
+// barriers -- for ONE trip of products.  Here a row has one wave and the wave-per-row walk (for_each_product<1>: no unit
+// table, no claim counter, no barrier), in the ways of k_num_hash<1, ..>: static XCD-contiguous schedule, the next row's
+// metadata and first A entries in flight one row ahead, up to 8 rounds gathered per trip.  The output position is a
+// register of the wave: no LDS counter.  The rounds of a trip are probed MW_CH at a time (registers).
+// Measured (profiles/README.md, "Mid rows: one wave per row"): 30 % fewer vector and scalar instructions than the four-wave
+// kernel, and with one launch per layout slot the SAME time -- a static schedule of 4-9 rows per wave ends on its slowest
+// wave, twice.  What pays is one launch over both slots with every wave's heavy rows first (MidWaveRows).
+#ifndef SMF_MW_CH
+#define SMF_MW_CH 4
+#endif
+constexpr int MW_CH = SMF_MW_CH;
+struct MidWaveShared {
+  slot_t tab[MW_SLOTS];
+  WalkStage1 st;
+};
+// The rows of one launch: this XCD's eighth of the bin's second layout slot (1025-2048 products) FIRST, then its eighth of
+// the first slot (513-1024), as one sequence that the waves of the XCD stride over -- a wave's heavy rows come first and the
+// launch ends on the light ones (one launch per slot, each with its own tail: 2 x 0.150 ms; profiles/README.md).
+struct MidWaveRows {
+  const int* hi; int nhi;                              // (second slot)
+  const int* lo; int nlo;
+  __device__ __forceinline__ int count() const { return nhi + nlo; }
+  __device__ __forceinline__ int at(int q) const { return q < nhi ? hi[q] : lo[q - nhi]; }
+};
+// (a row with a log that this kernel does not take: lc = -1, ls = 1 and the row id -- it goes on k_num_middirect's list)
+__device__ __forceinline__ MidMeta load_meta_midwave(const MidWaveRows& rows, int q, const int* IA, const int* IC,
+                                                     const int* rowFlops, const int2* meta, long long logCap, int waveCap) {
+  MidMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
+  if (q < rows.count()) {
+    const int row = rows.at(q);
+    const int2 lm = meta[row];
+    if (midwave_takes(lm, logCap, waveCap)) {
+      d.ls = lm.x; d.lc = lm.y;
+      d.m.row = row; d.m.as = IA[row]; d.m.ae = IA[row + 1]; d.m.x0 = IC[row]; d.m.x1 = IC[row + 1]; d.m.x2 = rowFlops[row];
+    } else if (lm.y >= 0) { d.ls = 1; d.m.row = row; }
+  }
+  return d;
+}
+
+// U rounds of products against the table of the row's repeated columns, keys read-only: a hit adds under EXEC, a miss is
+// stored at `pos` + its ballot rank.  Returns the position behind the misses.
+template <int U>
+__device__ __forceinline__ int midwave_rounds(char* base, int dumB, int size, int shift, const bool (&act)[U],
+                                              const int (&col)[U], const float (&val)[U], int pos, unsigned lim,
+                                              int* __restrict__ JCrow, float* __restrict__ Crow, int* __restrict__ err) {
+  const int maskB = size * 8 - 1;
+  int hB[U], hitB[U];                                  // byte offsets; dumB = "done" / "no hit"
+  bool miss[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
+    hB[u] = act[u] ? (int)(h * 8u) : dumB;
+    hitB[u] = dumB;
+    miss[u] = false;
+  }
+  for (int probe = 0;;) {
+    int key[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
+    ++probe;
+    int pendBits = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool pend = hB[u] != dumB;
+      const bool hit = pend && key[u] == col[u];
+      const bool emp = pend && key[u] == EMPTY_KEY;
+      hitB[u] = hit ? hB[u] : hitB[u];
+      miss[u] = miss[u] || emp;
+      hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the log insert
+      pendBits |= hB[u] ^ dumB;
+    }
+    if (ballot64(pendBits != 0) == 0ull) break;
+    if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned long long mk = ballot64(miss[u]);
+    const unsigned o = (unsigned)(pos + mask_rank(mk));
+    if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+    pos += __popcll(mk);
+  }
+  return pos;
+}
+
+__global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ slotBase, int slotLo, int slotHi,
+                                                      const int* __restrict__ rowIds,
+                                                      const int* __restrict__ IA, const int2* __restrict__ SBL,
+                                                      const float* __restrict__ VA,
+                                                      const int* __restrict__ JB,
+                                                      const float* __restrict__ VB,
+                                                      const int* __restrict__ IC, int* __restrict__ JC,
+                                                      float* __restrict__ C, int* __restrict__ err,
+                                                      const int* __restrict__ rowFlops,
+                                                      const int2* __restrict__ meta, const int* __restrict__ mlog,
+                                                      long long logCap, int waveCap,
+                                                      unsigned long long* __restrict__ took,
+                                                      int* __restrict__ restList, int* __restrict__ restCount) {
+  constexpr int S = MW_SLOTS;
+  __shared__ __attribute__((aligned(16))) MidWaveShared sh;
+  static_assert(sizeof(MidWaveShared) <= 6 * 1024, "24+ blocks of one wave share a CU");
+  const int lane = lane_id();
+  waveCap = min(waveCap, bd_cap(S));                   // a probe always ends at an empty slot
+  sh.st.dummy[lane] = DUMMY_SLOT;
+  MidWaveRows rows;                                    // static schedule: XCD-contiguous (see xcd_range)
+  const XcdRange xh = xcd_range(slotBase[slotHi + 1] - slotBase[slotHi]);
+  const XcdRange xl = xcd_range(slotBase[slotLo + 1] - slotBase[slotLo]);
+  rows.hi = rowIds + slotBase[slotHi] + xh.lo; rows.nhi = xh.hi - xh.lo;
+  rows.lo = rowIds + slotBase[slotLo] + xl.lo; rows.nlo = xl.hi - xl.lo;
+  const int count = rows.count();
+  const int stride = xh.nb;
+  int q = xh.bi;
+  // two rows of metadata and one row of A entries are in flight ahead of the row being processed
+  MidMeta cur = load_meta_midwave(rows, q, IA, IC, rowFlops, meta, logCap, waveCap);
+  MidMeta nxt = load_meta_midwave(rows, q + stride, IA, IC, rowFlops, meta, logCap, waveCap);
+  PreA pc = load_pre(cur.m, SBL, VA, true);            // (a row of the other kernels: as = ae = 0, nothing is read)
+  int tookRows = 0;
+  while (q < count) {
+    const int qn = q + stride;
+    const MidMeta nn = load_meta_midwave(rows, qn + stride, IA, IC, rowFlops, meta, logCap, waveCap);
+    const PreA pn = load_pre(nxt.m, SBL, VA, true);
+    if (cur.lc >= 0) {                                 // wave-uniform
+      ++tookRows;
+      const int want = cur.m.x1 - cur.m.x0;
+      int* const JCrow = JC + cur.m.x0;
+      float* const Crow = C + cur.m.x0;
+      const unsigned lim = (unsigned)max(want, 0);     // every store stays inside the row's own range
+      if (want == cur.m.x2) {
+        // no repeated column: expanded, every product at its place in the walk's numbering of the row
+        for_each_product<1, 2, true>(sh.st, cur.m.as, cur.m.ae, SBL, VA, JB, VB,
+                                     [&](const auto& act, const auto& col, const auto& val, int p0) {
+          constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
+#pragma unroll
+          for (int u = 0; u < R; ++u) {
+            const unsigned o = (unsigned)(p0 + u * WAVE + lane);
+            if (act[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+          }
+        }, pc, err);
+      } else {
+        const int lc = cur.lc;
+        // four slots per logged re-hit when that fits (the clear and the sweep are what a small table saves)
+        const int size = table_size<4>(lc, WAVE, S);
+        const int shift = 32 - log2_pow2(size);
+        clear_slots(sh.tab, size, lane, WAVE);
+        wave_lds_sync();
+        {                                              // the row's log: distinct keys <= lc <= waveCap < S, or size >= 4 * lc
+          const int* const lg = mlog + cur.ls;
+          const unsigned mask = (unsigned)size - 1u;
+          for (int i = lane; i < lc; i += WAVE) {
+            const int c = lg[i];
+            const slot_t own = make_slot(c, -0.0f);
+            unsigned h = ((unsigned)c * 2654435761u) >> shift;
+            for (int probe = 0; probe < size; ++probe) {
+              const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, own);
+              if (old == EMPTY_SLOT || slot_key(old) == c) break;
+              h = (h + 1u) & mask;
+            }
+          }
+        }
+        wave_lds_sync();
+        char* const base = reinterpret_cast<char*>(sh.tab);
+        const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
+        int pos = 0;                                   // next free place of the row's range: wave-uniform, a register
+        for_each_product<1, 2, true>(sh.st, cur.m.as, cur.m.ae, SBL, VA, JB, VB,
+                                     [&](const auto& act, const auto& col, const auto& val, int) {
+          constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
+          constexpr int CH = MW_CH <= 0 || MW_CH > R ? R : MW_CH;
+#pragma unroll
+          for (int c0 = 0; c0 < R; c0 += CH) {
+            bool a_[CH]; int c_[CH]; float v_[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) {
+              const int i = c0 + u < R ? c0 + u : 0;
+              a_[u] = c0 + u < R ? act[i] : false; c_[u] = col[i]; v_[u] = val[i];
+            }
+            pos = midwave_rounds<CH>(base, dumB, size, shift, a_, c_, v_, pos, lim, JCrow, Crow, err);
+          }
+        }, pc, err);
+        wave_lds_sync();                               // the adds have landed: the sweep reads their sums
+        for (int i0 = 0; i0 < size; i0 += WAVE) {
+          const slot_t sv = sh.tab[i0 + lane];
+          const bool occ = slot_key(sv) != EMPTY_KEY;
+          const unsigned long long mk = ballot64(occ);
+          const unsigned o = (unsigned)(pos + mask_rank(mk));
+          if (occ && o < lim) { st_out(JCrow + o, slot_key(sv)); st_out(Crow + o, slot_val(sv)); }
+          pos += __popcll(mk);
+        }
+        if (lane == 0 && pos != want) atomicOr(err, ERRF_COUNT_MISMATCH);
+        wave_lds_sync();                               // the next row clears the table behind the sweep's reads
+      }
+    } else if (cur.ls) {                               // a logged row of the four-wave kernel: onto its list (at most one
+      if (lane == 0) restList[atomicAdd(restCount, 1)] = cur.m.row;   // entry per row of the bin, which the list holds)
+    }
+    cur = nxt; nxt = nn; pc = pn;
+    q = qn;
+  }
+  if (took && lane == 0 && tookRows) atomicAdd(took, (unsigned long long)tookRows);
 }
 
 // ------------------------------------------------------------------------------------------------

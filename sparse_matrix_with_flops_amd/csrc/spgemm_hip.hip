@@ -240,6 +240,12 @@ struct HostMirror {                 // one small device block + its pinned host 
   alignas(128) int fbMid[4];
   alignas(128) unsigned long long mrCursor;
   unsigned long long mrLogged[2];   // (bin 6, bin 7)
+  // rows of bin 6 the numeric launches took: k_num_midwave, k_num_middirect (test hook; written after the mirror is
+  // taken, read from the device by spgemm_hip_debug_midrow_kernels)
+  unsigned long long mdTook[2];
+  // {0, rows}: the logged rows of bin 6 that k_num_midwave leaves to k_num_middirect, read by that kernel as the "bin" of
+  // their list (the third part of spgemm_handle::midFallback)
+  alignas(128) int mwRest[2];
   alignas(128) int fbPad_;
 };
 
@@ -322,9 +328,17 @@ struct spgemm_handle {
                                      // below it every row of the bin is resident at once in either kernel, the launch lasts as long as
                                      // its slowest row, and a row with many re-hits is slower direct than hashed (web surrogate, 862
                                      // rows of 2049-4096 products with 30-50 % re-hits: 0.033 -> 0.066 ms); the tests set 1
+  bool mdWave = true;                // SPGEMM_MD_WAVE=0: bin 6 keeps k_num_middirect for every direct row (A/B runs, tests)
+  int mwMinRows = 0;                 // SPGEMM_MW_MINROWS: a bin 6 with fewer rows keeps k_num_middirect for all its direct rows.  Default:
+                                     // 32 x the CU count -- one wave per row puts 16 rows on a CU (mwPerCU), and a bin of one or two rows
+                                     // per wave lasts as long as its slowest row on ONE wave (profiles/README.md, "Mid rows: one wave per row")
+  int mwPerCU = 16;                  // SPGEMM_MW_PERCU: blocks (= waves) of k_num_midwave per CU (measured 4 / 8 / 12 / 16 / 24: 0.301 /
+                                     // 0.189 / 0.149 / 0.152 / 0.163 ms per launch on the headline matrix)
+  bool mwRan = false;                // the latest numeric launch used k_num_midwave for bin 6
   long long mrLogEnv = 0;            // SPGEMM_MRLOG: ints of the log instead of the computed size (tests run it out of space)
   int2* mrMeta = nullptr;            // workspace block, one pair per row of A
-  int* midFallback = nullptr;        // workspace block, two ints per row of A: bin 6's list, then (at cap_m) bin 7's
+  int* midFallback = nullptr;        // workspace block, three ints per row of A: bin 6's list, then (at cap_m) bin 7's, then (at
+                                     // 2 cap_m) the rows of bin 6 that k_num_midwave passes on to k_num_middirect
   int* mrLog = nullptr;
   long long mr_cap = 0;
   bool mdLogged = false;             // the pending / current product's symbolic pass logged bins 6-7
@@ -356,7 +370,7 @@ static std::array<WsBlock, 12> ws_blocks(spgemm_handle* h, size_t cap) {
            {(void**)&h->blockP, sizeof(unsigned long long) * nblk},
            {(void**)&h->bigFallback, sizeof(int) * cap},
            {(void**)&h->mrMeta, sizeof(int2) * cap},
-           {(void**)&h->midFallback, sizeof(int) * 2 * cap},
+           {(void**)&h->midFallback, sizeof(int) * 3 * cap},
            {(void**)&h->batchStart, sizeof(int) * (3 * cap + 64)},
            {(void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)}}};
 }
@@ -464,6 +478,10 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   env_int("SPGEMM_MD_CAP", 0, h->mdCap, &h->mdCap);
   h->mdMinRows = 4 * h->numCU;
   env_int("SPGEMM_MD_MINROWS", 1, 1 << 30, &h->mdMinRows);
+  { int v = 1; env_int("SPGEMM_MD_WAVE", 0, 1, &v); h->mdWave = v != 0; }
+  h->mwMinRows = 32 * h->numCU;
+  env_int("SPGEMM_MW_MINROWS", 1, 1 << 30, &h->mwMinRows);
+  env_int("SPGEMM_MW_PERCU", 1, 32, &h->mwPerCU);
   { int v = 0; env_int("SPGEMM_MRLOG", 1, 1 << 30, &v); h->mrLogEnv = v; }
   env_int("SPGEMM_PATH", 0, 2, &h->pathMode);
   env_int("SPGEMM_CHAIN_CFG", INT_MIN, INT_MAX, &h->chainCfg);   // unchecked: chain_cfg() maps anything else to 0
@@ -562,6 +580,21 @@ extern "C" int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, 
   for (int b = 0; b < 2; ++b) if (h->mdRan[b]) *logged += (long long)h->mirror.mrLogged[b];
   *reserved = h->mdLogged ? (long long)h->mirror.mrCursor : 0;
   *capacity = h->mr_cap;
+  return SPGEMM_OK;
+}
+
+// ... and which of the two direct kernels took the direct rows of 513-2048 products: counted on the device by the kernels
+// themselves, behind the host mirror, so this hook waits for the handle's stream and reads the two counters
+extern "C" int spgemm_hip_debug_midrow_kernels(spgemm_handle* h, long long* wave_rows, long long* multiwave_rows) {
+  if (!h || !wave_rows || !multiwave_rows) return fail(SPGEMM_ERR_ARG, "null argument");
+  *wave_rows = 0; *multiwave_rows = 0;
+  if (!h->mdRan[0]) return SPGEMM_OK;                  // (bin 6 ran k_num_hash alone: the counters are not this product's)
+  unsigned long long v[2] = {0ull, 0ull};
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipMemcpy(v, h->dsmall->mdTook, sizeof(v), hipMemcpyDeviceToHost));
+  *wave_rows = h->mwRan ? (long long)v[0] : 0;
+  *multiwave_rows = (long long)v[1];
   return SPGEMM_OK;
 }
 
@@ -902,21 +935,36 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
   const bool mid = h->mdLogged && h->mrLog && !pcnt && minBin <= 6;
   const bool mid6 = mid && rows(6, 7) >= h->mdMinRows, mid7 = mid && rows(7, 8) >= h->mdMinRows;
   h->mdRan[0] = mid6; h->mdRan[1] = mid7;
-  auto launch_mid = [&](int bin, int nrows, int* qd, hipStream_t st) {
+  // bin 6, rows up to waveCap re-hits: one wave per row (k_num_midwave), both layout slots in one launch, the heavy slot
+  // first.  It puts the logged rows it leaves (midwave_takes is the one rule, read by both kernels) on a list, and
+  // k_num_middirect runs over that list instead of the bin: skipping 56 000 rows of the headline matrix one dequeue of four at
+  // a time cost it 0.185 ms (profiles/README.md, "Mid rows: one wave per row")
+  const int waveCap = mid6 && h->mdWave && rows(6, 7) >= h->mwMinRows ? std::min(h->mdCap, bd_cap(MW_SLOTS)) : -1;
+  h->mwRan = waveCap >= 0;
+  auto launch_mid = [&](int bin, int nrows, int* qd, hipStream_t st, int wcap, unsigned long long* took,
+                        const int* lbp, int lbin, const int* lrows) {       // (the rows: bin `lbin` of lbp over lrows)
     with_md_cfg(h->mdCfg >= 0 ? h->mdCfg : bin == 7 ? 1 : 0, [&](auto nw, auto slots) {
       const int lds = (int)sizeof(MidDirectShared<nw, slots>);
       const int perCU = std::max(1, std::min((160 * 1024) / lds, 32 / (int)nw));
       hipLaunchKernelGGL((k_num_middirect<nw, slots>), dim3(clampi(nrows, 1, cu * perCU)), dim3(WAVE * nw), 0, st,
-                         bp, bin, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qd, (const int*)h->rowFlops,
-                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, h->mdCap);
+                         lbp, lbin, lrows, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qd, (const int*)h->rowFlops,
+                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, h->mdCap, wcap, took);
       return 0; });
   };
   if (mid7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
-    launch_mid(7, rows(7, 8), qc + 9 * 32, st);
+    launch_mid(7, rows(7, 8), qc + 9 * 32, st, -1, (unsigned long long*)nullptr, bp, 7, rowIds);
     LAUNCH_U(k_num_hash, 8, 8192, dim3(clampi(rows(7, 8), 1, cu * 2)), dim3(512), st, h->dsmall->fbMid + 2, 0,
              (const int*)(h->midFallback + h->cap_m), dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 5 * 32, h->rowFlops, (int*)nullptr); }
   if (mid6) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
-    launch_mid(6, rows(6, 7), qc + 6 * 32, st);
+    if (waveCap >= 0) {
+      hipLaunchKernelGGL(k_num_midwave, dim3(grid8(rows(6, 7), cu * h->mwPerCU)), dim3(WAVE), 0, st, h->dsmall->slotBase,
+                         SLOT_H4A, SLOT_H4B, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, (const int*)h->rowFlops,
+                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, waveCap, &h->dsmall->mdTook[0],
+                         h->midFallback + 2 * (size_t)h->cap_m, &h->dsmall->mwRest[1]);
+      launch_mid(6, rows(6, 7), qc + 6 * 32, st, waveCap, &h->dsmall->mdTook[1], h->dsmall->mwRest, 0,
+                 (const int*)(h->midFallback + 2 * (size_t)h->cap_m));
+    } else
+    launch_mid(6, rows(6, 7), qc + 6 * 32, st, waveCap, &h->dsmall->mdTook[1], bp, 6, rowIds);
     LAUNCH_U(k_num_hash, 4, 4096, dim3(clampi(rows(6, 7), 1, cu * 4)), dim3(256), st, h->dsmall->fbMid, 0,
              (const int*)h->midFallback, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 7 * 32, h->rowFlops, (int*)nullptr); }
   if (!mid7 && rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);

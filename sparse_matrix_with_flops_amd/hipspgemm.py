@@ -62,7 +62,7 @@ EXPORTS = [
     "hip_sharded_spmm_info", "hip_sharded_spmm_destroy", "hip_gpuRmclIter_sharded", "spgemm_hip_host_api_stats",
     "hip_sharded_spmm_handle", "spgemm_hip_rccl_available", "spgemm_hip_pool_trim",
     "hip_sharded_rmcl_create", "hip_sharded_rmcl_run", "hip_sharded_rmcl_continue", "hip_sharded_rmcl_result", "hip_sharded_rmcl_iter_nnz",
-    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_debug_bigrow_paths", "spgemm_hip_debug_midrow_paths", "spgemm_hip_debug_midrow_log", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
+    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_debug_bigrow_paths", "spgemm_hip_debug_midrow_paths", "spgemm_hip_debug_midrow_log", "spgemm_hip_debug_midrow_kernels", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
     "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
     "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
     "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
@@ -311,6 +311,8 @@ def lib():
         if hasattr(L, "spgemm_hip_debug_midrow_paths"):
             L.spgemm_hip_debug_midrow_paths.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
             L.spgemm_hip_debug_midrow_log.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3
+        if hasattr(L, "spgemm_hip_debug_midrow_kernels"):
+            L.spgemm_hip_debug_midrow_kernels.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 2
         L.spgemm_hip_handle_device.argtypes = [C.c_void_p]
         L.free = C.CDLL(None).free
         L.free.argtypes = [C.c_void_p]
@@ -436,13 +438,18 @@ class Handle:
 
     def midrow_paths(self):
         """test hook: rows of 513-4096 products of the latest product, how many took the direct kernel / the hash kernel of
-        their bin, the re-hit cap of the direct kernel; re-hits the direct rows logged, log ints reserved, log ints there"""
+        their bin, the re-hit cap of the direct kernel; re-hits the direct rows logged, log ints reserved, log ints there;
+        direct rows of 513-2048 products that took the wave-per-row kernel / the four-wave kernel"""
         v = [C.c_int(0) for _ in range(4)]
         w = [C.c_longlong(0) for _ in range(3)]
+        k = [C.c_longlong(0) for _ in range(2)]
         _check(lib().spgemm_hip_debug_midrow_paths(self._h, *[C.byref(x) for x in v]), "spgemm_hip_debug_midrow_paths")
         _check(lib().spgemm_hip_debug_midrow_log(self._h, *[C.byref(x) for x in w]), "spgemm_hip_debug_midrow_log")
+        if hasattr(lib(), "spgemm_hip_debug_midrow_kernels"):
+            _check(lib().spgemm_hip_debug_midrow_kernels(self._h, *[C.byref(x) for x in k]), "spgemm_hip_debug_midrow_kernels")
         return {"rows": v[0].value, "direct": v[1].value, "fallback": v[2].value, "cap": v[3].value,
-                "logged": w[0].value, "reserved": w[1].value, "capacity": w[2].value}
+                "logged": w[0].value, "reserved": w[1].value, "capacity": w[2].value,
+                "wave": k[0].value, "multiwave": k[1].value}
 
     def close(self):
         if self._h and self._own:
