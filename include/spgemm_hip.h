@@ -9,7 +9,7 @@
  *
  * Each declaration cites the reference interface it replaces (paths relative to the reference tree).
  * The reference's other value type (QValue double, FDOUBLE, nlibs/tools/macro.h:3-6) has the *_f64 twins of the SpGEMM
- * entry points and the row sort, section (5) below.
+ * entry points, the row sort and R-MCL (prune, fused step, loop), section (5) below.
  * Thread model: one caller thread per handle; calls return after the device work has completed
  * (the reference's GPU path is blocking too: nlibs/gpus/gpu_csr_kernel.cu:162).
  */
@@ -858,8 +858,9 @@ int hip_rmcl_clusters_f64(spgemm_handle* h, int m, int n, int nnz, const int* dI
  * symbolic pass and scan are shared with the float path (they read the structure only), so C's structure is the float
  * call's; the numeric kernels accumulate in double.  spgemm_stats is filled as for a float call: f64 numeric launches are
  * timed into the SPGEMM_K_NUM_* slot of their bin (SPGEMM_NKERNELS and the struct layout are unchanged).
- * Not available in double: R-MCL (hip_rmcl_*, hip_gpuRmclIter*), multi-GPU, hip_sgpuSpMM / hip_gpuFlopsClassify,
- * COO -> CSR, mixed precision (float in, double accumulate).
+ * R-MCL in double (prune, fused step, loop on one device) is declared at the end of this section.
+ * Not available in double: multi-GPU (sharded SpGEMM and sharded R-MCL), hip_sgpuSpMM / hip_gpuFlopsClassify, mixed
+ * precision (float in, double accumulate).
  * Measured on one MI355X: a double call takes 2.0x the float call on the 1 M-row power-law A*A,
  * 1.45x on the web-graph surrogate. */
 /* CSR gpuSpMMWrapper for QValue double: cusparseDcsrgemm (nlibs/gpus/cusparse_spmm.cc:73).  Never takes the opt-in
@@ -881,6 +882,29 @@ int hip_CSR_SpMM_f64(const int* IA, const int* JA, const double* A, int nnzA,
                      int** IC, int** JC, double** C, int* nnzC, int m, int k, int n);
 /* CSR::makeOrdered with double values (nlibs/CSR.cc:73-86) */
 int hip_csr_sort_rows_f64(spgemm_handle* h, int m, const int* dIC, int* dJC, double* dC);
+
+/* R-MCL with QValue double: the contracts of hip_rmcl_prune / _n, hip_rmcl_expand_prune, hip_gpuRmclIter_device and
+ * hip_gpuRmclIter above (argument checks and status codes, h == NULL = the default handle, outputs from the pool, inputs
+ * not modified, rows column-unsorted, maxIter == 0 returns a copy, a square matrix is required).  The row rule is
+ * nlibs/tools/util.cc:4-69 / nlibs/qrmcl.cc:96-117 with every operation in double: v*v, row max and row sum,
+ * thresh = 0.90*avg*(1 - 2*(max - avg)) with avg = sum / stored entries, raised to 1e-7, lowered to max; keep v*v >= thresh;
+ * kept squares divided by their sum.  hip_rmcl_prune_f64 keeps the kept entries in input order.  The fused step always
+ * runs the symbolic pass (its scratch C has nnz(C) entries); the loop packs Mt after every iteration.
+ * hip_gpuRmclIter_f64 takes host arrays, returns malloc()ed arrays and runs on one device: SPGEMM_RMCL_DEVICES is ignored. */
+int hip_rmcl_prune_f64(spgemm_handle* h, int m, const int* dIC, const int* dJC, const double* dC,
+                       int** dIN, int** dJN, double** dCN, int* nnzN);
+int hip_rmcl_prune_n_f64(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const double* dC,
+                         int** dIN, int** dJN, double** dCN, int* nnzN);
+int hip_rmcl_expand_prune_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
+                              const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
+                              int** dIN, int** dJN, double** dCN, int* nnzN);
+int hip_gpuRmclIter_device_f64(spgemm_handle* h, int maxIter, int rows, int cols,
+                               const int* dgI, const int* dgJ, const double* dgA, int gnnz,
+                               const int* dtI, const int* dtJ, const double* dtA, int tnnz,
+                               int** oI, int** oJ, double** oA, int* onnz);
+int hip_gpuRmclIter_f64(int maxIter, int rows, int cols, const int* gIA, const int* gJA, const double* gA, int gnnz,
+                        const int* tIA, const int* tJA, const double* tA, int tnnz,
+                        int** oIA, int** oJA, double** oA, int* onnz);
 
 /* device self-test of the wave/block primitives (scans, ballots); returns SPGEMM_OK or INTERNAL */
 int spgemm_hip_selftest(spgemm_handle* h);

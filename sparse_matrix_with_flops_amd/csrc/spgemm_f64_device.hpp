@@ -20,6 +20,7 @@
 // word, and the call fails with SPGEMM_ERR_INTERNAL.
 #pragma once
 #include "spgemm_device.hpp"
+#include "rmcl_f64_device.hpp"
 
 namespace smf {
 
@@ -89,14 +90,17 @@ __device__ __forceinline__ void g64_walk(G64Stage& st, int gl, int as, int ae, c
   }
 }
 
-template <int TBL, int U>
+// PRUNE (the fused R-MCL step, rmcl_f64_device.hpp): the row rule is applied to the finished row in LDS, the kept entries
+// go, normalised, to the front of the row's range and their count to pcnt[row]; a row of distinct columns is held as the
+// plain list of its products in the slots the table would have used.
+template <int TBL, int U, bool PRUNE = false>
 __global__ __launch_bounds__(256) void k_num64_g16(const int* __restrict__ binPtr, int bin, int binHi,
                                                     const int* __restrict__ rowIds,
                                                     const int* __restrict__ IA, const int2* __restrict__ SBL,
                                                     const double* __restrict__ VA, const int* __restrict__ JB,
                                                     const double* __restrict__ VB, const int* __restrict__ IC,
                                                     int* __restrict__ JC, double* __restrict__ C, int* __restrict__ err,
-                                                    const int* __restrict__ rowFlops) {
+                                                    const int* __restrict__ rowFlops, int* __restrict__ pcnt) {
   __shared__ int keys[16][TBL];
   __shared__ double vals[16][TBL];
   __shared__ G64Stage st[16];
@@ -113,6 +117,20 @@ __global__ __launch_bounds__(256) void k_num64_g16(const int* __restrict__ binPt
     // every product on a column of its own (want == products): straight to its place in the row
     const bool hashRow = live && want != rowFlops[row];
     if (ballot64(hashRow) == 0ull) {
+      if constexpr (PRUNE) {
+        const int lim = min(want, TBL);                    // (want <= 64 products <= TBL: never cut)
+        if (live) {
+          g64_walk<U>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, double v, int pos) {
+            if (active && (unsigned)pos < (unsigned)lim) { keys[g][pos] = col; vals[g][pos] = v; }
+          });
+        }
+        wave_lds_sync();
+        int nocc;
+        const int kept = prune_emit_group64<16>(keys[g], vals[g], (lim + 15) & ~15, lim, false, live, gl, JC + off, C + off, &nocc);
+        if (live && gl == 0) pcnt[row] = kept;
+        wave_lds_sync();
+        continue;
+      }
       if (live) {
         g64_walk<U>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, double v, int pos) {
           if (active && (unsigned)pos < (unsigned)want) { st_out(JC + off + pos, col); st_out(C + off + pos, v); }
@@ -134,6 +152,16 @@ __global__ __launch_bounds__(256) void k_num64_g16(const int* __restrict__ binPt
       });
     }
     wave_lds_sync();
+    if constexpr (PRUNE) {
+      int nocc;
+      const int kept = prune_emit_group64<16>(keys[g], vals[g], size, want, true, live, gl, JC + off, C + off, &nocc);
+      if (live && gl == 0) {
+        pcnt[row] = kept;
+        if (nocc != want) atomicOr(err, ERRF_COUNT_MISMATCH);
+      }
+      wave_lds_sync();
+      continue;
+    }
     int written = 0;
     for (int i0 = 0; i0 < size; i0 += 16) {
       const int k = keys[g][i0 + gl];
@@ -212,13 +240,17 @@ __device__ __forceinline__ void row64_walk(Row64Stage<NT>& st, int as, int ae, c
 
 // GLOBAL = false: rows of the bin with lmin <= L_i <= lmax, LDS table of TBL slots.
 // GLOBAL = true: the same in a table of gslots slots per block at gkeys/gvals + blockIdx.x * gslots (device memory).
-template <int NT, int TBL, bool GLOBAL>
+// PRUNE: rows that finish in one LDS pass get the R-MCL row rule in the epilogue (kept entries to the front of the row's
+// range, their count to pcnt[row]); multi-pass and device-memory rows are written in full (k_rmcl_fix_rows64 takes them).
+template <int NT, int TBL, bool GLOBAL, bool PRUNE = false>
 __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPtr, int bin, const int* __restrict__ rowIds,
                                                    const int* __restrict__ IA, const int2* __restrict__ SBL,
                                                    const double* __restrict__ VA, const int* __restrict__ JB,
                                                    const double* __restrict__ VB, const int* __restrict__ IC,
                                                    int* __restrict__ JC, double* __restrict__ C, int* __restrict__ err,
-                                                   int lmin, int lmax, int* gkeys, double* gvals, int gslots) {
+                                                   int lmin, int lmax, int* gkeys, double* gvals, int gslots,
+                                                   int* __restrict__ pcnt) {
+  __shared__ PruneShared64<PRUNE ? NT / WAVE : 1> ps;
   __shared__ int skeys[GLOBAL ? 1 : TBL];
   __shared__ double svals[GLOBAL ? 1 : TBL];
   __shared__ Row64Stage<NT> st;
@@ -253,6 +285,13 @@ __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPt
         });
       if (GLOBAL) __threadfence();                       // the block's atomics are done before any lane reads the table
       __syncthreads();
+      if constexpr (PRUNE && !GLOBAL) {
+        if (npass == 1) {                                  // block-uniform
+          prune_emit_block64<NT, (TBL + NT - 1) / NT>(keys, vals, size, want, ps, JC + off, C + off, pcnt + row, err);
+          if (tid == 0) st.cnt = want;                     // (the epilogue has checked the count itself)
+          break;
+        }
+      }
       for (int i0 = 0; i0 < size; i0 += NT) {
         const int i = i0 + tid;
         const int k = i < size ? keys[i] : EMPTY_KEY;

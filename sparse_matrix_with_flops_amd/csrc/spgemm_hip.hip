@@ -1216,7 +1216,7 @@ static void grow_midrow_log(spgemm_handle* h) {
 // length sizes them (one small kernel and a host read, only when bin 8 has rows).
 static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB,
                               const int* rowIds, const int* hostBinPtr, const int* dIC, int* dJC, double* dC,
-                              int** gbuf) {
+                              int** gbuf, int* pcnt = nullptr) {
   const int2* sbl = h->sbl;
   clear_stale_hip_error();
   const int* bp = h->dsmall->binPtr;
@@ -1224,6 +1224,8 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   const int cu = h->numCU;
   hipStream_t s = h->stream;
   auto rows = [&](int lo, int hi) { return hostBinPtr[hi] - hostBinPtr[lo]; };
+  // pcnt: the fused R-MCL step (rmcl_f64_device.hpp) -- the same launches with the row rule in their epilogues
+  auto fused = [&](auto launch) { if (pcnt) launch(std::true_type()); else launch(std::false_type()); };
   int wide[2] = {0, 0};                                // largest L_i of the rows beyond F64_PASS_MAXL, their number
   int* gkeys = nullptr;
   double* gvals = nullptr;
@@ -1252,28 +1254,42 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   if (rows(8, 9) > 0) {
     hipStream_t st = h->side[3];
     { KTimer t(h, SPGEMM_K_NUM_BIG, st);
-      hipLaunchKernelGGL((k_num64_rows<F64_BIG_THREADS, F64_LDS_TBL, false>), dim3(clampi(rows(8, 9), 1, cu)),
-                         dim3(F64_BIG_THREADS), 0, st, bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0,
-                         F64_PASS_MAXL, (int*)nullptr, (double*)nullptr, 0); }
-    if (gblocks > 0) { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);
+      fused([&](auto P) {
+        hipLaunchKernelGGL((k_num64_rows<F64_BIG_THREADS, F64_LDS_TBL, false, decltype(P)::value>), dim3(clampi(rows(8, 9), 1, cu)),
+                           dim3(F64_BIG_THREADS), 0, st, bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0,
+                           F64_PASS_MAXL, (int*)nullptr, (double*)nullptr, 0, pcnt); }); }
+    // (device-memory rows are written in full either way: no fused form)
+    if (gblocks > 0 || pcnt) { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);
+      if (gblocks > 0)
       hipLaunchKernelGGL((k_num64_rows<F64_BIG_THREADS, 1, true>), dim3(gblocks), dim3(F64_BIG_THREADS), 0, st, bp, 8,
-                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, F64_PASS_MAXL + 1, 0x7fffffff, gkeys, gvals, gslots); }
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, F64_PASS_MAXL + 1, 0x7fffffff, gkeys, gvals, gslots,
+                         (int*)nullptr);
+      // fused step: the rows that pass through LDS in pieces or through a device-memory table were written in full --
+      // the row rule in place, behind both kernels on their stream (timed with the device-memory kernel's slot)
+      if (pcnt)
+        hipLaunchKernelGGL(k_rmcl_fix_rows64, dim3(clampi(rows(8, 9), 1, cu * 4)), dim3(256), 0, st, bp, 8, 9, rowIds, dIC, dJC,
+                           dC, pcnt, F64_LDS_MAXL); }
   }
   if (rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
-    hipLaunchKernelGGL((k_num64_rows<512, 8192, false>), dim3(clampi(rows(7, 8), 1, cu)), dim3(512), 0, st, bp, 7, rowIds,
-                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+    fused([&](auto P) {
+      hipLaunchKernelGGL((k_num64_rows<512, 8192, false, decltype(P)::value>), dim3(clampi(rows(7, 8), 1, cu)), dim3(512), 0, st, bp, 7,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0, pcnt); }); }
   if (rows(6, 7) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH4, st);
-    hipLaunchKernelGGL((k_num64_rows<256, 4096, false>), dim3(clampi(rows(6, 7), 1, cu * 3)), dim3(256), 0, st, bp, 6, rowIds,
-                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+    fused([&](auto P) {
+      hipLaunchKernelGGL((k_num64_rows<256, 4096, false, decltype(P)::value>), dim3(clampi(rows(6, 7), 1, cu * 3)), dim3(256), 0, st, bp, 6,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0, pcnt); }); }
   if (rows(5, 6) > 0) { hipStream_t st = h->side[1]; KTimer t(h, SPGEMM_K_NUM_HASH1, st);
-    hipLaunchKernelGGL((k_num64_rows<64, 1024, false>), dim3(clampi(rows(5, 6), 1, cu * 12)), dim3(64), 0, st, bp, 5, rowIds,
-                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0); }
+    fused([&](auto P) {
+      hipLaunchKernelGGL((k_num64_rows<64, 1024, false, decltype(P)::value>), dim3(clampi(rows(5, 6), 1, cu * 12)), dim3(64), 0, st, bp, 5,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0, pcnt); }); }
   if (rows(4, 5) > 0) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_NUM_G16, st);
-    hipLaunchKernelGGL((k_num64_g16<128, 4>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st, bp, 4, 5, rowIds,
-                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops); }
+    fused([&](auto P) {
+      hipLaunchKernelGGL((k_num64_g16<128, 4, decltype(P)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st, bp, 4, 5,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   if (rows(1, 4) > 0) { KTimer t(h, SPGEMM_K_NUM_SMALL4);
-    hipLaunchKernelGGL((k_num64_g16<32, 1>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, s, bp, 1, 4, rowIds,
-                       dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops); }
+    fused([&](auto P) {
+      hipLaunchKernelGGL((k_num64_g16<32, 1, decltype(P)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, s, bp, 1, 4,
+                         rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   join_streams(h);
   HIPCHK(hipGetLastError());
   return SPGEMM_OK;
@@ -2303,6 +2319,236 @@ extern "C" int hip_gpuRmclIter(int maxIter, int rows, int cols, const int* gIA, 
   if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) ||
       (rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) ||
       (rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(float) * (size_t)N.nnz))) { free(hI); free(hJ); free(hA); return rc; }
+  *oIA = hI; *oJA = hJ; *oA = hA; *onnz = N.nnz;
+  return SPGEMM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// R-MCL with double values (rmcl_f64_device.hpp): prune, fused step, loop on one device.  The float path's structure with
+// two differences: the symbolic pass always runs (the f64 tables are sized from the exact L_i), so the scratch C has
+// nnz(C) entries, not one per product; and every step leaves a packed matrix (the unpacked {start, kept} layout of the
+// float loop is not carried over).
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct DevCSR64 {                                      // a packed device matrix with double values that owns its pool blocks
+  DevBuf<int> I, J; DevBuf<double> V;
+  int nnz = 0;
+  hipError_t alloc_entries(long long n) {              // (J, V) for n entries; never a zero-sized block
+    const hipError_t e = J.alloc((size_t)std::max(n, 1ll));
+    return e != hipSuccess ? e : V.alloc((size_t)std::max(n, 1ll));
+  }
+  void reset() { *this = DevCSR64(); }
+  void give(int** oI, int** oJ, double** oV, int* onnz) {
+    *oI = I.release(); *oJ = J.release(); *oV = V.release(); *onnz = nnz;
+    reset();
+  }
+};
+}  // namespace
+
+static int rmcl_prune64_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const double* dC, DevCSR64* out) {
+  out->reset();
+  if (m < 0 || !dIC) return fail(SPGEMM_ERR_ARG, "bad argument");
+  if (!h) CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  h->sym_m = -1;                                   // scan scratch and the small device block are shared with a pending phase
+  clear_stale_hip_error();
+  CHK(ws_ensure(h, m));
+  DevCSR64 N;
+  DevBuf<double> th, ks;
+  auto hipfail = [&](const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl prune (f64): %s: %s", what, hipGetErrorString(hipGetLastError())); };
+  if (N.I.alloc((size_t)m + 1) || th.alloc((size_t)std::max(m, 1)) || ks.alloc((size_t)std::max(m, 1))) return hipfail("device allocation failed");
+  hipStream_t s = h->stream;
+  if (hipMemsetAsync(&h->dsmall->nnzC64, 0, sizeof(unsigned long long), s) != hipSuccess) return hipfail("memset");
+  if (m > 0 && nnzIn < 0) {
+    int tmp = 0;
+    if (hipMemcpyAsync(&tmp, dIC + m, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return hipfail("reading nnz");
+    nnzIn = tmp;
+  }
+  const RowLanes rl = row_lanes(h, m, nnzIn);
+  if (m > 0) {
+    RMCL_ROWS(k_rmcl_stats64, rl, s, m, dIC, dC, N.I.p, th.p, ks.p);
+    if (int rc = launch_scan(h, N.I, m, &h->dsmall->nnzC64)) return drained(s, rc);
+  } else {
+    hipMemsetAsync(N.I, 0, sizeof(int), s);
+  }
+  if (hipMemcpyAsync(&h->hsmall->nnzC64, &h->dsmall->nnzC64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return drained(s, hipfail("kept-entry count"));
+  N.nnz = (int)h->hsmall->nnzC64;
+  if (N.alloc_entries(N.nnz)) return hipfail("device allocation failed");
+  if (m > 0 && N.nnz > 0) {
+    RMCL_ROWS(k_rmcl_compact64, rl, s, m, dIC, dJC, dC, N.I.p, th.p, ks.p, N.J.p, N.V.p);
+    if (hipGetLastError() != hipSuccess) return drained(s, hipfail("compaction launch"));
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return drained(s, hipfail("compaction"));
+  *out = std::move(N);
+  return SPGEMM_OK;
+}
+
+static int rmcl_prune64_abi(spgemm_handle* h, int m, long long nnz, const int* dIC, const int* dJC, const double* dC, int** dIN,
+                            int** dJN, double** dCN, int* nnzN) {
+  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
+  DevCSR64 N;
+  CHK(rmcl_prune64_impl(h, m, nnz, dIC, dJC, dC, &N));
+  N.give(dIN, dJN, dCN, nnzN);
+  return SPGEMM_OK;
+}
+
+extern "C" int hip_rmcl_prune_f64(spgemm_handle* h, int m, const int* dIC, const int* dJC, const double* dC, int** dIN,
+                                  int** dJN, double** dCN, int* nnzN) {
+  return rmcl_prune64_abi(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+}
+
+extern "C" int hip_rmcl_prune_n_f64(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const double* dC,
+                                    int** dIN, int** dJN, double** dCN, int* nnzN) {
+  if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative nnz");
+  return rmcl_prune64_abi(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+}
+
+// Give-up route (no rows, no products, or a product beyond the cap): hip_gpuSpMM_f64 + prune.
+static int rmcl_two_steps64(spgemm_handle* h, const Product<double>& p, int nnzB, DevCSR64* out) {
+  DevCSR64 C;
+  CHK(hip_gpuSpMM_f64(h, p.IA, p.JA, p.A, p.nnzA, p.IB, p.JB, p.B, nnzB, p.m, p.k, p.n, &C.I.p, &C.J.p, &C.V.p, &C.nnz));
+  return rmcl_prune64_impl(h, p.m, C.nnz, C.I, C.J, C.V, out);
+}
+
+// One R-MCL iteration in double, *out = prune(A * B), packed: shared classification, symbolic pass and scan (the int32
+// refusal and the error word are hip_gpuSpMM_f64's), a scratch C of nnz(C) entries, the f64 numeric launches with the row
+// rule in their epilogues (+ k_rmcl_fix_rows64 for the rows that do not finish in one LDS table), the scan of the kept
+// counts and k_rmcl_move64.  Arguments are checked by the callers.
+static int rmcl_expand_prune64_core(spgemm_handle* h, const Product<double>& p, int nnzB, DevCSR64* out) {
+  out->reset();
+  HIPCHK(hipSetDevice(h->device));
+  if (p.m == 0) return rmcl_two_steps64(h, p, nnzB, out);
+  CHK(ws_ensure(h, p.m));
+  hipStream_t s = h->stream;
+  const int m = p.m;
+  DevCSR64 C;                                          // the scratch product: row starts of the full rows, nnz(C) slots
+  DevBuf<int> cnt;                                     // kept entries per row, then their scan = the result's row pointer
+  if (C.I.alloc((size_t)m + 1) || cnt.alloc((size_t)m + 1)) return rmcl_hipfail("device allocation failed");
+  int nnzC = 0;
+  int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, m, p.k, p.n, nullptr, C.I, &nnzC, false);
+  h->sym_m = -1;                                       // the phase is finished here, not by hip_spgemm_numeric_f64
+  if (rc) return drained(s, rc);
+  const unsigned long long P = h->mirror.totalP;
+  unsigned long long maxP = 1ull << 30;                // the float step's cap and its test hook
+  if (const char* e = getenv("SPGEMM_RMCL_MAXP")) maxP = std::min<unsigned long long>(maxP, strtoull(e, nullptr, 10));
+  if (P == 0 || P > maxP) {
+    C.reset(); cnt.reset();                            // (symbolic_phase waited for the stream)
+    return rmcl_two_steps64(h, p, nnzB, out);
+  }
+  if (hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return drained(s, rmcl_hipfail("memset"));
+  if (C.alloc_entries(nnzC)) return drained(s, rmcl_hipfail("device allocation of the scratch product failed"));
+  int* scratch[2] = {nullptr, nullptr};                // the numeric launch's probe words and device-memory tables
+  auto done = [&](int r) { r = drained(s, r); pool().release(scratch[0]); pool().release(scratch[1]); return r; };
+  hipEventRecord(h->ev[4], s);
+  if (nnzC > 0 && (rc = launch_numeric_f64(h, p.IA, p.A, p.JB, p.B, h->cur_rowIds, h->mirror.binPtr, C.I, C.J, C.V, scratch, cnt)))
+    return done(rc);
+  hipEventRecord(h->ev[5], s);
+  if ((rc = launch_scan(h, cnt, m, &h->dsmall->kept64))) return done(rc);
+  if ((rc = read_mirror(h, "rmcl expand+prune (f64)"))) return done(rc);
+  done(SPGEMM_OK);                                     // (read_mirror waited for the stream)
+  spgemm_stats& st = h->stats;
+  hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
+  st.ms_total += st.ms_numeric;
+  collect_kernel_times(h, false);
+  const int kept = (int)h->mirror.kept64;              // <= nnz(C) < 2^31
+  DevCSR64 N;
+  if (N.alloc_entries(kept)) return rmcl_hipfail("device allocation failed");
+  if (kept > 0) {
+    const RowLanes rl = row_lanes(h, m, kept);
+    RMCL_ROWS(k_rmcl_move64, rl, s, m, C.I.p, cnt.p, C.J.p, C.V.p, N.J.p, N.V.p);
+    if (hipGetLastError() != hipSuccess) return drained(s, rmcl_hipfail("move launch"));
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return drained(s, rmcl_hipfail("move"));
+  N.I = std::move(cnt);
+  N.nnz = kept;
+  *out = std::move(N);
+  return SPGEMM_OK;
+}
+
+extern "C" int hip_rmcl_expand_prune_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
+                                         const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
+                                         int** dIN, int** dJN, double** dCN, int* nnzN) {
+  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
+  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
+  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
+  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
+  if (!h) CHK(default_handle(&h));
+  DevCSR64 N;
+  CHK(rmcl_expand_prune64_core(h, {dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n}, nnzB, &N));
+  N.give(dIN, dJN, dCN, nnzN);
+  return SPGEMM_OK;
+}
+
+// gpuRmclIter on device arrays with QValue double: maxIter iterations Mt <- prune(Mgt * Mt) from (tI, tJ, tA), which are
+// left alone; the result is a packed device CSR of the pool.  Mt is packed after every iteration.
+extern "C" int hip_gpuRmclIter_device_f64(spgemm_handle* h, int maxIter, int rows, int cols, const int* dgI, const int* dgJ,
+                                          const double* dgA, int gnnz, const int* dtI, const int* dtJ, const double* dtA,
+                                          int tnnz, int** oI, int** oJ, double** oA, int* onnz) {
+  if (!oI || !oJ || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *oI = nullptr; *oJ = nullptr; *oA = nullptr; *onnz = 0;
+  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
+  CHK(check_common(dgI, dgJ, dgA, gnnz, "Mgt"));
+  CHK(check_common(dtI, dtJ, dtA, tnnz, "Mt"));
+  if (!h) CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  DevCSR64 cur;                                        // the current Mt once the loop owns one; until then the caller's
+  for (int it = 0; it < maxIter; ++it) {
+    DevCSR64 next;
+    const Product<double> p{dgI, dgJ, dgA, gnnz, it ? cur.I.p : dtI, it ? cur.J.p : dtJ, it ? cur.V.p : dtA, rows, cols, cols};
+    if (int rc = rmcl_expand_prune64_core(h, p, it ? cur.nnz : tnnz, &next)) return drained(s, rc);
+    cur = std::move(next);                             // (every step waits for its kernels: the old Mt is idle)
+  }
+  if (maxIter == 0) {                                  // a copy of Mt
+    if (cur.I.alloc((size_t)rows + 1) || cur.alloc_entries(tnnz)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
+    if (hipMemcpyAsync(cur.I, dtI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        (tnnz > 0 && (hipMemcpyAsync(cur.J, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                      hipMemcpyAsync(cur.V, dtA, sizeof(double) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess)) ||
+        hipStreamSynchronize(s) != hipSuccess)
+      return drained(s, fail(SPGEMM_ERR_HIP, "copy of Mt"));
+    cur.nnz = tnnz;
+  }
+  cur.give(oI, oJ, oA, onnz);
+  return SPGEMM_OK;
+}
+
+// host arrays in, malloc()ed host arrays out; one device (the default handle's), whatever SPGEMM_RMCL_DEVICES says
+extern "C" int hip_gpuRmclIter_f64(int maxIter, int rows, int cols, const int* gIA, const int* gJA, const double* gA, int gnnz,
+                                   const int* tIA, const int* tJA, const double* tA, int tnnz, int** oIA, int** oJA,
+                                   double** oA, int* onnz) {
+  if (!oIA || !oJA || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *oIA = nullptr; *oJA = nullptr; *oA = nullptr; *onnz = 0;
+  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
+  CHK(check_common(gIA, gJA, gA, gnnz, "Mgt"));
+  CHK(check_common(tIA, tJA, tA, tnnz, "Mt"));
+  CHK(validate_host_csr(gIA, gJA, rows, cols, gnnz, "Mgt"));
+  CHK(validate_host_csr(tIA, tJA, rows, cols, tnnz, "Mt"));
+  spgemm_handle* h = nullptr;
+  CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  DevCSR64 Mg, Mt, N;
+  auto up = [](auto& buf, const auto* src, size_t n) {
+    const int rc = spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * std::max<size_t>(n, 1));
+    return rc || n == 0 ? rc : spgemm_hip_memcpy_h2d(buf.p, src, sizeof(*src) * n);
+  };
+  int rc;
+  if ((rc = up(Mg.I, gIA, (size_t)rows + 1)) || (rc = up(Mg.J, gJA, (size_t)gnnz)) || (rc = up(Mg.V, gA, (size_t)gnnz)) ||
+      (rc = up(Mt.I, tIA, (size_t)rows + 1)) || (rc = up(Mt.J, tJA, (size_t)tnnz)) || (rc = up(Mt.V, tA, (size_t)tnnz)))
+    return rc;
+  CHK(hip_gpuRmclIter_device_f64(h, maxIter, rows, cols, Mg.I, Mg.J, Mg.V, gnnz, Mt.I, Mt.J, Mt.V, tnnz, &N.I.p, &N.J.p, &N.V.p, &N.nnz));
+  int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
+  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(N.nnz, 1));
+  double* hA = (double*)malloc(sizeof(double) * (size_t)std::max(N.nnz, 1));
+  if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return fail(SPGEMM_ERR_NOMEM, "host malloc failed"); }
+  if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) ||
+      (N.nnz > 0 && ((rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) ||
+                     (rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(double) * (size_t)N.nnz))))) { free(hI); free(hJ); free(hA); return rc; }
   *oIA = hI; *oJA = hJ; *oA = hA; *onnz = N.nnz;
   return SPGEMM_OK;
 }

@@ -79,6 +79,8 @@ EXPORTS = [
     "hip_dense_gemm", "hip_dense_gemm_f64",
     "hip_rmcl_attractors", "hip_rmcl_attractors_f64", "hip_rmcl_attractor_lanes", "hip_csr_connected_components",
     "hip_labels_to_clusters", "hip_rmcl_clusters", "hip_rmcl_clusters_f64",
+    "hip_rmcl_prune_f64", "hip_rmcl_prune_n_f64", "hip_rmcl_expand_prune_f64", "hip_gpuRmclIter_device_f64",
+    "hip_gpuRmclIter_f64",
 ]
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -205,6 +207,12 @@ def lib():
                                             C.POINTER(BinReport)]
         L.hip_gpuRmclIter.argtypes = [C.c_int, C.c_int, C.c_int, _I, _I, _F, C.c_int, _I, _I, _F, C.c_int,
                                       C.POINTER(_I), C.POINTER(_I), C.POINTER(_F), _I]
+        L.hip_rmcl_prune_f64.argtypes = L.hip_rmcl_prune.argtypes
+        L.hip_rmcl_prune_n_f64.argtypes = L.hip_rmcl_prune_n.argtypes
+        L.hip_rmcl_expand_prune_f64.argtypes = L.hip_rmcl_expand_prune.argtypes
+        L.hip_gpuRmclIter_device_f64.argtypes = L.hip_gpuRmclIter_device.argtypes
+        L.hip_gpuRmclIter_f64.argtypes = [C.c_int, C.c_int, C.c_int, _I, _I, _D, C.c_int, _I, _I, _D, C.c_int,
+                                          C.POINTER(_I), C.POINTER(_I), C.POINTER(_D), _I]
         L.hip_csr_sort_rows.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.hip_CSR_SpMM_f64.argtypes = [_I, _I, _D, C.c_int, _I, _I, _D, C.c_int, C.POINTER(_I), C.POINTER(_I),
                                        C.POINTER(_D), _I, C.c_int, C.c_int, C.c_int]
@@ -813,25 +821,43 @@ def device_synchronize():
     _check(lib().spgemm_hip_device_synchronize(), "spgemm_hip_device_synchronize")
 
 
+def _rmcl_prune(dtype, handle, m, IC, JC, CV, nnz):
+    out = _CsrOut()
+    if nnz is None:
+        _call("hip_rmcl_prune", dtype, _hp(handle), int(m), *_ptrs(IC, JC, CV), *out.refs())
+    else:
+        _call("hip_rmcl_prune_n", dtype, _hp(handle), int(m), int(nnz), *_ptrs(IC, JC, CV), *out.refs())
+    return out.values()
+
+
 def rmcl_prune_raw(handle, m, IC, JC, CV, nnz=None):
     """hip_rmcl_prune on raw device pointers: inflate/prune/normalise the rows of C, compacted into new pool arrays.
     nnz (optional): nnz(C) when the caller knows it (hip_rmcl_prune_n: no device read for it).
     Returns (IN, JN, CN, nnzN); release the three with dev_free."""
+    return _rmcl_prune(np.float32, handle, m, IC, JC, CV, nnz)
+
+
+def rmcl_prune_raw_f64(handle, m, IC, JC, CV, nnz=None):
+    """rmcl_prune_raw with float64 values (hip_rmcl_prune_f64 / hip_rmcl_prune_n_f64)."""
+    return _rmcl_prune(np.float64, handle, m, IC, JC, CV, nnz)
+
+
+def _rmcl_expand_prune(dtype, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
     out = _CsrOut()
-    if nnz is None:
-        _check(lib().hip_rmcl_prune(_hp(handle), int(m), *_ptrs(IC, JC, CV), *out.refs()), "hip_rmcl_prune")
-    else:
-        _check(lib().hip_rmcl_prune_n(_hp(handle), int(m), int(nnz), *_ptrs(IC, JC, CV), *out.refs()), "hip_rmcl_prune_n")
+    _call("hip_rmcl_expand_prune", dtype, _hp(handle), *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB),
+          int(m), int(k), int(n), *out.refs())
     return out.values()
 
 
 def rmcl_expand_prune_raw(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
     """hip_rmcl_expand_prune on raw device pointers: prune(A*B) of one R-MCL iteration without materialising the product.
     Returns (IN, JN, CN, nnzN) in pool arrays; release the three with dev_free."""
-    out = _CsrOut()
-    _check(lib().hip_rmcl_expand_prune(_hp(handle), *_ptrs(IA, JA, VA), int(nnzA), *_ptrs(IB, JB, VB), int(nnzB),
-                                       int(m), int(k), int(n), *out.refs()), "hip_rmcl_expand_prune")
-    return out.values()
+    return _rmcl_expand_prune(np.float32, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n)
+
+
+def rmcl_expand_prune_raw_f64(handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n):
+    """rmcl_expand_prune_raw with float64 values (hip_rmcl_expand_prune_f64)."""
+    return _rmcl_expand_prune(np.float64, handle, IA, JA, VA, nnzA, IB, JB, VB, nnzB, m, k, n)
 
 
 def pool_trim(device=0):
@@ -1053,35 +1079,50 @@ def scudaSpMM(hA, hB, handle=None):
             dB.deviceDispose()
 
 
-def rmcl_iter_device_raw(handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz):
-    """hip_gpuRmclIter_device on raw device pointers: maxIter iterations Mt <- prune(Mgt * Mt) without packing Mt between
-    them.  Returns (I, J, V, nnz) of the final Mt in pool arrays; release the three with dev_free."""
+def _rmcl_iter_device(dtype, handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz):
     out = _CsrOut()
-    _check(lib().hip_gpuRmclIter_device(_hp(handle), int(maxIter), int(rows), int(cols), *_ptrs(gI, gJ, gV), int(gnnz),
-                                        *_ptrs(tI, tJ, tV), int(tnnz), *out.refs()), "hip_gpuRmclIter_device")
+    _call("hip_gpuRmclIter_device", dtype, _hp(handle), int(maxIter), int(rows), int(cols), *_ptrs(gI, gJ, gV), int(gnnz),
+          *_ptrs(tI, tJ, tV), int(tnnz), *out.refs())
     return out.values()
 
 
+def rmcl_iter_device_raw(handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz):
+    """hip_gpuRmclIter_device on raw device pointers: maxIter iterations Mt <- prune(Mgt * Mt) without packing Mt between
+    them.  Returns (I, J, V, nnz) of the final Mt in pool arrays; release the three with dev_free."""
+    return _rmcl_iter_device(np.float32, handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz)
+
+
+def rmcl_iter_device_raw_f64(handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz):
+    """rmcl_iter_device_raw with float64 values (hip_gpuRmclIter_device_f64: Mt is packed after every iteration)."""
+    return _rmcl_iter_device(np.float64, handle, maxIter, rows, cols, gI, gJ, gV, gnnz, tI, tJ, tV, tnnz)
+
+
 def gpuRmclIter_device(maxIter, Mgt, Mt, handle=None):
-    """hip_gpuRmclIter_device on device CSRs: returns the new Mt as a device CSR (the inputs are left alone)."""
+    """hip_gpuRmclIter_device (float32) / _f64 (float64) on device CSRs: returns the new Mt as a device CSR of the
+    operands' value type (the inputs are left alone); mixed value types raise before any device work."""
     assert Mgt.on_device and Mt.on_device
-    i_, j_, c_, n_ = rmcl_iter_device_raw(handle, maxIter, Mgt.rows, Mgt.cols, Mgt.rowPtr, Mgt.colInd, Mgt.values, Mgt.nnz,
-                                          Mt.rowPtr, Mt.colInd, Mt.values, Mt.nnz)
-    return CSR(c_, j_, i_, Mt.rows, Mt.cols, n_, on_device=True)
+    dtype = _common_dtype(Mgt, Mt)
+    i_, j_, c_, n_ = _rmcl_iter_device(dtype, handle, maxIter, Mgt.rows, Mgt.cols, Mgt.rowPtr, Mgt.colInd, Mgt.values, Mgt.nnz,
+                                       Mt.rowPtr, Mt.colInd, Mt.values, Mt.nnz)
+    return CSR(c_, j_, i_, Mt.rows, Mt.cols, n_, on_device=True, dtype=dtype)
 
 
 def gpuRmclIter(maxIter, Mgt, Mt):
-    """void gpuRmclIter(const int maxIter, const CSR Mgt, CSR& Mt): returns the new Mt (host CSR)."""
+    """void gpuRmclIter(const int maxIter, const CSR Mgt, CSR& Mt): returns the new Mt (host CSR).  float64 operands go to
+    hip_gpuRmclIter_f64 (one device); mixed value types raise before any device work."""
     assert not Mgt.on_device and not Mt.on_device
     L = lib()
-    oi, oj, ov, on = _I(), _I(), _F(), C.c_int(0)
-    rc = L.hip_gpuRmclIter(int(maxIter), Mgt.rows, Mgt.cols, Mgt.rowPtr.ctypes.data_as(_I), Mgt.colInd.ctypes.data_as(_I),
-                           Mgt.values.ctypes.data_as(_F), Mgt.nnz, Mt.rowPtr.ctypes.data_as(_I),
-                           Mt.colInd.ctypes.data_as(_I), Mt.values.ctypes.data_as(_F), Mt.nnz,
-                           C.byref(oi), C.byref(oj), C.byref(ov), C.byref(on))
-    _check(rc, "hip_gpuRmclIter")
-    rp, ci, v = _take_malloced(L, oi, oj, ov, Mt.rows, on.value)
-    return CSR(v, ci, rp, Mt.rows, Mt.cols, on.value)
+    dtype = _common_dtype(Mgt, Mt)
+    _V = _D if dtype == np.float64 else _F
+    fn, name = _typed("hip_gpuRmclIter", dtype)
+    oi, oj, ov, on = _I(), _I(), _V(), C.c_int(0)
+    rc = fn(int(maxIter), Mgt.rows, Mgt.cols, Mgt.rowPtr.ctypes.data_as(_I), Mgt.colInd.ctypes.data_as(_I),
+            Mgt.values.ctypes.data_as(_V), Mgt.nnz, Mt.rowPtr.ctypes.data_as(_I),
+            Mt.colInd.ctypes.data_as(_I), Mt.values.ctypes.data_as(_V), Mt.nnz,
+            C.byref(oi), C.byref(oj), C.byref(ov), C.byref(on))
+    _check(rc, name)
+    rp, ci, v = _take_malloced(L, oi, oj, ov, Mt.rows, on.value, dtype)
+    return CSR(v, ci, rp, Mt.rows, Mt.cols, on.value, dtype=dtype)
 
 
 # ---------------------------------------------------------------------------------------------
