@@ -852,6 +852,74 @@ int hip_rmcl_clusters    (spgemm_handle* h, int m, int n, int nnz, const int* dI
 int hip_rmcl_clusters_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA, int* k,
                           int** dCluster, int** dClusterPtr, int** dMembers);
 
+/* ---- sparse add and the symmetrisation of a directed graph --------------------------------------------------------------
+ * (R-)MCL is defined on undirected graphs; the reference's loader only transposes (readSNAPFile(isTrans), nlibs/COO.h:19).
+ * These calls make a directed graph undirected on the device, in front of hip_coo_to_csr's rmclInit flags and
+ * hip_gpuRmclIter_device.  Every entry point has a _f64 twin.  All arrays are device pointers; array outputs handed out
+ * as int** / float** come from the library pool (release with spgemm_hip_free); h == NULL = the default handle; a call
+ * returns after its device work has completed.  Argument checks (a null output pointer, a negative size, nnz > 0 with
+ * null arrays, a NaN alpha / beta / exponent, an unknown mode -> SPGEMM_ERR_ARG) run before any device is touched.  Every
+ * value that becomes an address (rowPtr, a column that indexes a scale or a count) is validated by a read-only pass that
+ * completes before it is used: bad input -> SPGEMM_ERR_INPUT with a message, outputs NULL, the handle stays usable.
+ *
+ * hip_csr_add: C = alpha*A + beta*B.  A and B are m x n with every row strictly ascending by column (what hip_coo_to_csr
+ * with SPGEMM_COO_DEDUPE, hip_csr_transpose and hip_csr_sort_rows produce; the contract of hip_csr_diff), checked in the
+ * pass itself: an unsorted row, a repeated column or a column outside [0,n) -> SPGEMM_ERR_INPUT.  C holds the union of
+ * the two patterns, rows strictly ascending; an entry whose sum is zero stays (the structure depends on the patterns
+ * only).  alpha and beta are converted once to the value type V; values are computed with one rounding per operation
+ * (no fused multiply-add): V(alpha)*a + V(beta)*b on a common column, V(alpha)*a / V(beta)*b on a column of one operand.
+ * No floating-point atomic: two calls return the same bits.  nnz(C) is totalled in 64 bits; above INT_MAX ->
+ * SPGEMM_ERR_OVERFLOW.  m == 0 and two empty operands are valid. */
+int hip_csr_add(spgemm_handle* h, int m, int n,
+                double alpha, const int* dIA, const int* dJA, const float* dA, int nnzA,
+                double beta, const int* dIB, const int* dJB, const float* dB, int nnzB,
+                int** dIC, int** dJC, float** dC, int* nnzC);
+int hip_csr_add_f64(spgemm_handle* h, int m, int n,
+                    double alpha, const int* dIA, const int* dJA, const double* dA, int nnzA,
+                    double beta, const int* dIB, const int* dJB, const double* dB, int nnzB,
+                    int** dIC, int** dJC, double** dC, int* nnzC);
+
+/* dOut[j] = (dRowScale[r] * dA[j]) * dColScale[dJA[j]] for entry j of row r: the row factor first, then the column
+ * factor.  Either scale may be NULL (= 1, that multiplication is not done).  dOut (the caller's V[nnz]) may be dA.  The
+ * structure is not touched.  With a dColScale the columns are validated (they index it): outside [0,n) ->
+ * SPGEMM_ERR_INPUT, dOut untouched. */
+int hip_csr_scale(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                  const float* dRowScale, const float* dColScale, float* dOut);
+int hip_csr_scale_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                      const double* dRowScale, const double* dColScale, double* dOut);
+
+/* dCount[c] (the caller's int[n]) = the number of entries with column c: the in-degree (the out-degree is the row
+ * length).  Integer atomics: the same on every call.  A column outside [0,n) -> SPGEMM_ERR_INPUT, dCount untouched. */
+int hip_csr_col_counts(spgemm_handle* h, int n, int nnz, const int* dJA, int* dCount);
+
+/* dOut[i] = V(pow((double)dCount[i], -exponent)), and 0 where the count is 0 (or negative).  A count of 1 gives 1.  Not
+ * promised bit-equal to a host pow. */
+int hip_degree_factors(spgemm_handle* h, int len, const int* dCount, double exponent, float* dOut);
+int hip_degree_factors_f64(spgemm_handle* h, int len, const int* dCount, double exponent, double* dOut);
+
+/* S = a symmetric matrix built from the square m x m A, whose rows must be strictly ascending by column (checked:
+ * SPGEMM_ERR_INPUT otherwise).  S has strictly ascending rows and a symmetric pattern.
+ *   SPGEMM_SYM_SUM                A + A^T: hip_csr_transpose, then hip_csr_add(1, A, 1, A^T).  The values are symmetric bit
+ *                                 for bit; a diagonal entry is doubled, an edge stored in both directions is summed.
+ *   SPGEMM_SYM_BIBLIOMETRIC       A*A^T + A^T*A: the transpose, two hip_gpuSpMM, hip_csr_sort_rows on both products, the add.
+ *   SPGEMM_SYM_DEGREE_DISCOUNTED  Do^-alpha A Di^-beta A^T Do^-alpha + Di^-beta A^T Do^-alpha A Di^-beta with Do / Di the
+ *                                 diagonal matrices of the out- / in-degree COUNTS (alpha = beta = 0.5 is the published
+ *                                 default), computed as Y*Y^T + Z^T*Z with Y = Do^-alpha A Di^(-beta/2) and
+ *                                 Z = Do^(-alpha/2) A Di^-beta through hip_csr_col_counts, hip_degree_factors and
+ *                                 hip_csr_scale.
+ * alpha and beta are read by SPGEMM_SYM_DEGREE_DISCOUNTED only (a NaN there -> SPGEMM_ERR_ARG).  Temporaries go back to the
+ * pool when the call ends.  The two product modes densify hub-heavy graphs: a node with d in-links makes d*d entries of
+ * A^T*A.  The size of S is the caller's concern; the int32 refusal of the product (SPGEMM_ERR_OVERFLOW) applies. */
+#define SPGEMM_SYM_SUM               0
+#define SPGEMM_SYM_BIBLIOMETRIC      1
+#define SPGEMM_SYM_DEGREE_DISCOUNTED 2
+int hip_csr_symmetrize(spgemm_handle* h, int mode, double alpha, double beta, int m,
+                       const int* dIA, const int* dJA, const float* dA, int nnz,
+                       int** dIS, int** dJS, float** dS, int* nnzS);
+int hip_csr_symmetrize_f64(spgemm_handle* h, int mode, double alpha, double beta, int m,
+                           const int* dIA, const int* dJA, const double* dA, int nnz,
+                           int** dIS, int** dJS, double** dS, int* nnzS);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

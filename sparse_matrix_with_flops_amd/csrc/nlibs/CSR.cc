@@ -418,6 +418,31 @@ std::vector<int> gpuConnectedComponents(const CSR& dM) {
   return label;
 }
 
+CSR gpuAddWrapper(const CSR& dA, const CSR& dB, QValue alpha, QValue beta) {
+  if (dA.rows != dB.rows || dA.cols != dB.cols) {
+    printf("gpuAddWrapper: A is %d x %d, B is %d x %d\n", dA.rows, dA.cols, dB.rows, dB.cols);
+    exit(EXIT_FAILURE);
+  }
+  CSR dC;
+  hip_or_die(hip_csr_add(NULL, dA.rows, dA.cols, alpha, dA.rowPtr, dA.colInd, dA.values, dA.nnz, beta, dB.rowPtr, dB.colInd,
+                         dB.values, dB.nnz, &dC.rowPtr, &dC.colInd, &dC.values, &dC.nnz), "gpuAddWrapper");
+  dC.rows = dA.rows;
+  dC.cols = dA.cols;
+  return dC;
+}
+
+CSR gpuSymmetrize(const CSR& dA, int mode, QValue alpha, QValue beta) {
+  if (dA.rows != dA.cols) {
+    printf("gpuSymmetrize: the matrix is %d x %d, not square\n", dA.rows, dA.cols);
+    exit(EXIT_FAILURE);
+  }
+  CSR dS;
+  hip_or_die(hip_csr_symmetrize(NULL, mode, alpha, beta, dA.rows, dA.rowPtr, dA.colInd, dA.values, dA.nnz, &dS.rowPtr,
+                                &dS.colInd, &dS.values, &dS.nnz), "gpuSymmetrize");
+  dS.rows = dS.cols = dA.rows;
+  return dS;
+}
+
 std::vector<int> CSR::nnzStats() const {
   std::vector<int> stats(SPGEMM_NNZ_STATS_LEN, 0);
   for (int r = 0; r < rows; ++r) {

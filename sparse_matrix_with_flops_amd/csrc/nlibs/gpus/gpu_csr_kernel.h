@@ -38,6 +38,14 @@ void gpuWriteCSRWrapper(const CSR dA, const char* path, int fmt, int header);
 // gpuConnectedComponents: per vertex the smallest vertex id of its weakly connected component (pattern of a square dM).
 std::vector<int> gpuRmclClusters(const CSR& dMt, int* k);
 std::vector<int> gpuConnectedComponents(const CSR& dM);
+// sparse add and the symmetrisation of a directed graph in front of R-MCL (no counterpart in the reference, whose loader only
+// transposes: nlibs/COO.h:19; include/spgemm_hip.h "sparse add and the symmetrisation of a directed graph").  DEVICE CSRs
+// with strictly ascending rows in, a DEVICE CSR out.
+// gpuAddWrapper: alpha * dA + beta * dB, the union of the two patterns.
+// gpuSymmetrize: mode SPGEMM_SYM_SUM (A + A^T), SPGEMM_SYM_BIBLIOMETRIC (A A^T + A^T A) or SPGEMM_SYM_DEGREE_DISCOUNTED
+// (alpha / beta: the exponents of the out- / in-degree, read by that mode only).
+CSR gpuAddWrapper(const CSR& dA, const CSR& dB, QValue alpha = 1, QValue beta = 1);
+CSR gpuSymmetrize(const CSR& dA, int mode, QValue alpha = 0.5, QValue beta = 0.5);
 
 // bool resultsComparison(CSR& hC, CSR& rC, const vector<int>& hv, const int* hqueue) (mindex2-cuda/nGpuSpMM.cc:138-240):
 // hC (result under test) against rC (reference result), whole matrix first, then bin by bin; prints one line per bin

@@ -2675,7 +2675,12 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // ------------------------------------------------------------------------------------------------
 #include "clusters_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the ten headers above
+// ------------------------------------------------------------------------------------------------
+// sparse add, diagonal scaling, degree factors and the symmetrisations of a directed graph
+// ------------------------------------------------------------------------------------------------
+#include "symmetrize_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the eleven headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

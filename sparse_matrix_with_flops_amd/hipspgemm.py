@@ -23,6 +23,8 @@ Mirrors (reference file:line):
                               CSR::output (the text)           nlibs/CSR.h:109-168   (formatted on the device; the matrix's dtype)
   rmcl_attractors(dMt) / connected_components(dM) / rmcl_clusters(dMt) -> Clusters
                               (none: the reference stops at Mt, nlibs/qrmcl.cc:136-164; semantics: tests/clusters_ref.py)
+  CSR.add(B, alpha, beta) / CSR.symmetrize(mode, alpha, beta)
+                              (none: the reference's loader only transposes, nlibs/COO.h:19; semantics: tests/symmetrize_ref.py)
 
 Values are float32 (QValue float, the reference's default) or float64 (its FDOUBLE build, nlibs/tools/macro.h:3-6): a CSR
 carries its dtype (CSR.from_arrays(..., dtype=np.float64)) and gpuSpMMWrapper / CSR.hip_spmm / sort_rows_device call the
@@ -81,7 +83,10 @@ EXPORTS = [
     "hip_labels_to_clusters", "hip_rmcl_clusters", "hip_rmcl_clusters_f64",
     "hip_rmcl_prune_f64", "hip_rmcl_prune_n_f64", "hip_rmcl_expand_prune_f64", "hip_gpuRmclIter_device_f64",
     "hip_gpuRmclIter_f64",
+    "hip_csr_add", "hip_csr_add_f64", "hip_csr_scale", "hip_csr_scale_f64", "hip_csr_col_counts",
+    "hip_degree_factors", "hip_degree_factors_f64", "hip_csr_symmetrize", "hip_csr_symmetrize_f64",
 ]
+SYM_SUM, SYM_BIBLIOMETRIC, SYM_DEGREE_DISCOUNTED = 0, 1, 2
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
 DENSE_KEEP_REFERENCE, DENSE_KEEP_ABS = 0, 1
@@ -287,6 +292,17 @@ def lib():
         L.hip_rmcl_clusters.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _I] + \
             [C.POINTER(C.c_void_p)] * 3
         L.hip_rmcl_clusters_f64.argtypes = L.hip_rmcl_clusters.argtypes
+        L.hip_csr_add.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_double] + dev_in + [C.c_double] + dev_in + \
+            [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_csr_add_f64.argtypes = L.hip_csr_add.argtypes
+        L.hip_csr_scale.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.hip_csr_scale_f64.argtypes = L.hip_csr_scale.argtypes
+        L.hip_csr_col_counts.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hip_degree_factors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p]
+        L.hip_degree_factors_f64.argtypes = L.hip_degree_factors.argtypes
+        L.hip_csr_symmetrize.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int] + dev_in + \
+            [C.POINTER(C.c_void_p)] * 3 + [_I]
+        L.hip_csr_symmetrize_f64.argtypes = L.hip_csr_symmetrize.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -621,6 +637,37 @@ class CSR:
         def run(d):
             it, jt, vt = _csr_transpose(dt, handle, d.rows, d.cols, d.nnz, d.rowPtr, d.colInd, d.values)
             return CSR(vt, jt, it, d.cols, d.rows, d.nnz, True, dtype=d.dtype)
+        return self._on_device(run)
+
+    # -- sparse add and symmetrisation (include/spgemm_hip.h "sparse add and the symmetrisation of a directed graph");
+    #    rows of the operands must be strictly ascending by column (makeOrdered / sort_rows_device) -----------------
+    def add(self, B, alpha=1.0, beta=1.0, handle=None):
+        """alpha * self + beta * B (hip_csr_add): the union of the two patterns, rows ascending, zero sums kept.  A host
+        B is uploaded for the call."""
+        if (self.rows, self.cols) != (B.rows, B.cols):
+            raise SpgemmError(f"shape mismatch: A is {self.rows}x{self.cols}, B is {B.rows}x{B.cols}")
+        dt = _common_dtype(self, B)
+
+        def run(d):
+            b = B if B.on_device else (d if B is self else B.toGpuCSR())
+            try:
+                ic, jc, vc, nnz = csr_add_raw(handle, d.rows, d.cols, alpha, d.rowPtr, d.colInd, d.values, d.nnz, beta,
+                                              b.rowPtr, b.colInd, b.values, b.nnz, dtype=dt)
+            finally:
+                if b is not B and b is not d:
+                    b.deviceDispose()
+            return CSR(vc, jc, ic, d.rows, d.cols, nnz, True, dtype=d.dtype)
+        return self._on_device(run)
+
+    def symmetrize(self, mode=SYM_SUM, alpha=0.5, beta=0.5, handle=None):
+        """hip_csr_symmetrize of a square matrix: SYM_SUM (A + A^T), SYM_BIBLIOMETRIC (A A^T + A^T A) or
+        SYM_DEGREE_DISCOUNTED (alpha / beta: the exponents of the out- / in-degree, read by that mode only)."""
+        _need_square(self, "symmetrize")
+        dt = _value_dtype(self.dtype)
+
+        def run(d):
+            i, j, v, nnz = csr_symmetrize_raw(handle, mode, alpha, beta, d.rows, d.rowPtr, d.colInd, d.values, d.nnz, dtype=dt)
+            return CSR(v, j, i, d.rows, d.cols, nnz, True, dtype=d.dtype)
         return self._on_device(run)
 
     def rowDescendingOrderPermutation(self, handle=None):
@@ -2011,3 +2058,40 @@ def rmcl_clusters(dMt, handle=None):
     _call("hip_rmcl_clusters", dt, _hp(handle), dMt.rows, dMt.cols, dMt.nnz, *_ptrs(dMt.rowPtr, dMt.colInd, dMt.values),
           C.byref(k), *out.refs())
     return Clusters(dMt.rows, k.value, *out.values())
+
+
+# ---------------------------------------------------------------------------------------------
+# sparse add and symmetrisation (include/spgemm_hip.h "sparse add and the symmetrisation of a directed graph"); the
+# CSR methods add / symmetrize are the object form.  The reference has no counterpart: its loader only transposes.
+# ---------------------------------------------------------------------------------------------
+def csr_add_raw(handle, m, n, alpha, IA, JA, VA, nnzA, beta, IB, JB, VB, nnzB, dtype=np.float32):
+    """hip_csr_add / _f64 on raw device pointers: alpha * A + beta * B -> (dIC, dJC, dC, nnzC) from the library pool"""
+    out = _CsrOut()
+    _call("hip_csr_add", dtype, _hp(handle), int(m), int(n), float(alpha), *_ptrs(IA, JA, VA), int(nnzA), float(beta),
+          *_ptrs(IB, JB, VB), int(nnzB), *out.refs())
+    return out.values()
+
+
+def csr_scale_raw(handle, m, n, nnz, IA, JA, VA, rowScale, colScale, VOut, dtype=np.float32):
+    """hip_csr_scale / _f64: VOut[j] = (rowScale[row] * VA[j]) * colScale[JA[j]]; a scale of None is 1; VOut may be VA"""
+    _call("hip_csr_scale", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA, rowScale, colScale, VOut))
+
+
+def csr_col_counts_raw(handle, n, nnz, JA, count, dtype=np.float32):
+    """hip_csr_col_counts: count (the caller's device int32[n]) = entries per column.  dtype is accepted like the
+    neighbours' and not used: the call reads no value."""
+    _value_dtype(dtype)
+    _check(lib().hip_csr_col_counts(_hp(handle), int(n), int(nnz), *_ptrs(JA, count)), "hip_csr_col_counts")
+
+
+def degree_factors_raw(handle, length, count, exponent, out, dtype=np.float32):
+    """hip_degree_factors / _f64: out[i] = count[i] ** -exponent in the value type, 0 where the count is 0"""
+    _call("hip_degree_factors", dtype, _hp(handle), int(length), C.c_void_p(count), float(exponent), C.c_void_p(out))
+
+
+def csr_symmetrize_raw(handle, mode, alpha, beta, m, IA, JA, VA, nnz, dtype=np.float32):
+    """hip_csr_symmetrize / _f64 on raw device pointers -> (dIS, dJS, dS, nnzS) from the library pool"""
+    out = _CsrOut()
+    _call("hip_csr_symmetrize", dtype, _hp(handle), int(mode), float(alpha), float(beta), int(m), *_ptrs(IA, JA, VA),
+          int(nnz), *out.refs())
+    return out.values()
