@@ -330,6 +330,14 @@ int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, long long* 
  * rows than SPGEMM_MW_MINROWS (default: 32 x the number of CUs; the tests set 1).  SPGEMM_MW_PERCU=<1..32> sets the waves
  * of the wave-per-row kernel per CU (default 16). */
 int spgemm_hip_debug_midrow_kernels(spgemm_handle* h, long long* wave_rows, long long* multiwave_rows);
+/* ... and the symbolic kernel that counted and logged the rows of 513-2048 products of the latest product, when its
+ * symbolic pass logged: k_sym_midpair (one statically scheduled launch over the bin, two rows of 513-1024 products at a time
+ * in a block) or the four-wave kernel with its row queue.  SPGEMM_SYM_PAIR=1 (read at handle creation; default 0: measured no
+ * faster) turns k_sym_midpair on for the one-shot hip_gpuSpMM / hip_CSR_SpMM whose previous product on the handle had the same
+ * m, n and nnz(A) and at least SPGEMM_SP_MINROWS such rows (default: 32 x the number of CUs; 0 takes it without asking, which
+ * the tests set); every other product keeps the four-wave kernel.  SPGEMM_SP_WAVES=2|4 sets the waves of its blocks (default
+ * 4: two per row of 513-1024 products), SPGEMM_SP_PERCU=<1..8> its blocks per CU (default 6). */
+int spgemm_hip_debug_midrow_sym_paths(spgemm_handle* h, long long* pair_rows, long long* multiwave_rows);
 
 /* ---- the step in front of the path: COO -> CSR on device arrays -------------
  * Replaces COO::addSelfLoopIfNeeded (nlibs/COO.cc:160-188), COO::makeOrdered / orderedAndDuplicatesRemoving

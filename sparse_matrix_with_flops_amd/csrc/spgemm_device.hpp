@@ -1490,6 +1490,234 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
   if constexpr (LOG) if (tid == 0 && loggedSum) atomicAdd(ml.logged, loggedSum);
 }
 
+// ---- bin 6 of a logging symbolic pass: k_sym_midpair.  k_sym_hash<4,4096,2,true> gives every row of 513-2048 products four
+// waves, a dequeue and seven block barriers, and a row has 49 A entries on average: one staged group, three waves waiting
+// for it.  Here a block of HW waves has ONE table of 4096 keys, and one launch runs over both layout slots on the static
+// schedule of k_num_midwave (each XCD's eighth of the heavy slot first, then its eighth of the light one; no queue word):
+//   heavy rows (1025-2048 products): all HW waves on one row, the whole table (two slots per product);
+//   light rows (513-1024 products): TWO rows at a time, HW/2 waves and HALF of the table each (two slots per product,
+//     load <= 0.5 where the four-wave kernel gives them four).
+// The walk is the wave-per-row one and needs no barrier: EVERY wave of a row stages every group of 64 A entries for itself
+// (one load and one scan, the same for all of them) and takes the rounds k, k + K, ... of the group's products, up to 8
+// gathered before the first insert.  So a row costs two block barriers whatever its shape -- behind the table clear and
+// behind the count -- which is what lets two light rows share a block: both halves pass the same barriers (a half without
+// a row on the last trip passes them idle).  The row's counters alternate between two sets, so the next row's reset needs
+// no third barrier.  The next two rows' metadata and the next row's first A entries are in flight as in k_sym_hash<1, ..>.
+// HW = 2: 19.5 KB of LDS (a light row has one wave: no barrier in that mode).  HW = 4: 22.5 KB.  The compiler's occupancy
+// figures are 8 and 7 blocks per CU; measured, six of either are resident, and the host launches six (spPerCU).
+// Measured on the headline matrix (profiles/README.md, "Mid rows, symbolic"): HW = 4 equals the four-wave kernel's time, HW = 2
+// is 12 % behind it -- so the launch is opt-in (SPGEMM_SYM_PAIR=1).
+// The log is k_sym_hash<.., true>'s in meaning: IC exact, a row logs products - IC columns, meta / fbList / cursor / logged
+// as there.  Chunks are reserved by the block for heavy rows and by each half for light ones (half 0 goes on in the block's
+// chunk).  `took`: rows this launch processed (test hook).
+#ifndef SMF_SP_CH
+#define SMF_SP_CH 1
+#endif
+constexpr int SP_CH = SMF_SP_CH;                  // rounds of a trip inserted per probe loop, as in the wave-per-row kernels
+struct MidPairCtr { int cnt, logCnt, logOvf; };
+template <int HW>
+struct MidPairShared {
+  int keys[4096];
+  WalkStage1 st[HW];                             // every wave stages for itself
+  MidPairCtr ctr[2][2];                          // [half][row parity]: distinct columns, re-hits logged, "passed the cap" (heavy rows: half 0's)
+  unsigned long long chunk[2];                   // the chunk a half (heavy rows: the block) reserved last
+};
+static_assert(sizeof(MidPairShared<4>) <= 24 * 1024, "k_sym_midpair: six blocks per CU with room to spare");
+
+// U rounds of 64 short products of one staged group, the rounds given one by one (short_trip takes consecutive ones)
+template <int U, class F>
+__device__ __forceinline__ void short_trip_at(const char* rec, int T, int ns, const int (&rnd)[U], const unsigned long long (&W)[U],
+                                              const int (&base)[U], const int* __restrict__ JB, F&& f) {
+  const int lane = lane_id();
+  int col[U];
+  bool act[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {                          // straight-line, no branches around the gathers
+    const int p0 = rnd[u] * WAVE + lane;
+    act[u] = p0 < T;
+    const int p = min(p0, T - 1);                        // lanes past the end shadow the last product: valid, nearby reads
+    int e = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(W[u] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)W[u], (unsigned)base[u]));
+    e = min(e, ns - 1);
+    const int2 ra = *reinterpret_cast<const int2*>(rec + e * 8);
+    col[u] = JB[ra.x + p];
+  }
+  __builtin_amdgcn_sched_barrier(0);                     // all U gathers are issued before the first of them is waited for
+  f(act, col);
+}
+
+// the wave-per-row walk (for_each_product<1>, symbolic) of wave k of the K that share a row: all groups staged, the rounds
+// k, k + K, ... of each walked.  f(act[R], col[R]) for R in {1,2,3,4,6,8}, in wave-uniform control flow.
+template <int K, class F>
+__device__ __forceinline__ void for_each_column_dealt(WalkStage1& st, int k, int as, int ae, const int2* __restrict__ SBL,
+                                                      const int* __restrict__ JB, F&& f, PreA pre, int* err) {
+  const int lane = lane_id();
+  for (int gb = as; gb < ae; gb += WAVE) {
+    const GroupLanes g = stage_group<false, 8, 0x40000000>(st.marks, reinterpret_cast<char*>(st.rec), gb + lane, ae, SBL, nullptr,
+                                                           gb == as ? pre : PreA{0, 0, 0.f, false});
+    if (g.T > WAVE * WAVE || g.T <= 0) {                 // more than a row of this bin has / nothing but empty B rows
+      if (g.T > 0 && err && lane == 0) atomicOr(err, ERRF_TABLE_FULL);
+      continue;
+    }
+    const int nr = (g.T + WAVE - 1) >> 6;
+    const int nj = nr > k ? (nr - k + K - 1) / K : 0;    // this wave's rounds of the group: k + j K, j < nj
+    const unsigned mlo = (unsigned)g.mw, mhi = (unsigned)(g.mw >> 32);
+    for (int j0 = 0; j0 < nj; j0 += 8) {
+      with_rounds(min(8, nj - j0), [&](auto rc) {
+        constexpr int R = decltype(rc)::value;
+        unsigned long long W[R];
+        int base[R], rnd[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+          rnd[u] = k + (j0 + u) * K;                     // (past the group's end for the rounds that pad 5 to 6 and 7 to 8: no lane active)
+          const int r = min(rnd[u], WAVE - 1);
+          W[u] = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)mlo, r) |
+                 ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)mhi, r) << 32);
+          base[u] = __builtin_amdgcn_readlane(g.pexcl, r);
+        }
+        short_trip_at<R>(reinterpret_cast<const char*>(st.rec), g.T, g.ns, rnd, W, base, JB, f);
+      });
+    }
+  }
+}
+
+template <int HW>
+__global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict__ slotBase, int slotLo, int slotHi,
+                                                           const int* __restrict__ rowIds,
+                                                           const int* __restrict__ IA, const int2* __restrict__ SBL,
+                                                           const int* __restrict__ JB,
+                                                           const int* __restrict__ rowFlops, int* __restrict__ IC,
+                                                           int* __restrict__ err, MidLogArgs ml,
+                                                           unsigned long long* __restrict__ took) {
+  static_assert(HW == 2 || HW == 4, "two halves of HW/2 waves");
+  constexpr int TBL = 4096, LW = HW / 2;
+  __shared__ __attribute__((aligned(16))) MidPairShared<HW> sh;
+  const int tid = threadIdx.x, lane = lane_id(), w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  WalkStage1& st = sh.st[w];
+  int* const dummy = reinterpret_cast<int*>(&st.dummy[lane]);
+  st.dummy[lane] = DUMMY_SLOT;
+  wave_lds_sync();
+  // first int of the chunk in use, ints of it in use (MD_CHUNK: none reserved yet): uniform over the waves of a row;
+  // re-hits of direct rows and rows processed: kept by the first wave of a row
+  unsigned long long chunkStart = 0ull;
+  int cursor = MD_CHUNK;
+  unsigned long long loggedSum = 0ull;
+  int tookRows = 0;
+  int par = 0;
+  const XcdRange xh = xcd_range(slotBase[slotHi + 1] - slotBase[slotHi]);
+  const XcdRange xl = xcd_range(slotBase[slotLo + 1] - slotBase[slotLo]);
+  const int* const hiRows = rowIds + slotBase[slotHi] + xh.lo;
+  const int* const loRows = rowIds + slotBase[slotLo] + xl.lo;
+  const int nhi = xh.hi - xh.lo, nlo = xl.hi - xl.lo;
+  const int nb = xh.nb;
+  // one row by the K waves that share it; this wave is number k of them and this thread number gt.  have = false: a half
+  // without a row, which only passes the barriers
+  auto do_row = [&](auto kc, bool have, const RowMeta& cur, const PreA& pc, int* keys, int tblMax, int k, int gt,
+                    MidPairCtr* sets, unsigned long long* chunkSlot) {
+    constexpr int K = decltype(kc)::value;
+    auto sync = [] { if constexpr (K == HW) __syncthreads(); else if constexpr (K == 1) wave_lds_sync(); else __syncthreads(); };
+    MidPairCtr& rc = sets[par];
+    const int size = table_size<2>(cur.x0, 64, tblMax);
+    const int shift = 32 - log2_pow2(size);
+    const bool newChunk = have && cursor + ml.cap > MD_CHUNK;   // row-uniform: the chunk may not hold another row
+    if (have) {
+      clear_table(keys, nullptr, size, gt, K * WAVE);
+      if (gt == 0) {
+        rc.cnt = 0; rc.logCnt = 0; rc.logOvf = 0;
+        if (newChunk) *chunkSlot = atomicAdd(ml.cursor, (unsigned long long)MD_CHUNK);
+      }
+    }
+    sync();
+    if (newChunk) { chunkStart = *chunkSlot; cursor = 0; }   // (written again at the start of a later row, behind this row's barriers)
+    const bool logging = chunkStart + (unsigned long long)MD_CHUNK <= (unsigned long long)ml.logCap;
+    if (have) {
+      int* const myLog = logging ? ml.log + chunkStart + cursor : nullptr;
+      const int room = min(ml.cap, MD_CHUNK - cursor);   // (= cap; the chunk bounds every store whatever cap is)
+      int mine = 0;
+      for_each_column_dealt<K>(st, k, cur.as, cur.ae, SBL, JB, [&](const auto& act, const auto& col) {
+        constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
+        bool rehit[R];
+        mine += hash_insert_chunked<SP_CH, true>(keys, size, shift, act, col, dummy, err, &rehit);
+        if (logging) {                                   // row-uniform
+          unsigned long long mk[R];
+          int tot = 0;
+#pragma unroll
+          for (int u = 0; u < R; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
+          if (tot) {                                     // wave-uniform
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&rc.logCnt, tot);
+            base = __builtin_amdgcn_readfirstlane(base);
+            if (base + tot > room) {                     // wave-uniform: a row for the fallback kernel
+              if (lane == 0) rc.logOvf = 1;
+            } else {
+#pragma unroll
+              for (int u = 0; u < R; ++u) {              // cursor + base + tot <= cursor + room <= MD_CHUNK
+                if (rehit[u]) myLog[base + mask_rank(mk[u])] = col[u];
+                base += __popcll(mk[u]);
+              }
+            }
+          }
+        }
+      }, pc, err);
+      const int ws = wave_sum(mine);                     // hash_insert_multi counts per lane
+      if (lane == 0 && ws) atomicAdd(&rc.cnt, ws);
+      __builtin_amdgcn_s_waitcnt(0xc07f);                // lgkmcnt(0): the adds that return nothing have landed
+    }
+    sync();                                              // (every wave's inserts are behind it: the table is free, too)
+    if (have) {
+      const int cnt = rc.cnt, logged = rc.logCnt;        // (this set is reset two rows on, behind the next row's barrier)
+      const int rehits = cur.x0 - cnt;                   // what the row logs when it has room
+      const bool direct = logging && !rc.logOvf;         // then logged <= room <= cap
+      if (gt == 0) {
+        IC[cur.row] = cnt;
+        ml.meta[cur.row] = make_int2((int)chunkStart + cursor, direct ? logged : -1);
+        if (!direct) ml.fbList[atomicAdd(ml.fbCount, 1)] = cur.row;
+      }
+      if (direct) { cursor += logged; if (k == 0) loggedSum += (unsigned long long)logged; }
+      else if (!logging && rehits >= 0 && rehits <= ml.cap) cursor += rehits;   // no log yet: count the demand
+      if (k == 0) ++tookRows;
+    }
+    par ^= 1;
+  };
+  // ---- heavy rows: the block strides over the XCD's share
+  {
+    int q = xh.bi;
+    RowMeta cur = load_meta_sym(hiRows, q, nhi, IA, rowFlops);
+    RowMeta nxt = load_meta_sym(hiRows, q + nb, nhi, IA, rowFlops);
+    PreA pc = load_pre(cur, SBL, nullptr, false);
+    while (q < nhi) {
+      const int qn = q + nb;
+      const RowMeta nn = load_meta_sym(hiRows, qn + nb, nhi, IA, rowFlops);
+      const PreA pn = load_pre(nxt, SBL, nullptr, false);
+      do_row(std::integral_constant<int, HW>{}, true, cur, pc, sh.keys, TBL, w, tid, sh.ctr[0], &sh.chunk[0]);
+      cur = nxt; nxt = nn; pc = pn;
+      q = qn;
+    }
+  }
+  // ---- light rows: half h of block b takes rows 2b + h, 2b + h + 2 nb, ... of the XCD's share
+  {
+    const int h = w / LW, k = w % LW;
+    if (h != 0) { chunkStart = 0ull; cursor = MD_CHUNK; }   // (half 0 keeps the block's chunk)
+    const int stride = 2 * nb;
+    int q0 = 2 * xl.bi;
+    RowMeta cur = load_meta_sym(loRows, q0 + h, nlo, IA, rowFlops);
+    RowMeta nxt = load_meta_sym(loRows, q0 + h + stride, nlo, IA, rowFlops);
+    PreA pc = load_pre(cur, SBL, nullptr, false);
+    while (q0 < nlo) {                                   // block-uniform: both halves pass the same barriers
+      const int qn = q0 + stride;
+      const RowMeta nn = load_meta_sym(loRows, qn + h + stride, nlo, IA, rowFlops);
+      const PreA pn = load_pre(nxt, SBL, nullptr, false);
+      do_row(std::integral_constant<int, LW>{}, q0 + h < nlo, cur, pc, sh.keys + h * (TBL / 2), TBL / 2, k, tid - h * LW * WAVE,
+             sh.ctr[h], &sh.chunk[h]);
+      cur = nxt; nxt = nn; pc = pn;
+      q0 = qn;
+    }
+  }
+  if (lane == 0) {
+    if (loggedSum) atomicAdd(ml.logged, loggedSum);
+    if (tookRows) atomicAdd(took, (unsigned long long)tookRows);
+  }
+}
+
 template <int NW, int TBL, int U, int PRUNE = 0>      // PRUNE: see k_num_g16
 __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ binPtr, int bin,
                                                          const int* __restrict__ rowIds,

@@ -243,6 +243,8 @@ struct HostMirror {                 // one small device block + its pinned host 
   // rows of bin 6 the numeric launches took: k_num_midwave, k_num_middirect (test hook; written after the mirror is
   // taken, read from the device by spgemm_hip_debug_midrow_kernels)
   unsigned long long mdTook[2];
+  // rows of bin 6 that k_sym_midpair processed: written by the symbolic pass, so the mirror has it
+  unsigned long long spTook;
   // {0, rows}: the logged rows of bin 6 that k_num_midwave leaves to k_num_middirect, read by that kernel as the "bin" of
   // their list (the third part of spgemm_handle::midFallback)
   alignas(128) int mwRest[2];
@@ -335,6 +337,21 @@ struct spgemm_handle {
   int mwPerCU = 16;                  // SPGEMM_MW_PERCU: blocks (= waves) of k_num_midwave per CU (measured 4 / 8 / 12 / 16 / 24: 0.301 /
                                      // 0.189 / 0.149 / 0.152 / 0.163 ms per launch on the headline matrix)
   bool mwRan = false;                // the latest numeric launch used k_num_midwave for bin 6
+  // bin 6 of a logging symbolic pass by k_sym_midpair (one statically scheduled launch, two light rows at a time) instead of
+  // k_sym_hash<4,4096,2,true>.  Measured equal at best on the headline matrix (profiles/README.md, "Mid rows, symbolic"): off
+  bool symPair = false;              // SPGEMM_SYM_PAIR=1 turns it on
+  int spWaves = 4;                   // SPGEMM_SP_WAVES=2|4: waves per block (per heavy row; half as many per light row)
+  int spPerCU = 0;                   // SPGEMM_SP_PERCU: its blocks per CU; 0 = 6 -- a seventh block of four waves (158 KB of LDS in all) and an
+                                     // eighth of two do not become resident, and under a static schedule the blocks that wait start their
+                                     // whole share when the others end (measured: 5 / 6 / 7 blocks of four waves 0.280 / 0.271 / 0.322 ms)
+  int spMinRows = 0;                 // SPGEMM_SP_MINROWS: the static schedule pays only with many rows per wave, and the bin's size is on the
+                                     // device when the symbolic launches are queued.  The one-shot product takes the kernel when the handle's
+                                     // previous product had the same m, n and nnz(A) and at least this many rows in bin 6 (default: 32 x the
+                                     // CU count, mwMinRows' default; a wrong guess costs time only).  0: take it without asking (tests)
+  int spPrevM = -1, spPrevN = -1;    // the previous one-shot product: shape, nnz(A), rows of bin 6
+  long long spPrevNnzA = -1;
+  int spPrevRows6 = 0;
+  bool spRan = false;                // the latest symbolic launch used k_sym_midpair
   long long mrLogEnv = 0;            // SPGEMM_MRLOG: ints of the log instead of the computed size (tests run it out of space)
   int2* mrMeta = nullptr;            // workspace block, one pair per row of A
   int* midFallback = nullptr;        // workspace block, three ints per row of A: bin 6's list, then (at cap_m) bin 7's, then (at
@@ -482,6 +499,11 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   h->mwMinRows = 32 * h->numCU;
   env_int("SPGEMM_MW_MINROWS", 1, 1 << 30, &h->mwMinRows);
   env_int("SPGEMM_MW_PERCU", 1, 32, &h->mwPerCU);
+  { int v = 0; env_int("SPGEMM_SYM_PAIR", 0, 1, &v); h->symPair = v != 0; }
+  { int v = h->spWaves; env_int("SPGEMM_SP_WAVES", 2, 4, &v); if (v == 2 || v == 4) h->spWaves = v; }
+  env_int("SPGEMM_SP_PERCU", 1, 8, &h->spPerCU);
+  h->spMinRows = 32 * h->numCU;
+  env_int("SPGEMM_SP_MINROWS", 0, 1 << 30, &h->spMinRows);
   { int v = 0; env_int("SPGEMM_MRLOG", 1, 1 << 30, &v); h->mrLogEnv = v; }
   env_int("SPGEMM_PATH", 0, 2, &h->pathMode);
   env_int("SPGEMM_CHAIN_CFG", INT_MIN, INT_MAX, &h->chainCfg);   // unchecked: chain_cfg() maps anything else to 0
@@ -595,6 +617,16 @@ extern "C" int spgemm_hip_debug_midrow_kernels(spgemm_handle* h, long long* wave
   HIPCHK(hipMemcpy(v, h->dsmall->mdTook, sizeof(v), hipMemcpyDeviceToHost));
   *wave_rows = h->mwRan ? (long long)v[0] : 0;
   *multiwave_rows = (long long)v[1];
+  return SPGEMM_OK;
+}
+
+// ... and which symbolic kernel counted (and logged) the rows of 513-2048 products of a logging pass: k_sym_midpair
+// counts its rows on the device, in the block the host mirrors at the end of the product
+extern "C" int spgemm_hip_debug_midrow_sym_paths(spgemm_handle* h, long long* pair_rows, long long* multiwave_rows) {
+  if (!h || !pair_rows || !multiwave_rows) return fail(SPGEMM_ERR_ARG, "null argument");
+  const long long rows6 = h->mirror.binPtr[7] - h->mirror.binPtr[6];
+  *pair_rows = h->spRan ? (long long)h->mirror.spTook : 0;
+  *multiwave_rows = h->mdLogged && !h->spRan ? rows6 : 0;
   return SPGEMM_OK;
 }
 
@@ -803,12 +835,15 @@ static int launch_classify(spgemm_handle* h, const int* dIA, const int* dJA, con
 // symbolic pass over bins 2..8 (bins 0/1 were preset by K1).  Bin sizes are not known on the host
 // here (no sync): grids are capped by the CU count and every block strides / dequeues over its bin.
 static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
-                           int m, int n, const int* rowIds, int* dIC, int minBin = 0, bool skipH1A = false, bool logBig = false) {
+                           int m, int n, const int* rowIds, int* dIC, int minBin = 0, bool skipH1A = false, bool logBig = false,
+                           bool pairOk = false) {
   const int2* sbl = h->sbl;
   // logBig: a float product's big rows may take k_num_bigdirect -- the symbolic kernel logs their re-hit columns
   h->bdLogged = logBig && h->bigDirect && n > BIG_WC && m > 0;
   // ... and its rows of bins 6-7 k_num_middirect, for any n (the plain pipeline with its default rounds in flight only)
   h->mdLogged = logBig && h->midDirect && m > 0 && minBin == 0 && h->pathMode == 0 && h->U == 2;
+  // ... bin 6 by k_sym_midpair (pairOk: the caller's guess that the bin is large enough, see spMinRows)
+  h->spRan = h->mdLogged && h->symPair && pairOk;
   if (m <= 0) return SPGEMM_OK;
   clear_stale_hip_error();
   const int* bp = h->dsmall->binPtr;
@@ -841,7 +876,18 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
              sbl, dJB, h->rowFlops, dIC, err, qc + 1 * 32, MidLogArgs{}); }
   if (minBin <= 6) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_SYM_HASH4, st);
     // (one launch for both layout slots of bin 6: split like the numeric side it measured 15 % slower)
-    if (h->mdLogged)
+    // k_sym_midpair: both slots in one launch too, statically scheduled (the bin's size is not known here: the grid is
+    // what the CUs hold, a block without rows leaves at once)
+    if (h->spRan) {
+      const int perCU = h->spPerCU > 0 ? h->spPerCU : 6;
+      if (h->spWaves == 4)
+        hipLaunchKernelGGL(k_sym_midpair<4>, dim3(grid8(m, cu * perCU)), dim3(4 * WAVE), 0, st, h->dsmall->slotBase, SLOT_H4A,
+                           SLOT_H4B, rowIds, dIA, sbl, dJB, (const int*)h->rowFlops, dIC, err, mid_log(0), &h->dsmall->spTook);
+      else
+        hipLaunchKernelGGL(k_sym_midpair<2>, dim3(grid8(m, cu * perCU)), dim3(2 * WAVE), 0, st, h->dsmall->slotBase, SLOT_H4A,
+                           SLOT_H4B, rowIds, dIA, sbl, dJB, (const int*)h->rowFlops, dIC, err, mid_log(0), &h->dsmall->spTook);
+    }
+    else if (h->mdLogged)
       hipLaunchKernelGGL((k_sym_hash<4, 4096, 2, true>), dim3(clampi(m, 1, cu * 8)), dim3(256), 0, st, bp, 6, rowIds, dIA,
                          sbl, dJB, h->rowFlops, dIC, err, qc + 2 * 32, mid_log(0));
     else
@@ -1402,13 +1448,18 @@ static int one_shot_front(spgemm_handle* h, const Product<float>& p, const OptIn
       hipEventRecord(h->evMid, s) != hipSuccess)
     return fail(SPGEMM_ERR_HIP, "classification copy failed: %s", hipGetErrorString(hipGetLastError()));
   if (o.wb2) CHK(launch_wbatch<WB_SYM>(h, p.m, p.IA, nullptr, p.JB, nullptr, dIC, nullptr, nullptr, 0));
-  CHK(launch_symbolic(h, p.IA, p.JB, p.m, p.n, h->cur_rowIds, dIC, o.minBin, o.skipH1A, true));
+  // k_sym_midpair for bin 6: the handle's previous product looked the same and had enough such rows (spMinRows)
+  const bool pairOk = h->spMinRows <= 0 || (h->spPrevM == p.m && h->spPrevN == p.n && h->spPrevNnzA == (long long)p.nnzA &&
+                                            h->spPrevRows6 >= h->spMinRows);
+  CHK(launch_symbolic(h, p.IA, p.JB, p.m, p.n, h->cur_rowIds, dIC, o.minBin, o.skipH1A, true, pairOk));
   hipEventRecord(h->ev[2], s);
   if (!o.chain) CHK(launch_scan(h, dIC, p.m, &h->dsmall->nnzC64));
   hipEventRecord(h->ev[3], s);
   if (hipEventSynchronize(h->evMid) != hipSuccess)
     return fail(SPGEMM_ERR_HIP, "classification failed: %s", hipGetErrorString(hipGetLastError()));
   *mid = *h->hmid;
+  h->spPrevM = p.m; h->spPrevN = p.n; h->spPrevNnzA = (long long)p.nnzA;
+  h->spPrevRows6 = mid->binPtr[7] - mid->binPtr[6];
   return SPGEMM_OK;
 }
 

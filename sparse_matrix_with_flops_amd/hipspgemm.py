@@ -64,7 +64,7 @@ EXPORTS = [
     "hip_sharded_spmm_info", "hip_sharded_spmm_destroy", "hip_gpuRmclIter_sharded", "spgemm_hip_host_api_stats",
     "hip_sharded_spmm_handle", "spgemm_hip_rccl_available", "spgemm_hip_pool_trim",
     "hip_sharded_rmcl_create", "hip_sharded_rmcl_run", "hip_sharded_rmcl_continue", "hip_sharded_rmcl_result", "hip_sharded_rmcl_iter_nnz",
-    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_debug_bigrow_paths", "spgemm_hip_debug_midrow_paths", "spgemm_hip_debug_midrow_log", "spgemm_hip_debug_midrow_kernels", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
+    "hip_sharded_rmcl_info", "hip_sharded_rmcl_destroy", "spgemm_hip_debug_fail_next", "spgemm_hip_debug_bigrow_paths", "spgemm_hip_debug_midrow_paths", "spgemm_hip_debug_midrow_log", "spgemm_hip_debug_midrow_kernels", "spgemm_hip_debug_midrow_sym_paths", "spgemm_hip_rmcl_devices_used", "spgemm_hip_handle_device",
     "hip_gpuSpMM_f64", "hip_spgemm_numeric_f64", "hip_CSR_SpMM_f64", "hip_csr_sort_rows_f64",
     "hip_csr_permute", "hip_csr_permute_f64", "hip_permutation_transpose", "hip_csr_row_descending_permutation",
     "hip_csr_transpose", "hip_csr_transpose_f64", "spgemm_hip_device_synchronize",
@@ -337,6 +337,8 @@ def lib():
             L.spgemm_hip_debug_midrow_log.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 3
         if hasattr(L, "spgemm_hip_debug_midrow_kernels"):
             L.spgemm_hip_debug_midrow_kernels.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 2
+        if hasattr(L, "spgemm_hip_debug_midrow_sym_paths"):
+            L.spgemm_hip_debug_midrow_sym_paths.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 2
         L.spgemm_hip_handle_device.argtypes = [C.c_void_p]
         L.free = C.CDLL(None).free
         L.free.argtypes = [C.c_void_p]
@@ -474,6 +476,13 @@ class Handle:
         return {"rows": v[0].value, "direct": v[1].value, "fallback": v[2].value, "cap": v[3].value,
                 "logged": w[0].value, "reserved": w[1].value, "capacity": w[2].value,
                 "wave": k[0].value, "multiwave": k[1].value}
+
+    def midrow_sym_paths(self):
+        """test hook: rows of 513-2048 products of the latest product whose symbolic pass logged them, by the kernel that
+        did: k_sym_midpair (SPGEMM_SYM_PAIR=1) / the four-wave kernel"""
+        k = [C.c_longlong(0) for _ in range(2)]
+        _check(lib().spgemm_hip_debug_midrow_sym_paths(self._h, *[C.byref(x) for x in k]), "spgemm_hip_debug_midrow_sym_paths")
+        return {"pair": k[0].value, "multiwave": k[1].value}
 
     def close(self):
         if self._h and self._own:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Which numeric kernel the rows of 513-4096 products take on the benchmark's SpGEMM workloads: C = A * A three times on a
-fresh handle (the first call has no log), then Handle.midrow_paths() of the third call, one JSON line per workload.
+fresh handle (the first call has no log), then Handle.midrow_paths() of the third call -- with the log's size and the
+symbolic kernel that filled it (Handle.midrow_sym_paths()) -- one JSON line per workload.
 The SPGEMM_* knobs in the environment apply (SPGEMM_MW_MINROWS=1 forces the wave-per-row kernel on a small bin 6).
 
     python tools/midrow_split.py [workload ...]          (default: the four SpGEMM workloads of bench.py)
@@ -34,6 +35,8 @@ def split(name):
         for _ in range(3):
             hs.gpuSpMMWrapper(dA, dA, h).deviceDispose()
         p = h.midrow_paths()
+        if hasattr(h, "midrow_sym_paths"):               # the symbolic kernel of bin 6 (SPGEMM_SYM_PAIR, SPGEMM_SP_MINROWS)
+            p.update({"sym_" + k: v for k, v in h.midrow_sym_paths().items()})
     finally:
         dA.deviceDispose()
         h.close()
