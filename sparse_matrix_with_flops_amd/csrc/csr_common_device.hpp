@@ -184,10 +184,7 @@ static inline size_t scan_scratch_bytes(long long longest) {
 
 // in-place exclusive scan of data[0..cnt), data[cnt] = total (the k_scan_* kernels of the SpGEMM path)
 static inline void scan_inplace(hipStream_t s, int* data, int cnt, unsigned long long* tile) {
-  const int ntiles = std::max(1, cdiv(cnt, SCAN_TILE));
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(SCAN_THREADS), 0, s, cnt, data, tile + 1);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, ntiles, tile + 1, tile);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(SCAN_THREADS), 0, s, cnt, data, tile + 1, tile, 1);
+  scan_launches(s, data, cnt, tile + 1, tile, true);
 }
 
 // scan_inplace, then its 64-bit total on the host (one blocking read-back); what counts as an overflow is the caller's

@@ -724,65 +724,77 @@ __global__ __launch_bounds__(K1_THREADS) void k_row_flops(
 }
 
 // ------------------------------------------------------------------------------------------------
-// K2  exclusive scan of the per-block histograms in (bin-major, block-minor) order -> where each
-//     block writes its rows of each layout slot; binPtr[NBINS+1].  One 1024-thread block.
+// K2  exclusive scan of the per-block histograms, one layout slot per block: blockOff[slot][block] = rows of the slot in
+//     the blocks before this one, slotTot[slot] = rows of the slot.  Block 0 also sums blockP into totalP.  A thread
+//     holds K2_ITEMS consecutive counts; a tile of 1024 x K2_ITEMS counts is loaded before its first use and scanned
+//     with one block scan (16 x nblk counts in NSLOTS blocks, where one block used to walk them wave by wave).
+//     The running sums over the slots (slotBase, binPtr) are 16 adds: K3 makes them in its prologue.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_bin_scan(int nblk, const int* __restrict__ blockHist,
-                                                    int* __restrict__ blockOff, int* __restrict__ binPtr,
-                                                    int* __restrict__ slotBase,
-                                                    const unsigned long long* __restrict__ blockP,
-                                                    unsigned long long* __restrict__ totalP) {
-  static_assert(NSLOTS <= 16, "one wave of the 1024-thread block per layout slot");
-  __shared__ int slotTot[16];
-  __shared__ unsigned long long ptot;
-  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-  if (tid == 0) ptot = 0;
-  __syncthreads();
-  {
+constexpr int K2_THREADS = 1024;
+constexpr int K2_ITEMS = 4;
+constexpr int K2_TILE = K2_THREADS * K2_ITEMS;
+
+__global__ __launch_bounds__(K2_THREADS) void k_bin_scan(int nblk, const int* __restrict__ blockHist,
+                                                          int* __restrict__ blockOff, int* __restrict__ slotTot,
+                                                          const unsigned long long* __restrict__ blockP,
+                                                          unsigned long long* __restrict__ totalP) {
+  __shared__ int wsum[2][K2_THREADS / WAVE];            // (two sets: one barrier per tile)
+  __shared__ unsigned long long psum[K2_THREADS / WAVE];
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6, sl = blockIdx.x;
+  const int* src = blockHist + (size_t)sl * nblk;
+  int* dst = blockOff + (size_t)sl * nblk;
+  int run = 0;                                           // rows of the slot in the tiles before this one (block-uniform)
+  for (int t0 = 0, it = 0; t0 < nblk; t0 += K2_TILE, it ^= 1) {
+    const int base = t0 + tid * K2_ITEMS;
+    int v[K2_ITEMS];
+    int s = 0;
+#pragma unroll
+    for (int i = 0; i < K2_ITEMS; ++i) { v[i] = base + i < nblk ? src[base + i] : 0; s += v[i]; }
+    const int incl = wave_incl_add(s);
+    if (lane == 63) wsum[it][w] = incl;
+    __syncthreads();
+    int woff = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < K2_THREADS / WAVE; ++i) { const int x = wsum[it][i]; tot += x; if (i < w) woff += x; }
+    int o = run + woff + incl - s;
+#pragma unroll
+    for (int i = 0; i < K2_ITEMS; ++i) { if (base + i < nblk) dst[base + i] = o; o += v[i]; }
+    run += tot;
+  }
+  if (tid == 0) slotTot[sl] = run;
+  if (sl == 0) {
     unsigned long long p = 0;
-    for (int b = tid; b < nblk; b += 1024) p += blockP[b];
+    for (int b = tid; b < nblk; b += K2_THREADS) p += blockP[b];
     p = wave_sum_u64(p);
-    if (lane == 0 && p) atomicAdd(&ptot, p);
-  }
-  // wave w scans the counts of slot w over the blocks (slot-major arrays: coalesced, no barriers inside)
-  if (w < NSLOTS) {
-    const int* src = blockHist + (size_t)w * nblk;
-    int* dst = blockOff + (size_t)w * nblk;
-    int run = 0;
-    for (int t0 = 0; t0 < nblk; t0 += 4 * WAVE) {
-      int v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const int blk = t0 + i * WAVE + lane; v[i] = blk < nblk ? src[blk] : 0; }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int blk = t0 + i * WAVE + lane;
-        const int incl = wave_incl_add(v[i]);
-        if (blk < nblk) dst[blk] = run + incl - v[i];
-        run += __shfl(incl, 63, 64);
-      }
+    if (lane == 0) psum[w] = p;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long t = 0;
+      for (int i = 0; i < K2_THREADS / WAVE; ++i) t += psum[i];
+      *totalP = t;
     }
-    if (lane == 0) slotTot[w] = run;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    *totalP = ptot;
-    int run = 0;
-    binPtr[0] = 0;
-    for (int sl = 0; sl < NSLOTS; ++sl) { slotBase[sl] = run; run += slotTot[sl]; }
-    slotBase[NSLOTS] = run;
-    for (int b = 0; b < NBINS; ++b) binPtr[b + 1] = slotBase[last_slot_of_bin(b) + 1];
   }
 }
 
 // ------------------------------------------------------------------------------------------------
 // K3  stable scatter of row ids into their layout slots (rows ascend inside a bin / a size class of the last bin).
+//     Prologue: every block turns K2's NSLOTS slot totals into the slots' first positions; block 0 leaves them, and the
+//     bins' (binPtr), in the device block for the kernels of the later phases.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(K1_THREADS) void k_scatter_rows(int m, const unsigned char* __restrict__ binId,
                                                              const int* __restrict__ blockOff,
-                                                             const int* __restrict__ slotBase,
+                                                             const int* __restrict__ slotTot,
+                                                             int* __restrict__ slotBase, int* __restrict__ binPtr,
                                                              int* __restrict__ rowIds) {
+  static_assert(NSLOTS <= WAVE, "one wave scans the slot totals");
   __shared__ int wcnt[K1_THREADS / WAVE][NSLOTS];
+  __shared__ int sbase[NSLOTS + 1];
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  if (w == 0) {
+    const int incl = wave_incl_add(lane < NSLOTS ? slotTot[lane] : 0);
+    if (lane < NSLOTS) sbase[lane + 1] = incl;
+    if (lane == 0) sbase[0] = 0;
+  }
   const int r = blockIdx.x * K1_THREADS + tid;
   const int b = r < m ? (int)binId[r] : -1;
   int myrank = 0;
@@ -793,8 +805,12 @@ __global__ __launch_bounds__(K1_THREADS) void k_scatter_rows(int m, const unsign
     if (lane == 0) wcnt[w][q] = __popcll(mk);
   }
   __syncthreads();
+  if (blockIdx.x == 0) {
+    if (tid <= NSLOTS) slotBase[tid] = sbase[tid];
+    if (tid <= NBINS) binPtr[tid] = tid ? sbase[last_slot_of_bin(tid - 1) + 1] : 0;
+  }
   if (b >= 0) {
-    int off = slotBase[b] + blockOff[(size_t)b * gridDim.x + blockIdx.x];
+    int off = sbase[b] + blockOff[(size_t)b * gridDim.x + blockIdx.x];
     for (int i = 0; i < w; ++i) off += wcnt[i][b];
     rowIds[off + myrank] = r;
   }
@@ -2912,7 +2928,10 @@ __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ sl
 
 // ------------------------------------------------------------------------------------------------
 // Exclusive scan of IC[0..m) -> offsets, IC[m] = nnzC (64-bit total kept for the overflow check).
-// Three small launches: per-block sums, one block scans the sums, per-block rescan with offset.
+// Two launches: per-tile sums, then a rescan per tile whose block first adds up the sums of the tiles before its own
+// (up to SCAN_FOLD_MAX tiles: 256 at a million rows, one value per thread).  Beyond that the sums before a tile are
+// too many to add up in every block: a one-block launch scans them in between (k_scan_tiles), as the cut of the
+// one-pass path does.
 // (thrust::exclusive_scan in the reference: nlibs/gpus/gpu_csr_kernel.cu:149-150)
 // ------------------------------------------------------------------------------------------------
 constexpr int SCAN_THREADS = 1024;
@@ -2961,27 +2980,40 @@ __global__ __launch_bounds__(1024) void k_scan_tiles(int ntiles, unsigned long l
 
 // clampTotal: IC[m] = min(total, INT_MAX) (C.rowPtr: the host rejects an overflow anyway); otherwise the total wraps
 // modulo 2^32 like the interior prefixes, so that differences of neighbours stay exact (the dflops scan of the
-// classification API, whose consumers take differences)
+// classification API, whose consumers take differences).
+// FOLD: tileSum holds the tiles' own sums (k_scan_tile_sums) and the last block writes *total; otherwise tileSum holds
+// their exclusive scan and *total is there already (k_scan_tiles).
+template <bool FOLD>
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(int m, int* __restrict__ IC,
-                                                              const unsigned long long* __restrict__ tileOff,
-                                                              const unsigned long long* __restrict__ total, int clampTotal) {
+                                                              const unsigned long long* __restrict__ tileSum,
+                                                              unsigned long long* __restrict__ total, int clampTotal) {
   __shared__ int wsum[16];
+  __shared__ unsigned long long osum[16];
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int base = blockIdx.x * SCAN_TILE + tid * SCAN_ITEMS;
   int v[SCAN_ITEMS];
   int s = 0;
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; ++i) { v[i] = base + i < m ? IC[base + i] : 0; s += v[i]; }
+  unsigned long long before = 0;                           // FOLD: this thread's share of the tiles before the block's
+  if (FOLD) {
+    for (int t = tid; t < (int)blockIdx.x; t += SCAN_THREADS) before += tileSum[t];
+    before = wave_sum_u64(before);
+    if (lane == 0) osum[w] = before;
+  }
   const int incl = wave_incl_add(s);
   if (lane == 63) wsum[w] = incl;
   __syncthreads();
   int woff = 0;
   for (int i = 0; i < w; ++i) woff += wsum[i];
-  int run = (int)tileOff[blockIdx.x] + woff + incl - s;
+  if (FOLD) { before = 0; for (int i = 0; i < 16; ++i) before += osum[i]; }
+  else before = tileSum[blockIdx.x];
+  int run = (int)before + woff + incl - s;
 #pragma unroll
   for (int i = 0; i < SCAN_ITEMS; ++i) { if (base + i < m) IC[base + i] = run; run += v[i]; }
-  if (blockIdx.x == 0 && tid == 0) {
-    const unsigned long long t = *total;
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+    const unsigned long long t = FOLD ? before + tileSum[blockIdx.x] : *total;
+    if (FOLD) *total = t;
     IC[m] = (clampTotal && t > 0x7fffffffULL) ? 0x7fffffff : (int)(unsigned)t;
   }
 }

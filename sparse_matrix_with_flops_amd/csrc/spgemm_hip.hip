@@ -223,7 +223,8 @@ struct HostMirror {                 // one small device block + its pinned host 
   // slotBase, which every block reads when it starts) made all of them queue up behind one another in the L2.
   alignas(128) int qctr[10 * 32];
   alignas(128) int qpad_;
-  int slotBase[NSLOTS + 1];         // first position of every layout slot in rowIds, [NSLOTS] = m (k_bin_scan)
+  int slotBase[NSLOTS + 1];         // first position of every layout slot in rowIds, [NSLOTS] = m (k_scatter_rows)
+  int slotTot[NSLOTS];              // rows of every layout slot (k_bin_scan)
   unsigned long long totalP;
   unsigned long long nnzC64;
   unsigned long long kept64;        // entries that survive the fused R-MCL prune
@@ -739,6 +740,27 @@ static inline int clampi(long long v, int lo, int hi) { return (int)std::max<lon
 // grid of a statically scheduled kernel: a multiple of 8 (one contiguous eighth of the work per XCD: xcd_range)
 static inline int grid8(long long want, int hi) { return (clampi(want, 8, hi) + 7) & ~7; }
 
+// Tiles up to which every block of k_scan_apply adds up the sums of the tiles before its own (two launches); above, a
+// one-block launch scans the sums in between.  A block reads its share of the sums in one round of loads up to 1024 tiles
+// and in four at the limit; the work of all blocks together grows with the square of the tiles, so it has a limit.
+// -DSMF_SCAN_FOLD_MAX=0: always three launches.
+#ifndef SMF_SCAN_FOLD_MAX
+#define SMF_SCAN_FOLD_MAX 4096
+#endif
+// the launches of an in-place exclusive scan of cnt[0..m), cnt[m] = total (clamped to INT_MAX or wrapping: k_scan_apply);
+// tileSum: one word per tile of SCAN_TILE ints, *dTotal: the exact total
+static inline void scan_launches(hipStream_t s, int* cnt, int m, unsigned long long* tileSum, unsigned long long* dTotal,
+                                 bool clampTotal) {
+  const int ntiles = std::max(1, cdiv(m, SCAN_TILE));
+  hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(SCAN_THREADS), 0, s, m, cnt, tileSum);
+  if (ntiles <= SMF_SCAN_FOLD_MAX) {
+    hipLaunchKernelGGL(k_scan_apply<true>, dim3(ntiles), dim3(SCAN_THREADS), 0, s, m, cnt, tileSum, dTotal, clampTotal ? 1 : 0);
+  } else {
+    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, ntiles, tileSum, dTotal);
+    hipLaunchKernelGGL(k_scan_apply<false>, dim3(ntiles), dim3(SCAN_THREADS), 0, s, m, cnt, tileSum, dTotal, clampTotal ? 1 : 0);
+  }
+}
+
 static const char* kKernelNames[SPGEMM_NKERNELS] = {
     "k_row_flops", "k_bin_scan", "k_scatter_rows", "k_sym_g16<32,1>", "k_sym_g16", "k_sym_hash<1,1024>",
     "k_sym_hash<4,4096>", "k_sym_hash<8,8192>", "k_sym_big", "k_scan(3 launches)", "k_num_g16<32,1>", "k_num_g16",
@@ -822,11 +844,11 @@ static int launch_classify(spgemm_handle* h, const int* dIA, const int* dJA, con
       else hipLaunchKernelGGL(k_row_flops<false>, dim3(nblk), dim3(K1_THREADS), 0, h->stream, m, dIA, dJA, dIB, dIBse,
                               sbl, cap, h->rowFlops, h->binId, h->blockHist, h->blockP, dIC); }
     { KTimer t(h, SPGEMM_K_BIN_SCAN);
-      hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, h->stream, nblk, h->blockHist, h->blockOff,
-                         h->dsmall->binPtr, h->dsmall->slotBase, h->blockP, &h->dsmall->totalP); }
-    { KTimer t(h, SPGEMM_K_SCATTER);
+      hipLaunchKernelGGL(k_bin_scan, dim3(NSLOTS), dim3(K2_THREADS), 0, h->stream, nblk, h->blockHist, h->blockOff,
+                         h->dsmall->slotTot, h->blockP, &h->dsmall->totalP); }
+    { KTimer t(h, SPGEMM_K_SCATTER);             // also turns the slot totals into slotBase / binPtr
       hipLaunchKernelGGL(k_scatter_rows, dim3(nblk), dim3(K1_THREADS), 0, h->stream, m, h->binId, h->blockOff,
-                         h->dsmall->slotBase, h->rowIds); }
+                         h->dsmall->slotTot, h->dsmall->slotBase, h->dsmall->binPtr, h->rowIds); }
   }
   HIPCHK(hipGetLastError());
   return SPGEMM_OK;
@@ -913,12 +935,9 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
 
 // exclusive scan of cnt[0..m) in place, cnt[m] = total; 64-bit total lands in *dTotal
 static int launch_scan(spgemm_handle* h, int* cnt, int m, unsigned long long* dTotal, bool clampTotal = true) {
-  const int ntiles = std::max(1, cdiv(m, SCAN_TILE));
   clear_stale_hip_error();
   KTimer t(h, SPGEMM_K_SCAN);
-  hipLaunchKernelGGL(k_scan_tile_sums, dim3(ntiles), dim3(SCAN_THREADS), 0, h->stream, m, cnt, h->tileSum);
-  hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, h->stream, ntiles, h->tileSum, dTotal);
-  hipLaunchKernelGGL(k_scan_apply, dim3(ntiles), dim3(SCAN_THREADS), 0, h->stream, m, cnt, h->tileSum, dTotal, clampTotal ? 1 : 0);
+  scan_launches(h->stream, cnt, m, h->tileSum, dTotal, clampTotal);
   HIPCHK(hipGetLastError());
   return SPGEMM_OK;
 }
