@@ -840,7 +840,7 @@ static int sharded_rmcl_run(spgemm_sharded_rmcl* job, int maxIter, int* nnzOut, 
         HIPCHK(hipMemcpyAsync(N.V.p + off, K.V, sizeof(float) * (size_t)K.nnz, hipMemcpyDeviceToDevice, st));
       } else if (K.nnz > 0) {
         const RowLanes rl = row_lanes(s.h, ml, K.nnz);
-        RMCL_ROWS(k_rmcl_move, rl, st, ml, K.I.p, K.len.p, K.J.p, K.V.p, N.J.p + off, N.V.p + off);
+        RMCL_ROWS(k_rmcl_move, float, rl, st, ml, K.I.p, K.len.p, K.J.p, K.V.p, N.J.p + off, N.V.p + off);
       }
       HIPCHK(hipGetLastError());
       // RCCL runs on this same stream, behind the move; the other transports read the slice from other streams

@@ -3161,163 +3161,8 @@ __global__ __launch_bounds__(256) void k_sort_long_rows(int m, const int* __rest
   }
 }
 
-
-// ------------------------------------------------------------------------------------------------
-// R-MCL post-step (the step right after the SpGEMM in the reference's loop) on a C that is
-// already in HBM: the row rule above + compaction.  CPU: nlibs/tools/util.cc:4-69, nlibs/qrmcl.cc:96-117;
-// reference GPU: nlibs/gpus/dutil.cuh:8-80 + thrust::remove (gpu_csr_kernel.cu:218-229,265-270).
-// 16 lanes per row (4 rows per wave).  Sums are 16-lane tree reductions in float, so a value that sits within an
-// ulp of the threshold can fall on the other side than in the sequential CPU loop (the reference's own GPU path
-// has the same property).
-// ------------------------------------------------------------------------------------------------
-// pass 1: inflate (squares, recomputed where needed, never stored), per-row threshold and kept sum, kept count ->
-// cnt[row].  L lanes per row: 16 for short rows, a whole wave once rows average ~100 entries (R-MCL products do);
-// four loads in flight per lane.
-template <int L>
-__global__ __launch_bounds__(256) void k_rmcl_stats(int m, const int* __restrict__ IC, const float* __restrict__ C,
-                                                     int* __restrict__ cnt, float* __restrict__ thresh,
-                                                     float* __restrict__ ksum) {
-  constexpr int RPB = 256 / L;                       // rows per block
-  const int gl = threadIdx.x & (L - 1);
-  const int nrowsL = (m + RPB - 1) / RPB * RPB;
-  for (int row = blockIdx.x * RPB + threadIdx.x / L; row < nrowsL; row += gridDim.x * RPB) {
-    const bool live = row < m;
-    const int s = live ? IC[row] : 0, e = live ? IC[row + 1] : 0;
-    float mx = 0.f, sum = 0.f;
-    for (int p = s + gl; p < e; p += 4 * L) {
-      float c[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[i] = p + i * L < e ? C[p + i * L] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const float v = c[i] * c[i]; mx = fmaxf(mx, v); sum += v; }   // inflate: v^2
-    }
-    mx = rowL_max<L>(mx);
-    sum = rowL_sum<L>(sum);
-    const float th = rmcl_threshold(sum / (float)(e - s), mx);
-    float ks = 0.f;
-    int kc = 0;
-    for (int p = s + gl; p < e; p += 4 * L) {          // the row was just read: L2
-      float c[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) c[i] = p + i * L < e ? C[p + i * L] : 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const float v = c[i] * c[i]; if (p + i * L < e && v >= th) { ks += v; ++kc; } }
-    }
-    ks = rowL_sum<L>(ks);
-    kc = (int)rowL_sum<L>((float)kc);                  // (< 2^24 per lane group: exact)
-    if (live && gl == 0) { cnt[row] = kc; thresh[row] = th; ksum[row] = ks; }
-  }
-}
-
-// pass 2: stable compaction of the kept entries, normalised, into the new arrays at newPtr[row]
-template <int L>
-__global__ __launch_bounds__(256) void k_rmcl_compact(int m, const int* __restrict__ IC, const int* __restrict__ JC,
-                                                       const float* __restrict__ C, const int* __restrict__ newPtr,
-                                                       const float* __restrict__ thresh, const float* __restrict__ ksum,
-                                                       int* __restrict__ JN, float* __restrict__ CN) {
-  constexpr int RPB = 256 / L;
-  const int gl = threadIdx.x & (L - 1);
-  const int lane = lane_id();
-  const int nrowsL = (m + RPB - 1) / RPB * RPB;
-  for (int row = blockIdx.x * RPB + threadIdx.x / L; row < nrowsL; row += gridDim.x * RPB) {
-    const bool live = row < m;
-    const int s = live ? IC[row] : 0, e = live ? IC[row + 1] : 0;
-    const float th = live ? thresh[row] : 0.f, ks = live ? ksum[row] : 1.f;
-    int out = live ? newPtr[row] : 0;
-    for (int p0 = s; p0 < e; p0 += 2 * L) {            // two steps of L entries, their loads issued together
-      float c[2];
-      int j[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int p = p0 + i * L + gl;
-        c[i] = p < e ? C[p] : 0.f;
-        j[i] = p < e ? JC[p] : 0;
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float v = c[i] * c[i];
-        const bool keep = p0 + i * L + gl < e && v >= th;
-        const unsigned long long mk = ballot64(keep);
-        const unsigned long long gm = L == 64 ? mk : ((mk >> (lane - gl)) & ((1ull << L) - 1ull));
-        if (keep) { const int o = out + __popcll(gm & ((1ull << gl) - 1ull)); JN[o] = j[i]; CN[o] = v / ks; }
-        out += __popcll(gm);
-      }
-    }
-  }
-}
-
-
-// fused path, loop form: {start, end} of every row's kept entries in the scratch arrays, one pair per row
-__global__ __launch_bounds__(256) void k_zip_extents(int m, const int* __restrict__ IC, const int* __restrict__ cnt,
-                                                      int2* __restrict__ se) {
-  const int r = blockIdx.x * 256 + threadIdx.x;
-  if (r < m) { const int s = IC[r]; se[r] = make_int2(s, s + cnt[r]); }
-}
-
-// fused path, after the numeric kernels: the kept entries sit at the front of every row's scratch range
-// [IC[row], ...), newPtr is the scan of their counts -- pack them into the new arrays
-template <int L>
-__global__ __launch_bounds__(256) void k_rmcl_move(int m, const int* __restrict__ IC, const int* __restrict__ newPtr,
-                                                    const int* __restrict__ JC, const float* __restrict__ C,
-                                                    int* __restrict__ JN, float* __restrict__ CN) {
-  constexpr int RPB = 256 / L;
-  const int gl = threadIdx.x & (L - 1);
-  for (int row = blockIdx.x * RPB + threadIdx.x / L; row < m; row += gridDim.x * RPB) {
-    const int src = IC[row], dst = newPtr[row], n = newPtr[row + 1] - dst;
-    for (int i = gl; i < n; i += L) { JN[dst + i] = JC[src + i]; CN[dst + i] = C[src + i]; }
-  }
-}
-
-// fused path, rows the numeric kernels wrote out in full (bin 8: their rows pass through LDS in several pieces): the
-// row rule from HBM / L2 by one block per row, the kept entries compacted IN PLACE to the front of the row's range.
-__global__ __launch_bounds__(256) void k_rmcl_fix_rows(const int* __restrict__ binPtr, int binLo, int binHi,
-                                                        const int* __restrict__ rowIds, const int* __restrict__ IC,
-                                                        int* __restrict__ JC, float* __restrict__ C,
-                                                        int* __restrict__ cnt) {
-  __shared__ float fred[2][4];
-  __shared__ int wcnt[4];
-  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
-  const int first = binPtr[binLo], count = binPtr[binHi] - first;
-  for (int q = blockIdx.x; q < count; q += gridDim.x) {
-    const int row = rowIds[first + q];
-    const int s = IC[row], e = IC[row + 1];
-    float mx = 0.f, sum = 0.f;
-    for (int p = s + tid; p < e; p += 256) { const float c = C[p], v = c * c; mx = fmaxf(mx, v); sum += v; }
-    mx = rowL_max<64>(mx);
-    sum = rowL_sum<64>(sum);
-    if (lane == 0) { fred[0][w] = mx; fred[1][w] = sum; }
-    __syncthreads();
-    mx = fmaxf(fmaxf(fred[0][0], fred[0][1]), fmaxf(fred[0][2], fred[0][3]));
-    sum = ((fred[1][0] + fred[1][1]) + fred[1][2]) + fred[1][3];
-    __syncthreads();
-    const float th = rmcl_threshold(sum / (float)(e - s), mx);
-    float ks = 0.f;
-    for (int p = s + tid; p < e; p += 256) { const float c = C[p], v = c * c; ks += v >= th ? v : 0.f; }
-    ks = rowL_sum<64>(ks);
-    if (lane == 0) fred[0][w] = ks;
-    __syncthreads();
-    ks = ((fred[0][0] + fred[0][1]) + fred[0][2]) + fred[0][3];
-    int out = 0;                                       // kept so far (block-uniform)
-    for (int p0 = s; p0 < e; p0 += 256) {
-      const int p = p0 + tid;
-      const float c = p < e ? C[p] : 0.f;
-      const int j = p < e ? JC[p] : 0;
-      asm volatile("" :: "v"(c), "v"(j));              // both loads have landed before the barrier: writes below may hit
-      const float v = c * c;                           // positions other lanes of this step read
-      const bool keep = p < e && v >= th;
-      const unsigned long long mk = ballot64(keep);
-      if (lane == 0) wcnt[w] = __popcll(mk);
-      __syncthreads();
-      int base = out, total = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { base += i < w ? wcnt[i] : 0; total += wcnt[i]; }
-      if (keep) { const int o = s + base + mask_rank(mk); JC[o] = j; C[o] = v / ks; }
-      out += total;
-      __syncthreads();
-    }
-    if (tid == 0) cnt[row] = out;
-  }
-}
+// (the R-MCL post-step on rows in HBM -- k_rmcl_stats / _compact / _move / _fix_rows, k_zip_extents -- is written once
+// for float and double in rmcl_rows_device.hpp)
 
 // self-test of the DPP scans / mask ranks against serial results computed by every lane
 __global__ void k_selftest(const int* __restrict__ in, int* __restrict__ bad) {

@@ -241,7 +241,8 @@ __device__ __forceinline__ void row64_walk(Row64Stage<NT>& st, int as, int ae, c
 // GLOBAL = false: rows of the bin with lmin <= L_i <= lmax, LDS table of TBL slots.
 // GLOBAL = true: the same in a table of gslots slots per block at gkeys/gvals + blockIdx.x * gslots (device memory).
 // PRUNE: rows that finish in one LDS pass get the R-MCL row rule in the epilogue (kept entries to the front of the row's
-// range, their count to pcnt[row]); multi-pass and device-memory rows are written in full (k_rmcl_fix_rows64 takes them).
+// range, their count to pcnt[row]); multi-pass and device-memory rows are written in full (k_rmcl_fix_rows<double> of
+// rmcl_rows_device.hpp takes them).
 template <int NT, int TBL, bool GLOBAL, bool PRUNE = false>
 __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPtr, int bin, const int* __restrict__ rowIds,
                                                    const int* __restrict__ IA, const int2* __restrict__ SBL,

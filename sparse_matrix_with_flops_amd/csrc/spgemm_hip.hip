@@ -4,6 +4,7 @@
 // every entry point fails with SPGEMM_ERR_NODEVICE / SPGEMM_ERR_HIP.
 #include "spgemm_device.hpp"
 #include "spgemm_f64_device.hpp"
+#include "rmcl_rows_device.hpp"
 #include "chain_device.hpp"
 #include "../../include/spgemm_hip.h"
 
@@ -178,21 +179,24 @@ struct CsrView {
 //                          row, se = {start, end} per row, nnz = extent of (J, V).  The next iteration reads it as it is;
 //   block    (len, no se)  scratch rows too, but len = the SCANNED counts = the row pointer of the packed block (rows + 1
 //                          entries, len[rows] = nnz = kept entries): the sharded loop packs the rows into its slice of Mt.
-struct DevCSR {
-  DevBuf<int> I, J; DevBuf<float> V; DevBuf<int> len; DevBuf<int2> se;
+// Values of type T; the double loop packs after every step, so a DevCSRT<double> is always packed (len, se unused).
+template <class T>
+struct DevCSRT {
+  DevBuf<int> I, J; DevBuf<T> V; DevBuf<int> len; DevBuf<int2> se;
   int rows = 0, cols = 0, nnz = 0;                  // rows, cols: set by upload_csr; a step knows them from its arguments
   bool packed() const { return !len; }
-  CsrView view() const { return {I, J, V, nnz, len, se}; }
+  CsrView view() const { return {I, J, V, nnz, len, se}; }   // (float only: instantiated where it is called)
   hipError_t alloc_entries(long long n) {           // (J, V) for n entries; never a zero-sized block
     const hipError_t e = J.alloc((size_t)std::max(n, 1ll));
     return e != hipSuccess ? e : V.alloc((size_t)std::max(n, 1ll));
   }
-  void reset() { *this = DevCSR(); }
-  void give(int** oI, int** oJ, float** oV, int* onnz) {   // a packed matrix leaves the library (spgemm_hip_free takes it back)
+  void reset() { *this = DevCSRT(); }
+  void give(int** oI, int** oJ, T** oV, int* onnz) {   // a packed matrix leaves the library (spgemm_hip_free takes it back)
     *oI = I.release(); *oJ = J.release(); *oV = V.release(); *onnz = nnz;
     reset();
   }
 };
+using DevCSR = DevCSRT<float>;
 
 // The pool hands a released block to other handles and streams, so a block goes back only when no queued kernel can still
 // touch it.  The owners above release when they leave scope; two rules make that late enough.
@@ -990,8 +994,8 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
                              bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 8 * 32,
                              (const int2*)h->rlMeta, h->rl_rows, (const int*)h->rlLog);
           return 0; }); }
-    if (pcnt) hipLaunchKernelGGL(k_rmcl_fix_rows, dim3(clampi(rows(8, 9), 1, cu * 8)), dim3(256), 0, st,
-                                 bp, 8, 9, rowIds, dIC, dJC, dC, pcnt);
+    if (pcnt) hipLaunchKernelGGL(k_rmcl_fix_rows<float>, dim3(clampi(rows(8, 9), 1, cu * 8)), dim3(256), 0, st,
+                                 bp, 8, 9, rowIds, dIC, dJC, dC, pcnt, -1);   // lmin = -1: every row of the bin
   }
   // bins 6-7 of a product whose symbolic pass logged into a log that exists: k_num_middirect over the bin for the rows with
   // a log, k_num_hash (the larger table of the bin) over the bin's fallback list for the others -- its length is on the
@@ -1332,7 +1336,7 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
       // fused step: the rows that pass through LDS in pieces or through a device-memory table were written in full --
       // the row rule in place, behind both kernels on their stream (timed with the device-memory kernel's slot)
       if (pcnt)
-        hipLaunchKernelGGL(k_rmcl_fix_rows64, dim3(clampi(rows(8, 9), 1, cu * 4)), dim3(256), 0, st, bp, 8, 9, rowIds, dIC, dJC,
+        hipLaunchKernelGGL(k_rmcl_fix_rows<double>, dim3(clampi(rows(8, 9), 1, cu * 4)), dim3(256), 0, st, bp, 8, 9, rowIds, dIC, dJC,
                            dC, pcnt, F64_LDS_MAXL); }
   }
   if (rows(7, 8) > 0) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
@@ -2001,15 +2005,17 @@ static RowLanes row_lanes(const spgemm_handle* h, int m, long long nnz) {
   const bool wide = m > 0 && nnz >= 96ll * m;
   return {wide, wide ? clampi(cdiv(m, 4), 1, h->numCU * 32) : clampi(cdiv(m, 16), 1, h->numCU * 16)};
 }
-#define RMCL_ROWS(kern, rl, stream, ...)                                                              \
-  do {                                                                                                \
-    if ((rl).wide) hipLaunchKernelGGL(kern<64>, dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);  \
-    else hipLaunchKernelGGL(kern<16>, dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);            \
+// kern<16 or 64, V>; V is the value type of the arrays among the arguments
+#define RMCL_ROWS(kern, V, rl, stream, ...)                                                              \
+  do {                                                                                                   \
+    if ((rl).wide) hipLaunchKernelGGL((kern<64, V>), dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);  \
+    else hipLaunchKernelGGL((kern<16, V>), dim3((rl).grid), dim3(256), 0, stream, __VA_ARGS__);            \
   } while (0)
 
 // nnzIn >= 0: the caller knows nnz(C) (it is on the host after every SpGEMM of this library) and the choice of lanes per
 // row needs no device read; nnzIn < 0: one 4-byte copy fetches it.
-static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const float* dC, DevCSR* out) {
+template <class V>
+static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const V* dC, DevCSRT<V>* out) {
   out->reset();
   if (m < 0 || !dIC) return fail(SPGEMM_ERR_ARG, "bad argument");
   if (!h) CHK(default_handle(&h));
@@ -2017,9 +2023,11 @@ static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* 
   h->sym_m = -1;                                   // scan scratch and the small device block are shared with a pending phase
   clear_stale_hip_error();
   CHK(ws_ensure(h, m));
-  DevCSR N;
-  DevBuf<float> th, ks;
-  auto hipfail = [&](const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl prune: %s: %s", what, hipGetErrorString(hipGetLastError())); };
+  DevCSRT<V> N;
+  DevBuf<V> th, ks;
+  auto hipfail = [&](const char* what) {
+    return fail(SPGEMM_ERR_HIP, "rmcl prune%s: %s: %s", std::is_same<V, double>::value ? " (f64)" : "", what, hipGetErrorString(hipGetLastError()));
+  };
   if (N.I.alloc((size_t)m + 1) || th.alloc((size_t)std::max(m, 1)) || ks.alloc((size_t)std::max(m, 1))) return hipfail("device allocation failed");
   hipStream_t s = h->stream;
   if (hipMemsetAsync(&h->dsmall->nnzC64, 0, sizeof(unsigned long long), s) != hipSuccess) return hipfail("memset");
@@ -2032,30 +2040,57 @@ static int rmcl_prune_impl(spgemm_handle* h, int m, long long nnzIn, const int* 
   }
   const RowLanes rl = row_lanes(h, m, nnzIn);
   if (m > 0) {
-    RMCL_ROWS(k_rmcl_stats, rl, s, m, dIC, dC, N.I.p, th.p, ks.p);
-    CHK(launch_scan(h, N.I, m, &h->dsmall->nnzC64));
+    RMCL_ROWS(k_rmcl_stats, V, rl, s, m, dIC, dC, N.I.p, th.p, ks.p);
+    if (int rc = launch_scan(h, N.I, m, &h->dsmall->nnzC64)) return drained(s, rc);
   } else {
     hipMemsetAsync(N.I, 0, sizeof(int), s);
   }
   if (hipMemcpyAsync(&h->hsmall->nnzC64, &h->dsmall->nnzC64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return hipfail("kept-entry count");
+    return drained(s, hipfail("kept-entry count"));
   N.nnz = (int)h->hsmall->nnzC64;
   if (N.alloc_entries(N.nnz)) return hipfail("device allocation failed");
   if (m > 0 && N.nnz > 0) {
-    RMCL_ROWS(k_rmcl_compact, rl, s, m, dIC, dJC, dC, N.I.p, th.p, ks.p, N.J.p, N.V.p);
-    if (hipGetLastError() != hipSuccess) return hipfail("compaction launch");
+    RMCL_ROWS(k_rmcl_compact, V, rl, s, m, dIC, dJC, dC, N.I.p, th.p, ks.p, N.J.p, N.V.p);
+    if (hipGetLastError() != hipSuccess) return drained(s, hipfail("compaction launch"));
   }
-  if (hipStreamSynchronize(s) != hipSuccess) return hipfail("compaction");
+  if (hipStreamSynchronize(s) != hipSuccess) return drained(s, hipfail("compaction"));
   *out = std::move(N);
   return SPGEMM_OK;
 }
 
-static int rmcl_prune_abi(spgemm_handle* h, int m, long long nnz, const int* dIC, const int* dJC, const float* dC, int** dIN,
-                          int** dJN, float** dCN, int* nnzN) {
-  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
-  DevCSR N;
+// ---- the argument checks of the R-MCL entry points, one of each for both precisions ----
+// the four output pointers, set to "nothing" until the call succeeds
+template <class V>
+static int clear_outputs(int** oI, int** oJ, V** oV, int* onnz) {
+  if (!oI || !oJ || !oV || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
+  *oI = nullptr; *oJ = nullptr; *oV = nullptr; *onnz = 0;
+  return SPGEMM_OK;
+}
+// the fused step's: outputs, dimensions, both operands
+template <class V>
+static int rmcl_step_args(const int* dIA, const int* dJA, const V* dA, int nnzA, const int* dIB, const int* dJB, const V* dB,
+                          int nnzB, int m, int k, int n, int** dIN, int** dJN, V** dCN, int* nnzN) {
+  CHK(clear_outputs(dIN, dJN, dCN, nnzN));
+  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
+  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
+  return check_common(dIB, dJB, dB, nnzB, "B");
+}
+// the loop's: outputs, a square matrix, both operands
+template <class V>
+static int rmcl_loop_args(int maxIter, int rows, int cols, const int* gI, const int* gJ, const V* gA, int gnnz, const int* tI,
+                          const int* tJ, const V* tA, int tnnz, int** oI, int** oJ, V** oA, int* onnz) {
+  CHK(clear_outputs(oI, oJ, oA, onnz));
+  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
+  CHK(check_common(gI, gJ, gA, gnnz, "Mgt"));
+  return check_common(tI, tJ, tA, tnnz, "Mt");
+}
+
+template <class V>
+static int rmcl_prune_abi(spgemm_handle* h, int m, long long nnz, const int* dIC, const int* dJC, const V* dC, int** dIN,
+                          int** dJN, V** dCN, int* nnzN) {
+  CHK(clear_outputs(dIN, dJN, dCN, nnzN));
+  DevCSRT<V> N;
   CHK(rmcl_prune_impl(h, m, nnz, dIC, dJC, dC, &N));
   N.give(dIN, dJN, dCN, nnzN);
   return SPGEMM_OK;
@@ -2063,13 +2098,19 @@ static int rmcl_prune_abi(spgemm_handle* h, int m, long long nnz, const int* dIC
 
 extern "C" int hip_rmcl_prune(spgemm_handle* h, int m, const int* dIC, const int* dJC, float* dC, int** dIN, int** dJN,
                               float** dCN, int* nnzN) {
-  return rmcl_prune_abi(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+  return rmcl_prune_abi<float>(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
 }
-
 extern "C" int hip_rmcl_prune_n(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const float* dC,
                                 int** dIN, int** dJN, float** dCN, int* nnzN) {
-  if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative nnz");
-  return rmcl_prune_abi(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+  return nnz < 0 ? fail(SPGEMM_ERR_ARG, "negative nnz") : rmcl_prune_abi<float>(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+}
+extern "C" int hip_rmcl_prune_f64(spgemm_handle* h, int m, const int* dIC, const int* dJC, const double* dC, int** dIN,
+                                  int** dJN, double** dCN, int* nnzN) {
+  return rmcl_prune_abi<double>(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
+}
+extern "C" int hip_rmcl_prune_n_f64(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const double* dC,
+                                    int** dIN, int** dJN, double** dCN, int* nnzN) {
+  return nnz < 0 ? fail(SPGEMM_ERR_ARG, "negative nnz") : rmcl_prune_abi<double>(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
 }
 
 // Expansion and prune of one R-MCL iteration as ONE operator: C = A*B is never materialised.  Every numeric kernel
@@ -2097,7 +2138,7 @@ static int rmcl_pack_rows(spgemm_handle* h, int m, const CsrView& R, DevCSR* out
   if (N.alloc_entries(N.nnz)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
   if (N.nnz > 0 && m > 0) {
     const RowLanes rl = row_lanes(h, m, 0);          // always the 16-lane form
-    RMCL_ROWS(k_rmcl_move, rl, s, m, R.I, N.I.p, R.J, R.V, N.J.p, N.V.p);
+    RMCL_ROWS(k_rmcl_move, float, rl, s, m, R.I, N.I.p, R.J, R.V, N.J.p, N.V.p);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail(SPGEMM_ERR_HIP, "pack: move");
   }
   *out = std::move(N);
@@ -2111,12 +2152,20 @@ enum { RMCL_EXTENTS = 0, RMCL_PACK = 1, RMCL_BLOCK = 2 };
 
 static int rmcl_hipfail(const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl expand+prune: %s: %s", what, hipGetErrorString(hipGetLastError())); }
 
+// Products beyond which the scratch C is not made and the step runs as SpGEMM + prune.  SPGEMM_RMCL_MAXP lowers the bound
+// (test hook: the give-up path, in the float loop behind an unpacked Mt, on small inputs).
+static unsigned long long rmcl_max_products() {
+  unsigned long long maxP = 1ull << 30;
+  if (const char* e = getenv("SPGEMM_RMCL_MAXP")) maxP = std::min<unsigned long long>(maxP, strtoull(e, nullptr, 10));
+  return maxP;
+}
+
 // Give-up route (no rows, no products, or a product too large for the scratch C): SpGEMM + prune, an unpacked B packed first.
 static int rmcl_two_steps(spgemm_handle* h, const CsrView& A, CsrView B, int m, int k, int n, DevCSR* out) {
   DevCSR Bp, C;
   if (B.len) { CHK(rmcl_pack_rows(h, k, B, &Bp)); B = Bp.view(); }
   CHK(spgemm_device(h, {A.I, A.J, A.V, A.nnz, B.I, B.J, B.V, m, k, n}, B.nnz, nullptr, {&C.I.p, &C.J.p, &C.V.p, &C.nnz}));
-  return rmcl_prune_impl(h, m, C.nnz, C.I, C.J, C.V, out);
+  return rmcl_prune_impl<float>(h, m, C.nnz, C.I, C.J, C.V, out);
 }
 
 // Classification of the rows by their products into `mid`; C gets its row-start and kept-count arrays (m + 1 each).
@@ -2189,12 +2238,13 @@ static int rmcl_leave_extents(spgemm_handle* h, int m, const HostMirror& mid, De
 
 // Finish 3 (finish 2, the block form, is the scratch C as it stands): the kept entries move into packed arrays, the
 // scanned counts become the row pointer and the scratch C goes back to the pool.
-static int rmcl_pack_result(spgemm_handle* h, int m, int nz, DevCSR* C) {
-  DevCSR N;
+template <class V>
+static int rmcl_pack_result(spgemm_handle* h, int m, int nz, DevCSRT<V>* C) {
+  DevCSRT<V> N;
   if (N.alloc_entries(nz)) return rmcl_hipfail("device allocation failed");
   if (nz > 0) {
     const RowLanes rl = row_lanes(h, m, nz);
-    RMCL_ROWS(k_rmcl_move, rl, h->stream, m, C->I.p, C->len.p, C->J.p, C->V.p, N.J.p, N.V.p);
+    RMCL_ROWS(k_rmcl_move, V, rl, h->stream, m, C->I.p, C->len.p, C->J.p, C->V.p, N.J.p, N.V.p);
     if (hipGetLastError() != hipSuccess) return drained(h->stream, rmcl_hipfail("move launch"));   // N goes before the caller drains
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess) return drained(h->stream, rmcl_hipfail("move"));
@@ -2218,11 +2268,7 @@ static int rmcl_expand_prune_core(spgemm_handle* h, const CsrView& A, const CsrV
   HostMirror mid;
   int rc = rmcl_classify(h, A, B, m, &C, &mid, errPending);
   if (rc) return drained(s, rc);
-  // products beyond which the scratch C (8 bytes per product) is not made and the step runs as SpGEMM + prune.
-  // SPGEMM_RMCL_MAXP lowers the bound (test hook: the give-up path behind an unpacked Mt on small inputs).
-  unsigned long long maxP = 1ull << 30;
-  if (const char* e = getenv("SPGEMM_RMCL_MAXP")) maxP = std::min<unsigned long long>(maxP, strtoull(e, nullptr, 10));
-  if (mid.totalP == 0 || mid.totalP > maxP) {
+  if (mid.totalP == 0 || mid.totalP > rmcl_max_products()) {   // (the scratch C takes 8 bytes per product)
     if (hipStreamSynchronize(s) != hipSuccess) return drained(s, rmcl_hipfail("classification"));
     C.reset();
     return rmcl_two_steps(h, A, B, m, k, n, out);
@@ -2257,15 +2303,26 @@ static int rmcl_expand_prune_core(spgemm_handle* h, const CsrView& A, const CsrV
 extern "C" int hip_rmcl_expand_prune(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
                                      const int* dIB, const int* dJB, const float* dB, int nnzB, int m, int k, int n,
                                      int** dIN, int** dJN, float** dCN, int* nnzN) {
-  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
-  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
-  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
-  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
+  CHK(rmcl_step_args(dIA, dJA, dA, nnzA, dIB, dJB, dB, nnzB, m, k, n, dIN, dJN, dCN, nnzN));
   if (!h) CHK(default_handle(&h));
   DevCSR N;
   CHK(rmcl_expand_prune_core(h, {dIA, dJA, dA, nnzA}, {dIB, dJB, dB, nnzB}, m, k, n, RMCL_PACK, &N));
   N.give(dIN, dJN, dCN, nnzN);
+  return SPGEMM_OK;
+}
+
+// maxIter == 0: the loop's result is a copy of Mt
+template <class V>
+static int rmcl_copy_of_mt(hipStream_t s, int rows, const int* dtI, const int* dtJ, const V* dtA, int tnnz, DevCSRT<V>* out) {
+  DevCSRT<V> N;
+  if (N.I.alloc((size_t)rows + 1) || N.alloc_entries(tnnz)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
+  if (hipMemcpyAsync(N.I, dtI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      (tnnz > 0 && (hipMemcpyAsync(N.J, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                    hipMemcpyAsync(N.V, dtA, sizeof(V) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess)) ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return drained(s, fail(SPGEMM_ERR_HIP, "copy of Mt"));
+  N.nnz = tnnz;
+  *out = std::move(N);
   return SPGEMM_OK;
 }
 
@@ -2277,11 +2334,7 @@ extern "C" int hip_rmcl_expand_prune(spgemm_handle* h, const int* dIA, const int
 extern "C" int hip_gpuRmclIter_device(spgemm_handle* h, int maxIter, int rows, int cols, const int* dgI, const int* dgJ,
                                       const float* dgA, int gnnz, const int* dtI, const int* dtJ, const float* dtA,
                                       int tnnz, int** oI, int** oJ, float** oA, int* onnz) {
-  if (!oI || !oJ || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *oI = nullptr; *oJ = nullptr; *oA = nullptr; *onnz = 0;
-  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
-  CHK(check_common(dgI, dgJ, dgA, gnnz, "Mgt"));
-  CHK(check_common(dtI, dtJ, dtA, tnnz, "Mt"));
+  CHK(rmcl_loop_args(maxIter, rows, cols, dgI, dgJ, dgA, gnnz, dtI, dtJ, dtA, tnnz, oI, oJ, oA, onnz));
   if (!h) CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
   const bool keep_packed = getenv("SPGEMM_RMCL_PACK") != nullptr;       // A/B switch: pack after every iteration
@@ -2298,14 +2351,8 @@ extern "C" int hip_gpuRmclIter_device(spgemm_handle* h, int maxIter, int rows, i
     old.park(std::move(cur));                        // that call waited behind the readers of the Mt parked before
     cur = std::move(next);
   }                                                  // (the last iteration packs and waits for everything)
-  if (maxIter == 0) {                                // a copy of Mt
-    if (cur.I.alloc((size_t)rows + 1) || cur.alloc_entries(tnnz)) return drained(s, fail(SPGEMM_ERR_NOMEM, "device allocation failed"));
-    if (hipMemcpyAsync(cur.I, dtI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        (tnnz > 0 && (hipMemcpyAsync(cur.J, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                      hipMemcpyAsync(cur.V, dtA, sizeof(float) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess)) ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return drained(s, fail(SPGEMM_ERR_HIP, "copy of Mt"));
-    cur.nnz = tnnz;
+  if (maxIter == 0) {
+    CHK(rmcl_copy_of_mt(s, rows, dtI, dtJ, dtA, tnnz, &cur));
   } else if (!cur.packed()) {                        // the last iteration gave up on the fused step?  it returns packed: not reached
     return drained(s, fail(SPGEMM_ERR_INTERNAL, "the last iteration returned an unpacked matrix"));
   }
@@ -2313,8 +2360,51 @@ extern "C" int hip_gpuRmclIter_device(spgemm_handle* h, int maxIter, int rows, i
   return SPGEMM_OK;
 }
 
+// ---- hip_gpuRmclIter[_f64] on one device: host arrays in, the device loop on the default handle, malloc()ed arrays out ----
+// Host CSR -> pool blocks on the current device; arrays without entries get their (never empty) blocks and no copy.
+template <class V>
+static int csr_to_device(const int* I, const int* J, const V* A, int rows, int nnz, DevCSRT<V>* M) {
+  auto up = [](auto& buf, const auto* src, size_t n) {
+    const int rc = spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * std::max<size_t>(n, 1));
+    return rc || n == 0 ? rc : spgemm_hip_memcpy_h2d(buf.p, src, sizeof(*src) * n);
+  };
+  M->nnz = nnz;
+  int rc;
+  if ((rc = up(M->I, I, (size_t)rows + 1)) || (rc = up(M->J, J, (size_t)nnz)) || (rc = up(M->V, A, (size_t)nnz))) return rc;
+  return SPGEMM_OK;
+}
+// A packed device CSR -> malloc()ed host arrays (never of size zero); the caller free()s them.
+template <class V>
+static int csr_to_host(const DevCSRT<V>& N, int rows, int** oI, int** oJ, V** oA, int* onnz) {
+  int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
+  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(N.nnz, 1));
+  V* hA = (V*)malloc(sizeof(V) * (size_t)std::max(N.nnz, 1));
+  int rc = SPGEMM_OK;
+  if (!hI || !hJ || !hA) rc = fail(SPGEMM_ERR_NOMEM, "host malloc failed");
+  else if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) == SPGEMM_OK && N.nnz > 0 &&
+           (rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) == SPGEMM_OK)
+    rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(V) * (size_t)N.nnz);
+  if (rc) { free(hI); free(hJ); free(hA); return rc; }
+  *oI = hI; *oJ = hJ; *oA = hA; *onnz = N.nnz;
+  return SPGEMM_OK;
+}
+// loop: hip_gpuRmclIter_device or its _f64 twin
+template <class V, class Loop>
+static int rmcl_iter_host(Loop loop, int maxIter, int rows, const int* gIA, const int* gJA, const V* gA, int gnnz, const int* tIA,
+                          const int* tJA, const V* tA, int tnnz, int** oIA, int** oJA, V** oA, int* onnz) {
+  spgemm_handle* h = nullptr;
+  CHK(default_handle(&h));
+  HIPCHK(hipSetDevice(h->device));
+  DevCSRT<V> Mg, Mt, N;
+  CHK(csr_to_device(gIA, gJA, gA, rows, gnnz, &Mg));
+  CHK(csr_to_device(tIA, tJA, tA, rows, tnnz, &Mt));
+  CHK(loop(h, maxIter, rows, rows, Mg.I, Mg.J, Mg.V, gnnz, Mt.I, Mt.J, Mt.V, tnnz, &N.I.p, &N.J.p, &N.V.p, &N.nnz));
+  Mt.reset();
+  return csr_to_host(N, rows, oIA, oJA, oA, onnz);
+}
+
 struct spgemm_group;
-static std::mutex g_rmcl_group_mu;                     // the group hip_gpuRmclIter keeps between calls (same device layout)
+static std::mutex g_rmcl_group_mu;                    // the group hip_gpuRmclIter keeps between calls (same device layout)
 static spgemm_group* g_rmcl_group = nullptr;
 static std::vector<int> g_rmcl_group_devs;
 static int g_rmcl_devices_used = 1;
@@ -2329,10 +2419,7 @@ extern "C" int hip_gpuRmclIter_sharded(spgemm_group* g, int maxIter, int rows, i
 extern "C" int hip_gpuRmclIter(int maxIter, int rows, int cols, const int* gIA, const int* gJA, const float* gA, int gnnz,
                                const int* tIA, const int* tJA, const float* tA, int tnnz, int** oIA, int** oJA,
                                float** oA, int* onnz) {
-  if (!oIA || !oJA || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
-  CHK(check_common(gIA, gJA, gA, gnnz, "Mgt"));
-  CHK(check_common(tIA, tJA, tA, tnnz, "Mt"));
+  CHK(rmcl_loop_args(maxIter, rows, cols, gIA, gJA, gA, gnnz, tIA, tJA, tA, tnnz, oIA, oJA, oA, onnz));
   CHK(validate_host_csr(gIA, gJA, rows, cols, gnnz, "Mgt"));
   CHK(validate_host_csr(tIA, tJA, rows, cols, tnnz, "Mt"));
   {
@@ -2369,126 +2456,28 @@ extern "C" int hip_gpuRmclIter(int maxIter, int rows, int cols, const int* gIA, 
       fprintf(stderr, "hip_gpuRmclIter: the %d-shard loop failed (%s); running on one device\n", shards, spgemm_hip_last_error());
     }
   }
-  spgemm_handle* h = nullptr;
-  CHK(default_handle(&h));
-  DevCSR Mg, Mt, N;
-  auto up = [](auto& buf, const auto* src, size_t n) {
-    const int rc = spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * n);
-    return rc ? rc : spgemm_hip_memcpy_h2d(buf.p, src, sizeof(*src) * n);
-  };
-  int rc;
-  if ((rc = up(Mg.I, gIA, (size_t)rows + 1)) || (rc = up(Mg.J, gJA, (size_t)gnnz)) || (rc = up(Mg.V, gA, (size_t)gnnz)) ||
-      (rc = up(Mt.I, tIA, (size_t)rows + 1)) || (rc = up(Mt.J, tJA, (size_t)tnnz)) || (rc = up(Mt.V, tA, (size_t)tnnz)))
-    return rc;
-  CHK(hip_gpuRmclIter_device(h, maxIter, rows, cols, Mg.I, Mg.J, Mg.V, gnnz, Mt.I, Mt.J, Mt.V, tnnz, &N.I.p, &N.J.p, &N.V.p, &N.nnz));
-  Mt.reset();
-  int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
-  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(N.nnz, 1));
-  float* hA = (float*)malloc(sizeof(float) * (size_t)std::max(N.nnz, 1));
-  if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return fail(SPGEMM_ERR_NOMEM, "host malloc failed"); }
-  if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) ||
-      (rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) ||
-      (rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(float) * (size_t)N.nnz))) { free(hI); free(hJ); free(hA); return rc; }
-  *oIA = hI; *oJA = hJ; *oA = hA; *onnz = N.nnz;
-  return SPGEMM_OK;
+  return rmcl_iter_host<float>(hip_gpuRmclIter_device, maxIter, rows, gIA, gJA, gA, gnnz, tIA, tJA, tA, tnnz, oIA, oJA, oA, onnz);
 }
 
 // ------------------------------------------------------------------------------------------------
-// R-MCL with double values (rmcl_f64_device.hpp): prune, fused step, loop on one device.  The float path's structure with
-// two differences: the symbolic pass always runs (the f64 tables are sized from the exact L_i), so the scratch C has
-// nnz(C) entries, not one per product; and every step leaves a packed matrix (the unpacked {start, kept} layout of the
-// float loop is not carried over).
+// R-MCL with double values: fused step and loop on one device (the prune, the entry points' checks and the host copies
+// are the templates above).  The float path's structure with two differences: the symbolic pass always runs (the f64
+// tables are sized from the exact L_i), so the scratch C has nnz(C) entries, not one per product; and every step leaves
+// a packed matrix (the unpacked {start, kept} layout of the float loop is not carried over).
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct DevCSR64 {                                      // a packed device matrix with double values that owns its pool blocks
-  DevBuf<int> I, J; DevBuf<double> V;
-  int nnz = 0;
-  hipError_t alloc_entries(long long n) {              // (J, V) for n entries; never a zero-sized block
-    const hipError_t e = J.alloc((size_t)std::max(n, 1ll));
-    return e != hipSuccess ? e : V.alloc((size_t)std::max(n, 1ll));
-  }
-  void reset() { *this = DevCSR64(); }
-  void give(int** oI, int** oJ, double** oV, int* onnz) {
-    *oI = I.release(); *oJ = J.release(); *oV = V.release(); *onnz = nnz;
-    reset();
-  }
-};
-}  // namespace
-
-static int rmcl_prune64_impl(spgemm_handle* h, int m, long long nnzIn, const int* dIC, const int* dJC, const double* dC, DevCSR64* out) {
-  out->reset();
-  if (m < 0 || !dIC) return fail(SPGEMM_ERR_ARG, "bad argument");
-  if (!h) CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  h->sym_m = -1;                                   // scan scratch and the small device block are shared with a pending phase
-  clear_stale_hip_error();
-  CHK(ws_ensure(h, m));
-  DevCSR64 N;
-  DevBuf<double> th, ks;
-  auto hipfail = [&](const char* what) { return fail(SPGEMM_ERR_HIP, "rmcl prune (f64): %s: %s", what, hipGetErrorString(hipGetLastError())); };
-  if (N.I.alloc((size_t)m + 1) || th.alloc((size_t)std::max(m, 1)) || ks.alloc((size_t)std::max(m, 1))) return hipfail("device allocation failed");
-  hipStream_t s = h->stream;
-  if (hipMemsetAsync(&h->dsmall->nnzC64, 0, sizeof(unsigned long long), s) != hipSuccess) return hipfail("memset");
-  if (m > 0 && nnzIn < 0) {
-    int tmp = 0;
-    if (hipMemcpyAsync(&tmp, dIC + m, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return hipfail("reading nnz");
-    nnzIn = tmp;
-  }
-  const RowLanes rl = row_lanes(h, m, nnzIn);
-  if (m > 0) {
-    RMCL_ROWS(k_rmcl_stats64, rl, s, m, dIC, dC, N.I.p, th.p, ks.p);
-    if (int rc = launch_scan(h, N.I, m, &h->dsmall->nnzC64)) return drained(s, rc);
-  } else {
-    hipMemsetAsync(N.I, 0, sizeof(int), s);
-  }
-  if (hipMemcpyAsync(&h->hsmall->nnzC64, &h->dsmall->nnzC64, sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return drained(s, hipfail("kept-entry count"));
-  N.nnz = (int)h->hsmall->nnzC64;
-  if (N.alloc_entries(N.nnz)) return hipfail("device allocation failed");
-  if (m > 0 && N.nnz > 0) {
-    RMCL_ROWS(k_rmcl_compact64, rl, s, m, dIC, dJC, dC, N.I.p, th.p, ks.p, N.J.p, N.V.p);
-    if (hipGetLastError() != hipSuccess) return drained(s, hipfail("compaction launch"));
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return drained(s, hipfail("compaction"));
-  *out = std::move(N);
-  return SPGEMM_OK;
-}
-
-static int rmcl_prune64_abi(spgemm_handle* h, int m, long long nnz, const int* dIC, const int* dJC, const double* dC, int** dIN,
-                            int** dJN, double** dCN, int* nnzN) {
-  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
-  DevCSR64 N;
-  CHK(rmcl_prune64_impl(h, m, nnz, dIC, dJC, dC, &N));
-  N.give(dIN, dJN, dCN, nnzN);
-  return SPGEMM_OK;
-}
-
-extern "C" int hip_rmcl_prune_f64(spgemm_handle* h, int m, const int* dIC, const int* dJC, const double* dC, int** dIN,
-                                  int** dJN, double** dCN, int* nnzN) {
-  return rmcl_prune64_abi(h, m, -1, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
-}
-
-extern "C" int hip_rmcl_prune_n_f64(spgemm_handle* h, int m, int nnz, const int* dIC, const int* dJC, const double* dC,
-                                    int** dIN, int** dJN, double** dCN, int* nnzN) {
-  if (nnz < 0) return fail(SPGEMM_ERR_ARG, "negative nnz");
-  return rmcl_prune64_abi(h, m, nnz, dIC, dJC, dC, dIN, dJN, dCN, nnzN);
-}
+using DevCSR64 = DevCSRT<double>;
 
 // Give-up route (no rows, no products, or a product beyond the cap): hip_gpuSpMM_f64 + prune.
 static int rmcl_two_steps64(spgemm_handle* h, const Product<double>& p, int nnzB, DevCSR64* out) {
   DevCSR64 C;
   CHK(hip_gpuSpMM_f64(h, p.IA, p.JA, p.A, p.nnzA, p.IB, p.JB, p.B, nnzB, p.m, p.k, p.n, &C.I.p, &C.J.p, &C.V.p, &C.nnz));
-  return rmcl_prune64_impl(h, p.m, C.nnz, C.I, C.J, C.V, out);
+  return rmcl_prune_impl<double>(h, p.m, C.nnz, C.I, C.J, C.V, out);
 }
 
 // One R-MCL iteration in double, *out = prune(A * B), packed: shared classification, symbolic pass and scan (the int32
 // refusal and the error word are hip_gpuSpMM_f64's), a scratch C of nnz(C) entries, the f64 numeric launches with the row
-// rule in their epilogues (+ k_rmcl_fix_rows64 for the rows that do not finish in one LDS table), the scan of the kept
-// counts and k_rmcl_move64.  Arguments are checked by the callers.
+// rule in their epilogues (+ k_rmcl_fix_rows<double> for the rows that do not finish in one LDS table), the scan of the kept
+// counts and rmcl_pack_result.  Arguments are checked by the callers.
 static int rmcl_expand_prune64_core(spgemm_handle* h, const Product<double>& p, int nnzB, DevCSR64* out) {
   out->reset();
   HIPCHK(hipSetDevice(h->device));
@@ -2496,58 +2485,41 @@ static int rmcl_expand_prune64_core(spgemm_handle* h, const Product<double>& p, 
   CHK(ws_ensure(h, p.m));
   hipStream_t s = h->stream;
   const int m = p.m;
-  DevCSR64 C;                                          // the scratch product: row starts of the full rows, nnz(C) slots
-  DevBuf<int> cnt;                                     // kept entries per row, then their scan = the result's row pointer
-  if (C.I.alloc((size_t)m + 1) || cnt.alloc((size_t)m + 1)) return rmcl_hipfail("device allocation failed");
+  DevCSR64 C;                                          // the scratch product: row starts of the full rows, nnz(C) slots;
+  if (C.I.alloc((size_t)m + 1) || C.len.alloc((size_t)m + 1)) return rmcl_hipfail("device allocation failed");   // len: kept per row
   int nnzC = 0;
   int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, m, p.k, p.n, nullptr, C.I, &nnzC, false);
   h->sym_m = -1;                                       // the phase is finished here, not by hip_spgemm_numeric_f64
   if (rc) return drained(s, rc);
   const unsigned long long P = h->mirror.totalP;
-  unsigned long long maxP = 1ull << 30;                // the float step's cap and its test hook
-  if (const char* e = getenv("SPGEMM_RMCL_MAXP")) maxP = std::min<unsigned long long>(maxP, strtoull(e, nullptr, 10));
-  if (P == 0 || P > maxP) {
-    C.reset(); cnt.reset();                            // (symbolic_phase waited for the stream)
+  if (P == 0 || P > rmcl_max_products()) {             // the float step's cap and its test hook
+    C.reset();                                         // (symbolic_phase waited for the stream)
     return rmcl_two_steps64(h, p, nnzB, out);
   }
-  if (hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return drained(s, rmcl_hipfail("memset"));
+  if (hipMemsetAsync(C.len, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return drained(s, rmcl_hipfail("memset"));
   if (C.alloc_entries(nnzC)) return drained(s, rmcl_hipfail("device allocation of the scratch product failed"));
   int* scratch[2] = {nullptr, nullptr};                // the numeric launch's probe words and device-memory tables
   auto done = [&](int r) { r = drained(s, r); pool().release(scratch[0]); pool().release(scratch[1]); return r; };
   hipEventRecord(h->ev[4], s);
-  if (nnzC > 0 && (rc = launch_numeric_f64(h, p.IA, p.A, p.JB, p.B, h->cur_rowIds, h->mirror.binPtr, C.I, C.J, C.V, scratch, cnt)))
+  if (nnzC > 0 && (rc = launch_numeric_f64(h, p.IA, p.A, p.JB, p.B, h->cur_rowIds, h->mirror.binPtr, C.I, C.J, C.V, scratch, C.len)))
     return done(rc);
   hipEventRecord(h->ev[5], s);
-  if ((rc = launch_scan(h, cnt, m, &h->dsmall->kept64))) return done(rc);
+  if ((rc = launch_scan(h, C.len, m, &h->dsmall->kept64))) return done(rc);
   if ((rc = read_mirror(h, "rmcl expand+prune (f64)"))) return done(rc);
   done(SPGEMM_OK);                                     // (read_mirror waited for the stream)
   spgemm_stats& st = h->stats;
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
   collect_kernel_times(h, false);
-  const int kept = (int)h->mirror.kept64;              // <= nnz(C) < 2^31
-  DevCSR64 N;
-  if (N.alloc_entries(kept)) return rmcl_hipfail("device allocation failed");
-  if (kept > 0) {
-    const RowLanes rl = row_lanes(h, m, kept);
-    RMCL_ROWS(k_rmcl_move64, rl, s, m, C.I.p, cnt.p, C.J.p, C.V.p, N.J.p, N.V.p);
-    if (hipGetLastError() != hipSuccess) return drained(s, rmcl_hipfail("move launch"));
-  }
-  if (hipStreamSynchronize(s) != hipSuccess) return drained(s, rmcl_hipfail("move"));
-  N.I = std::move(cnt);
-  N.nnz = kept;
-  *out = std::move(N);
+  CHK(rmcl_pack_result(h, m, (int)h->mirror.kept64, &C));   // kept <= nnz(C) < 2^31; the scanned counts become the row pointer
+  *out = std::move(C);
   return SPGEMM_OK;
 }
 
 extern "C" int hip_rmcl_expand_prune_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
                                          const int* dIB, const int* dJB, const double* dB, int nnzB, int m, int k, int n,
                                          int** dIN, int** dJN, double** dCN, int* nnzN) {
-  if (!dIN || !dJN || !dCN || !nnzN) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *dIN = nullptr; *dJN = nullptr; *dCN = nullptr; *nnzN = 0;
-  if (m < 0 || k < 0 || n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", m, k, n);
-  CHK(check_common(dIA, dJA, dA, nnzA, "A"));
-  CHK(check_common(dIB, dJB, dB, nnzB, "B"));
+  CHK(rmcl_step_args(dIA, dJA, dA, nnzA, dIB, dJB, dB, nnzB, m, k, n, dIN, dJN, dCN, nnzN));
   if (!h) CHK(default_handle(&h));
   DevCSR64 N;
   CHK(rmcl_expand_prune64_core(h, {dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n}, nnzB, &N));
@@ -2560,11 +2532,7 @@ extern "C" int hip_rmcl_expand_prune_f64(spgemm_handle* h, const int* dIA, const
 extern "C" int hip_gpuRmclIter_device_f64(spgemm_handle* h, int maxIter, int rows, int cols, const int* dgI, const int* dgJ,
                                           const double* dgA, int gnnz, const int* dtI, const int* dtJ, const double* dtA,
                                           int tnnz, int** oI, int** oJ, double** oA, int* onnz) {
-  if (!oI || !oJ || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *oI = nullptr; *oJ = nullptr; *oA = nullptr; *onnz = 0;
-  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
-  CHK(check_common(dgI, dgJ, dgA, gnnz, "Mgt"));
-  CHK(check_common(dtI, dtJ, dtA, tnnz, "Mt"));
+  CHK(rmcl_loop_args(maxIter, rows, cols, dgI, dgJ, dgA, gnnz, dtI, dtJ, dtA, tnnz, oI, oJ, oA, onnz));
   if (!h) CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
   hipStream_t s = h->stream;
@@ -2575,15 +2543,7 @@ extern "C" int hip_gpuRmclIter_device_f64(spgemm_handle* h, int maxIter, int row
     if (int rc = rmcl_expand_prune64_core(h, p, it ? cur.nnz : tnnz, &next)) return drained(s, rc);
     cur = std::move(next);                             // (every step waits for its kernels: the old Mt is idle)
   }
-  if (maxIter == 0) {                                  // a copy of Mt
-    if (cur.I.alloc((size_t)rows + 1) || cur.alloc_entries(tnnz)) return fail(SPGEMM_ERR_NOMEM, "device allocation failed");
-    if (hipMemcpyAsync(cur.I, dtI, sizeof(int) * ((size_t)rows + 1), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        (tnnz > 0 && (hipMemcpyAsync(cur.J, dtJ, sizeof(int) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                      hipMemcpyAsync(cur.V, dtA, sizeof(double) * (size_t)tnnz, hipMemcpyDeviceToDevice, s) != hipSuccess)) ||
-        hipStreamSynchronize(s) != hipSuccess)
-      return drained(s, fail(SPGEMM_ERR_HIP, "copy of Mt"));
-    cur.nnz = tnnz;
-  }
+  if (maxIter == 0) CHK(rmcl_copy_of_mt(s, rows, dtI, dtJ, dtA, tnnz, &cur));
   cur.give(oI, oJ, oA, onnz);
   return SPGEMM_OK;
 }
@@ -2592,35 +2552,10 @@ extern "C" int hip_gpuRmclIter_device_f64(spgemm_handle* h, int maxIter, int row
 extern "C" int hip_gpuRmclIter_f64(int maxIter, int rows, int cols, const int* gIA, const int* gJA, const double* gA, int gnnz,
                                    const int* tIA, const int* tJA, const double* tA, int tnnz, int** oIA, int** oJA,
                                    double** oA, int* onnz) {
-  if (!oIA || !oJA || !oA || !onnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
-  *oIA = nullptr; *oJA = nullptr; *oA = nullptr; *onnz = 0;
-  if (rows < 0 || cols != rows || maxIter < 0) return fail(SPGEMM_ERR_ARG, "R-MCL needs a square matrix and maxIter >= 0");
-  CHK(check_common(gIA, gJA, gA, gnnz, "Mgt"));
-  CHK(check_common(tIA, tJA, tA, tnnz, "Mt"));
+  CHK(rmcl_loop_args(maxIter, rows, cols, gIA, gJA, gA, gnnz, tIA, tJA, tA, tnnz, oIA, oJA, oA, onnz));
   CHK(validate_host_csr(gIA, gJA, rows, cols, gnnz, "Mgt"));
   CHK(validate_host_csr(tIA, tJA, rows, cols, tnnz, "Mt"));
-  spgemm_handle* h = nullptr;
-  CHK(default_handle(&h));
-  HIPCHK(hipSetDevice(h->device));
-  DevCSR64 Mg, Mt, N;
-  auto up = [](auto& buf, const auto* src, size_t n) {
-    const int rc = spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * std::max<size_t>(n, 1));
-    return rc || n == 0 ? rc : spgemm_hip_memcpy_h2d(buf.p, src, sizeof(*src) * n);
-  };
-  int rc;
-  if ((rc = up(Mg.I, gIA, (size_t)rows + 1)) || (rc = up(Mg.J, gJA, (size_t)gnnz)) || (rc = up(Mg.V, gA, (size_t)gnnz)) ||
-      (rc = up(Mt.I, tIA, (size_t)rows + 1)) || (rc = up(Mt.J, tJA, (size_t)tnnz)) || (rc = up(Mt.V, tA, (size_t)tnnz)))
-    return rc;
-  CHK(hip_gpuRmclIter_device_f64(h, maxIter, rows, cols, Mg.I, Mg.J, Mg.V, gnnz, Mt.I, Mt.J, Mt.V, tnnz, &N.I.p, &N.J.p, &N.V.p, &N.nnz));
-  int* hI = (int*)malloc(sizeof(int) * ((size_t)rows + 1));
-  int* hJ = (int*)malloc(sizeof(int) * (size_t)std::max(N.nnz, 1));
-  double* hA = (double*)malloc(sizeof(double) * (size_t)std::max(N.nnz, 1));
-  if (!hI || !hJ || !hA) { free(hI); free(hJ); free(hA); return fail(SPGEMM_ERR_NOMEM, "host malloc failed"); }
-  if ((rc = spgemm_hip_memcpy_d2h(hI, N.I, sizeof(int) * ((size_t)rows + 1))) ||
-      (N.nnz > 0 && ((rc = spgemm_hip_memcpy_d2h(hJ, N.J, sizeof(int) * (size_t)N.nnz)) ||
-                     (rc = spgemm_hip_memcpy_d2h(hA, N.V, sizeof(double) * (size_t)N.nnz))))) { free(hI); free(hJ); free(hA); return rc; }
-  *oIA = hI; *oJA = hJ; *oA = hA; *onnz = N.nnz;
-  return SPGEMM_OK;
+  return rmcl_iter_host<double>(hip_gpuRmclIter_device_f64, maxIter, rows, gIA, gJA, gA, gnnz, tIA, tJA, tA, tnnz, oIA, oJA, oA, onnz);
 }
 
 // ------------------------------------------------------------------------------------------------

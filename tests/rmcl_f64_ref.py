@@ -81,8 +81,9 @@ class Step64:
         self.bound = step_bound(N, n)
 
 
-def step_bound(N, n):
-    return (8 * int(N) + 2 * int(n) + 16) * EPS64
+def step_bound(N, n, u=EPS64):
+    """the value bound above; u = the unit roundoff of the device's value type (2^-24 for the float kernels)"""
+    return (8 * int(N) + 2 * int(n) + 16) * u
 
 
 def step64(Mgt, Mt):

@@ -198,8 +198,8 @@ def test_fused_step_wide_rows(handle):
     precondition([step], step.bound, "wide")
     L = np.diff(step.product.rowPtr)
     assert len(strict_subset_rows(step, 4097, F64_LDS_MAXL)) > 0          # one LDS pass of bin 8
-    assert len(strict_subset_rows(step, F64_LDS_MAXL + 1, 65536)) > 0     # several passes: k_rmcl_fix_rows64
-    assert len(strict_subset_rows(step, 65537, 1 << 30)) > 0              # device-memory table: k_rmcl_fix_rows64
+    assert len(strict_subset_rows(step, F64_LDS_MAXL + 1, 65536)) > 0     # several passes: k_rmcl_fix_rows<double>
+    assert len(strict_subset_rows(step, 65537, 1 << 30)) > 0              # device-memory table: k_rmcl_fix_rows<double>
     assert L.max() > 65536
     assert_step(fused(handle, A, B), step.kept, step.bound, "wide")
 
