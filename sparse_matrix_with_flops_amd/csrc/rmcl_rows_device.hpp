@@ -9,18 +9,15 @@
 //   k_rmcl_move<L, V>                           packs the fronts of the scratch rows into the result CSR
 //   k_zip_extents                               {start, end} of every scratch row (the float loop's unpacked Mt)
 //
-// What differs by type stays in the overload sets of spgemm_device.hpp (float) and rmcl_f64_device.hpp (double):
-// rmcl_threshold (the float one keeps the reference's promotions) and rowL_sum / rowL_max (the double ones move two 32-bit
-// halves by DPP).  Sums are L-lane tree reductions in V, so a value that sits within an ulp of the threshold can fall on
+// What differs by type are two overload sets of spgemm_device.hpp, shared with the fused epilogues of the numeric kernels:
+// rmcl_threshold (the float one keeps the reference's promotions) and the lane moves under rowL_sum / rowL_max (a double
+// crosses lanes as two 32-bit halves).  Sums are L-lane tree reductions in V, so a value that sits within an ulp of the threshold can fall on
 // the other side than in the sequential CPU loop (the reference's own GPU path has the same property).
 #pragma once
-#include "rmcl_f64_device.hpp"
+#include "spgemm_device.hpp"
 #include <type_traits>
 
 namespace smf {
-
-__device__ __forceinline__ float rmcl_max(float a, float b) { return fmaxf(a, b); }
-__device__ __forceinline__ double rmcl_max(double a, double b) { return fmax(a, b); }
 
 // pass 1: inflate (squares, recomputed where needed, never stored), per-row threshold and kept sum, kept count ->
 // cnt[row].  L lanes per row: 16 for short rows, a whole wave once rows average ~100 entries (R-MCL products do);

@@ -462,6 +462,8 @@ __device__ __forceinline__ void emit_claimed(const slot_t* tab, int base, int pe
 // ------------------------------------------------------------------------------------------------
 // R-MCL row rule (CPU: nlibs/tools/util.cc:4-69; reference GPU: nlibs/gpus/dutil.cuh:8-80): inflate (square), max,
 // sum, thresh = clamp(0.9*avg*(1-2(max-avg)), 1e-7, max), keep v >= thresh, divide the kept values by their sum.
+// Written once for both value types V = float, double (the reference's QValue); what differs by type is the threshold's
+// arithmetic, how one value crosses lanes, and how a row's table is laid out in LDS (RowTab<V>).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float rmcl_threshold(float avg, float mx) {
   float ret = (float)(0.90 * avg * (1 - 2 * (mx - avg)));       // same promotions as computeThreshold (util.cc:4-9)
@@ -469,148 +471,262 @@ __device__ __forceinline__ float rmcl_threshold(float avg, float mx) {
   ret = (ret > mx) ? mx : ret;
   return ret;
 }
+__device__ __forceinline__ double rmcl_threshold(double avg, double mx) {
+  double ret = 0.90 * avg * (1 - 2 * (mx - avg));               // computeThreshold with QValue = double: nothing to promote
+  ret = (ret > 1.0e-7) ? ret : 1.0e-7;
+  ret = (ret > mx) ? mx : ret;
+  return ret;
+}
+__device__ __forceinline__ float rmcl_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ double rmcl_max(double a, double b) { return fmax(a, b); }
+
+// one value across lanes: by DPP control CTRL inside a 16-lane row, or read from lane l.  A float is one 32-bit move; a
+// double travels as its two halves (gfx950 has no 64-bit DPP operand for these controls, and __shfl_xor of a double is two
+// ds_bpermute_b32 plus the address VALU and a wait on the LDS queue, which the fused epilogues read their tables through).
+template <int CTRL> __device__ __forceinline__ float lane_dpp(float v) {
+  return __int_as_float(SMF_DPP(__float_as_int(v), CTRL, 0xf, 0));
+}
+template <int CTRL> __device__ __forceinline__ double lane_dpp(double v) {
+  const int lo = SMF_DPP(__double2loint(v), CTRL, 0xf, 0), hi = SMF_DPP(__double2hiint(v), CTRL, 0xf, 0);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ float lane_read(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+__device__ __forceinline__ double lane_read(double v, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 
 // all-reduce inside the L lanes that share a row (L = 16: one DPP row; L = 64: the wave).  DPP butterflies (xor 1, xor 2,
-// half-row mirror, row mirror): four VALU ops for 16 lanes and no LDS round trip -- a ds_bpermute chain here costs more
+// half-row mirror, row mirror): four VALU steps for 16 lanes and no LDS round trip -- a ds_bpermute chain here costs more
 // than the whole product walk of a 100-product row.  64 lanes: the four row results are combined in a fixed order.
-template <class Op>
-__device__ __forceinline__ float row16_allreduce(float v, Op op) {
-  v = op(v, __int_as_float(SMF_DPP(__float_as_int(v), 0xB1, 0xf, 0)));    // quad_perm [1,0,3,2]
-  v = op(v, __int_as_float(SMF_DPP(__float_as_int(v), 0x4E, 0xf, 0)));    // quad_perm [2,3,0,1]
-  v = op(v, __int_as_float(SMF_DPP(__float_as_int(v), 0x141, 0xf, 0)));   // row_half_mirror
-  v = op(v, __int_as_float(SMF_DPP(__float_as_int(v), 0x140, 0xf, 0)));   // row_mirror
-  return v;
-}
-template <int L, class Op>
-__device__ __forceinline__ float rowL_allreduce(float v, Op op) {
+template <int L, class V, class Op>
+__device__ __forceinline__ V rowL_allreduce(V v, Op op) {
   static_assert(L == 16 || L == 64, "16-lane groups or whole waves");
-  v = row16_allreduce(v, op);
+  v = op(v, lane_dpp<0xB1>(v));                       // quad_perm [1,0,3,2]
+  v = op(v, lane_dpp<0x4E>(v));                       // quad_perm [2,3,0,1]
+  v = op(v, lane_dpp<0x141>(v));                      // row_half_mirror
+  v = op(v, lane_dpp<0x140>(v));                      // row_mirror
   if (L == 64) {
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    const V r0 = lane_read(v, 0), r1 = lane_read(v, 16), r2 = lane_read(v, 32), r3 = lane_read(v, 48);
     v = op(op(r0, r1), op(r2, r3));
   }
   return v;
 }
-template <int L> __device__ __forceinline__ float rowL_sum(float v) { return rowL_allreduce<L>(v, [](float a, float b) { return a + b; }); }
-template <int L> __device__ __forceinline__ float rowL_max(float v) { return rowL_allreduce<L>(v, [](float a, float b) { return fmaxf(a, b); }); }
+template <int L, class V> __device__ __forceinline__ V rowL_sum(V v) { return rowL_allreduce<L>(v, [](V a, V b) { return a + b; }); }
+template <int L, class V> __device__ __forceinline__ V rowL_max(V v) { return rowL_allreduce<L>(v, [](V a, V b) { return rmcl_max(a, b); }); }
 // this group's 16 (or all 64) bits of a wave-wide lane mask
 template <int L>
 __device__ __forceinline__ unsigned long long group_mask(unsigned long long mk, int gl) {
   return L == 64 ? mk : ((mk >> (lane_id() - gl)) & 0xffffull);
 }
 
+// A finished row's slots in LDS, by value type: a view of pointers only, everything inlines to what the kernels did by hand.
+//   float   one packed 64-bit slot per entry (make_slot): a product that meets an empty slot deposits both with one CAS
+//   double  int keys claimed by CAS + double values accumulated by atomicAdd: (column, double) does not fit one CAS
+// at(i) reads slot i once for key() and val(), empty() is what a cleared slot reads as; put() writes entry i of a plain
+// list; accum() adds a product to the hash table.
+// BOUND: a store that takes an entry from the row's swept slots to C is checked against the row's length (store_ok).
+// Nothing is stored past it in a correct run (the symbolic pass counted the same columns); the check only keeps a count
+// mismatch, which raises ERRF_COUNT_MISMATCH either way, from touching the next row.  On for double.  Off for float: with
+// it, nine of the sixteen fused float kernels take 2 more VGPRs and all of them, the headline path's k_num_g16 included,
+// more code, and the fused float kernels of the R-MCL loop measured about 2 % slower, for a case the error word already
+// reports (the same split as k_rmcl_compact's BOUND; figures in profiles/README.md).
+template <class V> struct RowTab;
+template <> struct RowTab<float> {
+  typedef float value_type;
+  static constexpr bool BOUND = false;
+  struct Entry {                                      // the slot as loaded: one 64-bit read serves key and value
+    slot_t sv;
+    __device__ __forceinline__ int key() const { return slot_key(sv); }
+    __device__ __forceinline__ float val() const { return slot_val(sv); }
+  };
+  slot_t* tab;
+  __device__ __forceinline__ Entry at(int i) const { return {tab[i]}; }
+  __device__ __forceinline__ static Entry empty() { return {EMPTY_SLOT}; }
+  __device__ __forceinline__ void clear(int i) const { tab[i] = EMPTY_SLOT; }
+  __device__ __forceinline__ void put(int i, int col, float v) const { tab[i] = make_slot(col, v); }
+  __device__ __forceinline__ void accum(int size, int shift, int col, float v, int* err) const {
+    hash_accum(tab, size, shift, col, v, err);
+  }
+};
+template <> struct RowTab<double> {
+  typedef double value_type;
+  static constexpr bool BOUND = true;
+  struct Entry {
+    int k;
+    double v;
+    __device__ __forceinline__ int key() const { return k; }
+    __device__ __forceinline__ double val() const { return v; }
+  };
+  int* keys;
+  double* vals;
+  __device__ __forceinline__ Entry at(int i) const { return {keys[i], vals[i]}; }
+  __device__ __forceinline__ static Entry empty() { return {EMPTY_KEY, 0.0}; }
+  __device__ __forceinline__ void clear(int i) const { keys[i] = EMPTY_KEY; vals[i] = 0.0; }
+  __device__ __forceinline__ void put(int i, int col, double v) const { keys[i] = col; vals[i] = v; }
+  __device__ __forceinline__ void accum(int size, int shift, int col, double v, int* err) const {
+    bool isnew;
+    atomicAdd(&vals[hash_insert(keys, size, shift, col, &isnew, err)], v);
+  }
+};
+// the LDS behind a view of N slots
+template <class V, int N> struct RowTabMem;
+template <int N> struct RowTabMem<float, N> {
+  slot_t tab[N];
+  __device__ __forceinline__ RowTab<float> view() { return {tab}; }
+};
+template <int N> struct RowTabMem<double, N> {
+  double vals[N];
+  int keys[N];
+  __device__ __forceinline__ RowTab<double> view() { return {keys, vals}; }
+};
+// may entry `o` of a row of `want` entries be stored?  want < 0 (length unknown, see prune_emit_group) bounds nothing.
+template <class Tab>
+__device__ __forceinline__ bool store_ok(int o, int want) { return !Tab::BOUND || (unsigned)o < (unsigned)want; }
+// ... and how many of `kept` entries were stored
+template <class Tab>
+__device__ __forceinline__ int stored_count(int kept, int want) { return Tab::BOUND && want >= 0 ? min(kept, want) : kept; }
+
 // Fused expansion + prune (hip_rmcl_expand_prune): the row rule applied to a finished row that still sits in LDS, so
 // that only the KEPT entries (about a quarter of an R-MCL product) ever reach HBM.  They are written, normalised, to
 // the FRONT of the row's range of the scratch arrays, their count to cnt[row]; k_rmcl_move then packs the rows.
 // The slots hold either a hash table (occupied = key set) or the plain list of the row's `want` products (expanded rows).
 // L lanes share the row (a 16-lane group or a whole wave) and sweep slots [0, per), per a multiple of L.
-// want < 0: the number of distinct columns is not known beforehand (no symbolic pass ran), the occupied slots are counted.
-template <int L>
-__device__ __forceinline__ int prune_emit_group(const slot_t* tab, int per, int want, bool byKey, bool live, int gl,
-                                                int* __restrict__ JCrow, float* __restrict__ Crow, int* nocc) {
-  float mx = 0.f, sum = 0.f;
+// want < 0: the number of distinct columns is not known beforehand (no symbolic pass ran), the occupied slots are counted;
+// the row's range then holds all its products, so no store needs a bound (store_ok).
+// Returns the count of kept entries stored; *nocc = occupied slots.
+template <int L, class Tab>
+__device__ __forceinline__ int prune_emit_group(Tab t, int per, int want, bool byKey, bool live, int gl, int* __restrict__ JCrow,
+                                                typename Tab::value_type* __restrict__ Crow, int* nocc) {
+  typedef typename Tab::value_type V;
+  V mx = V(0), sum = V(0);
   int n = 0;
   for (int i0 = 0; i0 < per; i0 += L) {
-    const slot_t sv = tab[i0 + gl];
-    const bool occ = live && (byKey ? slot_key(sv) != EMPTY_KEY : i0 + gl < want);
-    const float c = slot_val(sv), v = occ ? c * c : 0.f;
-    mx = fmaxf(mx, v);
+    const auto sv = t.at(i0 + gl);
+    const bool occ = live && (byKey ? sv.key() != EMPTY_KEY : i0 + gl < want);
+    const V c = sv.val(), v = occ ? c * c : V(0);
+    mx = rmcl_max(mx, v);
     sum += v;
     n += __popcll(group_mask<L>(ballot64(occ), gl));
   }
   mx = rowL_max<L>(mx);
   sum = rowL_sum<L>(sum);
   *nocc = n;
-  const float th = rmcl_threshold(sum / (float)(want >= 0 ? want : n), mx);
-  float ks = 0.f;
+  const V th = rmcl_threshold(sum / (V)(want >= 0 ? want : n), mx);
+  V ks = V(0);
   for (int i0 = 0; i0 < per; i0 += L) {
-    const slot_t sv = tab[i0 + gl];
-    const bool occ = live && (byKey ? slot_key(sv) != EMPTY_KEY : i0 + gl < want);
-    const float c = slot_val(sv), v = c * c;
-    ks += (occ && v >= th) ? v : 0.f;
+    const auto sv = t.at(i0 + gl);
+    const bool occ = live && (byKey ? sv.key() != EMPTY_KEY : i0 + gl < want);
+    const V c = sv.val(), v = c * c;
+    ks += (occ && v >= th) ? v : V(0);
   }
   ks = rowL_sum<L>(ks);
-  const float inv = 1.0f / ks;                        // one division per row; v*inv is within an ulp of v/ks
+  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks
   int pos = 0;
   for (int i0 = 0; i0 < per; i0 += L) {
-    const slot_t sv = tab[i0 + gl];
-    const bool occ = live && (byKey ? slot_key(sv) != EMPTY_KEY : i0 + gl < want);
-    const float c = slot_val(sv), v = c * c;
+    const auto sv = t.at(i0 + gl);
+    const bool occ = live && (byKey ? sv.key() != EMPTY_KEY : i0 + gl < want);
+    const V c = sv.val(), v = c * c;
     const bool keep = occ && v >= th;
     const unsigned long long gm = group_mask<L>(ballot64(keep), gl);
     if (keep) {
       const int o = pos + __popcll(gm & ((1ull << gl) - 1ull));
-      st_out(JCrow + o, slot_key(sv));
-      st_out(Crow + o, v * inv);
+      if (store_ok<Tab>(o, want)) { st_out(JCrow + o, sv.key()); st_out(Crow + o, v * inv); }
     }
     pos += __popcll(gm);
   }
-  return pos;
+  return stored_count<Tab>(pos, want);
 }
 
-// the same for a block of NW waves whose wave w owns slots [w*per, w*per+per) of a hash table: slots into registers,
-// two block reductions (partials summed in wave order by every thread: the result does not depend on timing)
-template <int NW> struct PruneShared { float mx[NW], sum[NW], ks[NW]; int occ[NW], kc[NW]; };
+// The same for a block of NW waves on a hash table.  One sweep of the table: every thread takes its MAXSTEPS slots in one
+// unrolled loop (the loads overlap; three dependent sweeps of a 4096-slot table cost more than the product walk of its row)
+// and keeps key and squared value in registers, -1 marking an empty slot (never >= a threshold).  Partials are combined in wave
+// order by every thread, so the threshold, the kept sum and the places of the kept entries (wave by wave, step by step,
+// lane by lane) do not depend on timing.
+// Which slot a thread holds at a step is the layout's: slot(s), has(s) = that slot lies inside the table, live(s) = step s is
+// worth running at all (uniform over the block; a step that is not live is skipped throughout).
+//   WaveSegments     wave w owns slots [w*per, w*per+per), per a multiple of 64: a wave's kept entries are neighbours in
+//                    the table (k_num_hash, whose table is at most twice its steps: the empty steps are swept like the rest)
+//   BlockStrided<NT> step s is slots [s*NT, s*NT+NT) of a table of `size` slots, any power of two from 64 on
+//                    (k_num64_rows, whose table is sized by the row: most rows need few of the steps)
+struct WaveSegments {
+  int per;
+  __device__ __forceinline__ int slot(int s) const { return (threadIdx.x >> 6) * per + s * WAVE + lane_id(); }
+  __device__ __forceinline__ bool has(int s) const { return s * WAVE < per; }
+  __device__ __forceinline__ bool live(int) const { return true; }
+};
+template <int NT> struct BlockStrided {
+  int size;
+  __device__ __forceinline__ int slot(int s) const { return s * NT + threadIdx.x; }
+  __device__ __forceinline__ bool has(int s) const { return slot(s) < size; }
+  __device__ __forceinline__ bool live(int s) const { return s * NT < size; }
+};
+template <class V, int NW> struct PruneShared { V mx[NW], sum[NW], ks[NW]; int occ[NW], kc[NW]; };
 
-template <int NW, int MAXSTEPS>
-__device__ __forceinline__ void prune_emit_block(const slot_t* tab, int per, int want, PruneShared<NW>& ps,
-                                                 int* __restrict__ JCrow, float* __restrict__ Crow,
+template <int NW, int MAXSTEPS, class Tab, class Lay>
+__device__ __forceinline__ void prune_emit_block(Tab t, Lay lay, int want, PruneShared<typename Tab::value_type, NW>& ps,
+                                                 int* __restrict__ JCrow, typename Tab::value_type* __restrict__ Crow,
                                                  int* __restrict__ cntRow, int* __restrict__ err) {
+  typedef typename Tab::value_type V;
   const int lane = lane_id(), w = threadIdx.x >> 6;
-  slot_t sl[MAXSTEPS];
-  float v[MAXSTEPS];                                  // squared value; -1 marks an empty slot (never >= a threshold)
-  float mx = 0.f, sum = 0.f;
+  int k[MAXSTEPS];
+  V v[MAXSTEPS];                                      // squared value; -1 marks an empty slot (never >= a threshold)
+  V mx = V(0), sum = V(0);
   int n = 0;
 #pragma unroll
   for (int sidx = 0; sidx < MAXSTEPS; ++sidx) {
-    sl[sidx] = sidx * WAVE < per ? tab[w * per + sidx * WAVE + lane] : EMPTY_SLOT;
-    const bool occ = slot_key(sl[sidx]) != EMPTY_KEY;
-    const float c = slot_val(sl[sidx]);
-    v[sidx] = occ ? c * c : -1.f;
-    mx = fmaxf(mx, v[sidx]);
-    sum += occ ? v[sidx] : 0.f;
-    n += __popcll(ballot64(occ));
+    const typename Tab::Entry sv = lay.has(sidx) ? t.at(lay.slot(sidx)) : Tab::empty();
+    k[sidx] = sv.key();
+    v[sidx] = V(-1);                                  // (a step that is not live holds nothing)
+    if (lay.live(sidx)) {
+      const bool occ = sv.key() != EMPTY_KEY;
+      v[sidx] = occ ? sv.val() * sv.val() : V(-1);
+      mx = rmcl_max(mx, v[sidx]);
+      sum += occ ? v[sidx] : V(0);
+      n += __popcll(ballot64(occ));
+    }
   }
   mx = rowL_max<64>(mx);
   sum = rowL_sum<64>(sum);
   if (lane == 0) { ps.mx[w] = mx; ps.sum[w] = sum; ps.occ[w] = n; }
   __syncthreads();
-  mx = 0.f; sum = 0.f; n = 0;
+  mx = V(0); sum = V(0); n = 0;
 #pragma unroll
-  for (int i = 0; i < NW; ++i) { mx = fmaxf(mx, ps.mx[i]); sum += ps.sum[i]; n += ps.occ[i]; }
-  const float th = rmcl_threshold(sum / (float)(want >= 0 ? want : n), mx);
-  float ks = 0.f;
-  int kc = 0;
+  for (int i = 0; i < NW; ++i) { mx = rmcl_max(mx, ps.mx[i]); sum += ps.sum[i]; n += ps.occ[i]; }
+  const V th = rmcl_threshold(sum / (V)(want >= 0 ? want : n), mx);
+  V ks = V(0);
+  int kc = 0;                                         // kept by this wave (wave-uniform)
 #pragma unroll
   for (int sidx = 0; sidx < MAXSTEPS; ++sidx) {
-    const bool keep = v[sidx] >= th;
-    ks += keep ? v[sidx] : 0.f;
-    kc += __popcll(ballot64(keep));
+    if (lay.live(sidx)) {
+      const bool keep = v[sidx] >= th;
+      ks += keep ? v[sidx] : V(0);
+      kc += __popcll(ballot64(keep));
+    }
   }
   ks = rowL_sum<64>(ks);
   if (lane == 0) { ps.ks[w] = ks; ps.kc[w] = kc; }
   __syncthreads();
-  ks = 0.f;
-  int pos = 0, total = 0;
+  ks = V(0);
+  int pos = 0, total = 0;                             // this wave's first place: the waves before it, in wave order
 #pragma unroll
   for (int i = 0; i < NW; ++i) { ks += ps.ks[i]; pos += i < w ? ps.kc[i] : 0; total += ps.kc[i]; }
-  const float inv = 1.0f / ks;
+  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks
 #pragma unroll
   for (int sidx = 0; sidx < MAXSTEPS; ++sidx) {
-    const bool keep = v[sidx] >= th;
-    const unsigned long long mk = ballot64(keep);
-    if (keep) {
-      const int o = pos + mask_rank(mk);
-      st_out(JCrow + o, slot_key(sl[sidx]));
-      st_out(Crow + o, v[sidx] * inv);
+    if (lay.live(sidx)) {
+      const bool keep = v[sidx] >= th;
+      const unsigned long long mk = ballot64(keep);
+      if (keep) {
+        const int o = pos + mask_rank(mk);
+        if (store_ok<Tab>(o, want)) { st_out(JCrow + o, k[sidx]); st_out(Crow + o, v[sidx] * inv); }
+      }
+      pos += __popcll(mk);
     }
-    pos += __popcll(mk);
   }
   if (threadIdx.x == 0) {
-    *cntRow = total;
+    *cntRow = stored_count<Tab>(total, want);
     if (want >= 0 && n != want) atomicOr(err, ERRF_COUNT_MISMATCH);
   }
 }
@@ -842,17 +958,19 @@ __device__ __forceinline__ int row16_incl_add(int v) {   // inclusive scan insid
   return v;
 }
 
-struct G16Stage { int incl[16]; int off[16]; float aval[16]; };
+template <class V> struct G16Stage { int incl[16]; int off[16]; V aval[16]; };
 
-template <int U, bool NEED_VAL, class F>
-__device__ __forceinline__ void g16_walk(G16Stage& st, int gl, int as, int ae, const int2* __restrict__ SBL,
-                                         const float* __restrict__ VA,
-                                         const int* __restrict__ JB, const float* __restrict__ VB, F&& f) {
+// the products of one row, 16 A entries staged at a time; f(active, col, a*b, position of the product in the row).
+// NEED_VAL = false (the symbolic pass): no value is loaded, staged or multiplied.
+template <class V, int U, bool NEED_VAL, class F>
+__device__ __forceinline__ void g16_walk(G16Stage<V>& st, int gl, int as, int ae, const int2* __restrict__ SBL,
+                                         const V* __restrict__ VA,
+                                         const int* __restrict__ JB, const V* __restrict__ VB, F&& f) {
   int rowBase = 0;                                  // products of the chunks before this one
   for (int chunk = as; chunk < ae; chunk += 16) {
     const int ap = chunk + gl;
     int len = 0, bs = 0;
-    float a = 0.f;
+    V a = V(0);
     if (ap < ae) {
       const int2 sbl = SBL[ap];
       bs = sbl.x;
@@ -878,15 +996,15 @@ __device__ __forceinline__ void g16_walk(G16Stage& st, int gl, int as, int ae, c
         }
       }
       int col[U];
-      float val[U], av[U], vb[U];
+      V val[U], av[U], vb[U];
       bool act[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {                // straight-line, no branches around the gathers
         act[u] = (r0 + u) * 16 + gl < T;
         const int jb = st.off[e[u]] + p[u];
         col[u] = JB[jb];
-        vb[u] = NEED_VAL ? VB[jb] : 0.f;
-        av[u] = NEED_VAL ? st.aval[e[u]] : 0.f;
+        vb[u] = NEED_VAL ? VB[jb] : V(0);
+        av[u] = NEED_VAL ? st.aval[e[u]] : V(0);
       }
       __builtin_amdgcn_sched_barrier(0);           // all gathers issued before the first wait
 #pragma unroll
@@ -907,7 +1025,7 @@ __global__ __launch_bounds__(256) void k_sym_g16(const int* __restrict__ binPtr,
                                                   const int* __restrict__ rowFlops, int* __restrict__ IC,
                                                   int* __restrict__ err) {
   __shared__ int keys[16][TBL];
-  __shared__ G16Stage st[16];
+  __shared__ G16Stage<float> st[16];               // (no value is staged: the type only sizes the unused array)
   const int tid = threadIdx.x, g = tid >> 4, gl = tid & 15;
   const int first = binPtr[bin], count = binPtr[binHi] - first;
   const int iters = (count + 15) / 16;
@@ -925,7 +1043,7 @@ __global__ __launch_bounds__(256) void k_sym_g16(const int* __restrict__ binPtr,
     wave_lds_sync();
     int mine = 0;
     if (live) {
-      g16_walk<U, false>(st[g], gl, IA[row], IA[row + 1], SBL, nullptr, JB, nullptr, [&](bool active, int col, float, int) {
+      g16_walk<float, U, false>(st[g], gl, IA[row], IA[row + 1], SBL, nullptr, JB, nullptr, [&](bool active, int col, float, int) {
         if (active) {
           bool isnew;
           hash_insert(keys[g], size, shift, col, &isnew, err);
@@ -942,20 +1060,28 @@ __global__ __launch_bounds__(256) void k_sym_g16(const int* __restrict__ binPtr,
 // PRUNE: 0 plain product; 1 fused R-MCL prune, IC = exact row pointers of the product (symbolic pass ran); 2 fused prune
 // WITHOUT a symbolic pass: IC = prefix sums of the rows' product counts (an upper bound of every row; rows of bin 8, which
 // these kernels do not see, contribute their exact counts), every row is hashed
-// in a table sized by its products and the distinct columns are counted by the epilogue itself.
-template <int TBL, int U, int PRUNE = 0>
+// in a table sized by its products and the distinct columns are counted by the epilogue itself (float only).
+// V: float or double; the double pipeline (spgemm_f64_device.hpp) launches this kernel for its bins 1-4 with the exact row
+// pointers of the float pipeline's symbolic pass.  Two rules hold for both types:
+//   * a row kept as a plain list that is longer than the table (cannot happen for rows of these bins: at most 64 products,
+//     TBL >= 64 where they go) is cut at the table and raises ERRF_TABLE_FULL;
+//   * the stores of the compaction sweeps are bounded by the row's length where the view says so (RowTab<V>::BOUND).
+template <class V, int TBL, int U, int PRUNE = 0>
 __global__ __launch_bounds__(256) void k_num_g16(const int* __restrict__ binPtr, int bin, int binHi,
                                                   const int* __restrict__ rowIds,
                                                   const int* __restrict__ IA, const int2* __restrict__ SBL,
-                                                  const float* __restrict__ VA,
+                                                  const V* __restrict__ VA,
                                                   const int* __restrict__ JB,
-                                                  const float* __restrict__ VB,
+                                                  const V* __restrict__ VB,
                                                   const int* __restrict__ IC, int* __restrict__ JC,
-                                                  float* __restrict__ C, int* __restrict__ err,
+                                                  V* __restrict__ C, int* __restrict__ err,
                                                   const int* __restrict__ rowFlops, int* __restrict__ pcnt) {
-  __shared__ slot_t tab[16][TBL];              // (column, value) pairs
-  __shared__ G16Stage st[16];
+  static_assert(PRUNE != 2 || std::is_same<V, float>::value, "the fused prune without a symbolic pass is float only");
+  typedef RowTab<V> Tab;
+  __shared__ RowTabMem<V, TBL> mem[16];        // one table (or plain list) per row of the block
+  __shared__ G16Stage<V> st[16];
   const int tid = threadIdx.x, g = tid >> 4, gl = tid & 15;
+  const Tab t = mem[g].view();
   const int first = binPtr[bin], count = binPtr[binHi] - first;
   const int iters = (count + 15) / 16;
   // XCD-contiguous schedule: the blocks that share an XCD (blockIdx % 8, guide "Workgroup dispatch") walk ONE contiguous
@@ -974,20 +1100,20 @@ __global__ __launch_bounds__(256) void k_num_g16(const int* __restrict__ binPtr,
     if (ballot64(hashRow) == 0ull) {
       if (PRUNE) {                                   // the row's products as a plain list in LDS, then the row rule
         if (live) {
-          g16_walk<U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, float v, int pos) {
-            if (active && (unsigned)pos < (unsigned)min(want, TBL)) tab[g][pos] = make_slot(col, v);
+          g16_walk<V, U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, V v, int pos) {
+            if (active && (unsigned)pos < (unsigned)min(want, TBL)) t.put(pos, col, v);
           });
         }
         wave_lds_sync();
         int nocc;
-        const int kept = prune_emit_group<16>(tab[g], (min(want, TBL) + 15) & ~15, min(want, TBL), false, live, gl,
+        const int kept = prune_emit_group<16>(t, (min(want, TBL) + 15) & ~15, min(want, TBL), false, live, gl,
                                               JC + off, C + off, &nocc);
         if (live && gl == 0) { pcnt[row] = kept; if (want > TBL) atomicOr(err, ERRF_TABLE_FULL); }
         wave_lds_sync();
         continue;
       }
       if (live) {
-        g16_walk<U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, float v, int pos) {
+        g16_walk<V, U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, V v, int pos) {
           if (active && (unsigned)pos < (unsigned)want) { st_out(JC + off + pos, col); st_out(C + off + pos, v); }
         });
       }
@@ -995,29 +1121,29 @@ __global__ __launch_bounds__(256) void k_num_g16(const int* __restrict__ binPtr,
     }
     const int size = table_size(want, 16, TBL);
     const int shift = 32 - log2_pow2(size);
-    for (int i = gl; i < size; i += 16) tab[g][i] = EMPTY_SLOT;
+    for (int i = gl; i < size; i += 16) t.clear(i);
     wave_lds_sync();
     if (live) {
-      g16_walk<U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, float v, int) {
-        if (active) hash_accum(tab[g], size, shift, col, v, err);
+      g16_walk<V, U, true>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, V v, int) {
+        if (active) t.accum(size, shift, col, v, err);
       });
     }
     wave_lds_sync();
     if (PRUNE) {
       int nocc;
-      const int kept = prune_emit_group<16>(tab[g], size, PRUNE == 2 ? -1 : want, true, live, gl, JC + off, C + off, &nocc);
+      const int kept = prune_emit_group<16>(t, size, PRUNE == 2 ? -1 : want, true, live, gl, JC + off, C + off, &nocc);
       if (live && gl == 0) { pcnt[row] = kept; if (PRUNE == 1 && nocc != want) atomicOr(err, ERRF_COUNT_MISMATCH); }
       wave_lds_sync();
       continue;
     }
     int written = 0;
     for (int i0 = 0; i0 < size; i0 += 16) {
-      const slot_t sv = tab[g][i0 + gl];
-      const bool occ = live && slot_key(sv) != EMPTY_KEY;
+      const auto sv = t.at(i0 + gl);
+      const bool occ = live && sv.key() != EMPTY_KEY;
       const unsigned long long mk = ballot64(occ);
       const unsigned gm = (unsigned)(mk >> (lane_id() - gl)) & 0xffffu;
       const int rank = __popc(gm & ((1u << gl) - 1u));
-      if (occ) { st_out(JC + off + written + rank, slot_key(sv)); st_out(C + off + written + rank, slot_val(sv)); }
+      if (occ && store_ok<Tab>(written + rank, want)) { st_out(JC + off + written + rank, sv.key()); st_out(C + off + written + rank, sv.val()); }
       written += __popc(gm);
     }
     if (live && gl == 0 && written != want) atomicOr(err, ERRF_COUNT_MISMATCH);
@@ -1746,7 +1872,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
                                                          int* __restrict__ qctr, const int* __restrict__ rowFlops,
                                                          int* __restrict__ pcnt) {
   __shared__ __attribute__((aligned(16))) slot_t tab[TBL];   // (column, value) pairs
-  __shared__ PruneShared<NW> ps;                 // (fused prune, several waves: the block reductions)
+  __shared__ PruneShared<float, NW> ps;               // (fused prune, several waves: the block reductions)
   __shared__ typename WalkSel<NW>::type st;
   __shared__ int qslot;
   __shared__ int emitted;                        // output positions handed out so far in this row (NW > 1)
@@ -1794,7 +1920,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
       }, pc, err);
       wave_lds_sync();
       int nocc;
-      const int kept = prune_emit_group<64>(tab, (want + 63) & ~63, want, false, true, lane_id(), JC + off, C + off, &nocc);
+      const int kept = prune_emit_group<64>(RowTab<float>{tab}, (want + 63) & ~63, want, false, true, lane_id(), JC + off, C + off, &nocc);
       if (lane_id() == 0) pcnt[cur.row] = kept;
       wave_lds_sync();
       cur = nxt;
@@ -1865,11 +1991,11 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_hash(const int* __restrict__ 
     if (ABL(4)) { __syncthreads(); }
     else if (PRUNE && NW == 1) {
       int nocc;
-      const int kept = prune_emit_group<64>(tab, per, PRUNE == 2 ? -1 : want, true, true, lane, JC + off, C + off, &nocc);
+      const int kept = prune_emit_group<64>(RowTab<float>{tab}, per, PRUNE == 2 ? -1 : want, true, true, lane, JC + off, C + off, &nocc);
       if (tid == 0) { pcnt[cur.row] = kept; if (PRUNE == 1 && nocc != want) atomicOr(err, ERRF_COUNT_MISMATCH); }
       __syncthreads();
     } else if (PRUNE) {
-      prune_emit_block<NW, TBL / NW / WAVE>(tab, per, PRUNE == 2 ? -1 : want, ps, JC + off, C + off, pcnt + cur.row, err);
+      prune_emit_block<NW, TBL / NW / WAVE>(RowTab<float>{tab}, WaveSegments{per}, PRUNE == 2 ? -1 : want, ps, JC + off, C + off, pcnt + cur.row, err);
       __syncthreads();
     } else if (NW == 1) {
       int pos = 0;                                    // relative to the row: small 32-bit offsets for both stores

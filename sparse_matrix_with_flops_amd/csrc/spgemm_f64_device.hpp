@@ -6,9 +6,10 @@
 // pointers IC, i.e. every row i knows its output length L_i = IC[i+1] - IC[i].  The float kernels pack (column, float)
 // into one 64-bit slot and CAS it; a (column, double) pair does not fit one CAS, so the tables here are split: int keys
 // claimed by CAS, double values accumulated by atomicAdd (ds_add_f64 in LDS, global_atomic_add_f64 in device memory under
-// -munsafe-fp-atomics).  Tables are sized from L_i, not from the product count.
+// -munsafe-fp-atomics): RowTab<double> of spgemm_device.hpp.  Tables are sized from L_i, not from the product count.
 //
-//   bins 1-4 (1-64 products)      k_num64_g16    16 lanes per row; rows whose products all hit different columns
+//   bins 1-4 (1-64 products)      k_num_g16<double>  the float pipeline's 16-lane kernel (spgemm_device.hpp) on the
+//                                                split table; rows whose products all hit different columns
 //                                                (L_i == products) write them straight to their place, no table
 //   bins 5-7 (65-4096 products)   k_num64_rows   one block per row, LDS table of up to 8192 slots (96 KB)
 //   bin 8, L_i <= F64_LDS_MAXL    k_num64_rows   the same with 1024 threads, table of 8192 slots loaded up to 3/4
@@ -18,9 +19,10 @@
 //                                                per block, compacted into the output row
 // Rows come out column-unsorted (the float path's contract).  A full table or an emitted count != L_i raises the error
 // word, and the call fails with SPGEMM_ERR_INTERNAL.
+// The fused R-MCL step (PRUNE) is the float path's: prune_emit_block of spgemm_device.hpp over RowTab<double>, with the
+// table swept NT slots a step (BlockStrided<NT>) where the float kernels give each wave a segment.
 #pragma once
 #include "spgemm_device.hpp"
-#include "rmcl_f64_device.hpp"
 
 namespace smf {
 
@@ -36,146 +38,6 @@ __device__ __forceinline__ int col_class(int c, int npass) {
   return (int)(((unsigned long long)x * (unsigned)npass) >> 32);
 }
 constexpr int F64_BIG_THREADS = 1024;
-
-// ---- bins 1-4: 16 lanes per row ------------------------------------------------------------------------------------
-struct G64Stage { int incl[16]; int off[16]; double aval[16]; };
-
-// the products of one row, 16 A entries staged at a time; f(active, col, a*b, position of the product in the row)
-template <int U, class F>
-__device__ __forceinline__ void g64_walk(G64Stage& st, int gl, int as, int ae, const int2* __restrict__ SBL,
-                                         const double* __restrict__ VA, const int* __restrict__ JB,
-                                         const double* __restrict__ VB, F&& f) {
-  int rowBase = 0;
-  for (int chunk = as; chunk < ae; chunk += 16) {
-    const int ap = chunk + gl;
-    int len = 0, bs = 0;
-    double a = 0.0;
-    if (ap < ae) {
-      const int2 sbl = SBL[ap];
-      bs = sbl.x;
-      len = sbl.y;
-      a = VA[ap];
-    }
-    const int incl = row16_incl_add(len);
-    st.incl[gl] = incl;
-    st.off[gl] = bs - (incl - len);
-    st.aval[gl] = a;
-    wave_lds_sync();
-    const int T = st.incl[15];
-    for (int r0 = 0; r0 * 16 < T; r0 += U) {
-      int p[U], e[U], col[U];
-      double vb[U], av[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) { p[u] = min((r0 + u) * 16 + gl, T - 1); e[u] = 0; }
-#pragma unroll
-      for (int sft = 8; sft >= 1; sft >>= 1) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int c = e[u] + sft;
-          e[u] = st.incl[c - 1] <= p[u] ? c : e[u];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int jb = st.off[e[u]] + p[u];
-        col[u] = JB[jb];
-        vb[u] = VB[jb];
-        av[u] = st.aval[e[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) f((r0 + u) * 16 + gl < T, col[u], av[u] * vb[u], rowBase + (r0 + u) * 16 + gl);
-    }
-    rowBase += T;
-    wave_lds_sync();
-  }
-}
-
-// PRUNE (the fused R-MCL step, rmcl_f64_device.hpp): the row rule is applied to the finished row in LDS, the kept entries
-// go, normalised, to the front of the row's range and their count to pcnt[row]; a row of distinct columns is held as the
-// plain list of its products in the slots the table would have used.
-template <int TBL, int U, bool PRUNE = false>
-__global__ __launch_bounds__(256) void k_num64_g16(const int* __restrict__ binPtr, int bin, int binHi,
-                                                    const int* __restrict__ rowIds,
-                                                    const int* __restrict__ IA, const int2* __restrict__ SBL,
-                                                    const double* __restrict__ VA, const int* __restrict__ JB,
-                                                    const double* __restrict__ VB, const int* __restrict__ IC,
-                                                    int* __restrict__ JC, double* __restrict__ C, int* __restrict__ err,
-                                                    const int* __restrict__ rowFlops, int* __restrict__ pcnt) {
-  __shared__ int keys[16][TBL];
-  __shared__ double vals[16][TBL];
-  __shared__ G64Stage st[16];
-  const int tid = threadIdx.x, g = tid >> 4, gl = tid & 15;
-  const int first = binPtr[bin], count = binPtr[binHi] - first;
-  const int iters = (count + 15) / 16;
-  const XcdRange xr = xcd_range(iters);
-  for (int it = xr.lo + xr.bi; it < xr.hi; it += xr.nb) {
-    const int q = it * 16 + g;
-    const bool live = q < count;
-    const int row = live ? rowIds[first + q] : 0;
-    const int off = live ? IC[row] : 0;
-    const int want = live ? IC[row + 1] - off : 0;
-    // every product on a column of its own (want == products): straight to its place in the row
-    const bool hashRow = live && want != rowFlops[row];
-    if (ballot64(hashRow) == 0ull) {
-      if constexpr (PRUNE) {
-        const int lim = min(want, TBL);                    // (want <= 64 products <= TBL: never cut)
-        if (live) {
-          g64_walk<U>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, double v, int pos) {
-            if (active && (unsigned)pos < (unsigned)lim) { keys[g][pos] = col; vals[g][pos] = v; }
-          });
-        }
-        wave_lds_sync();
-        int nocc;
-        const int kept = prune_emit_group64<16>(keys[g], vals[g], (lim + 15) & ~15, lim, false, live, gl, JC + off, C + off, &nocc);
-        if (live && gl == 0) pcnt[row] = kept;
-        wave_lds_sync();
-        continue;
-      }
-      if (live) {
-        g64_walk<U>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, double v, int pos) {
-          if (active && (unsigned)pos < (unsigned)want) { st_out(JC + off + pos, col); st_out(C + off + pos, v); }
-        });
-      }
-      continue;
-    }
-    const int size = table_size(want, 16, TBL);
-    const int shift = 32 - log2_pow2(size);
-    for (int i = gl; i < size; i += 16) { keys[g][i] = EMPTY_KEY; vals[g][i] = 0.0; }
-    wave_lds_sync();
-    if (live) {
-      g64_walk<U>(st[g], gl, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](bool active, int col, double v, int) {
-        if (active) {
-          bool isnew;
-          const int s = hash_insert(keys[g], size, shift, col, &isnew, err);
-          atomicAdd(&vals[g][s], v);
-        }
-      });
-    }
-    wave_lds_sync();
-    if constexpr (PRUNE) {
-      int nocc;
-      const int kept = prune_emit_group64<16>(keys[g], vals[g], size, want, true, live, gl, JC + off, C + off, &nocc);
-      if (live && gl == 0) {
-        pcnt[row] = kept;
-        if (nocc != want) atomicOr(err, ERRF_COUNT_MISMATCH);
-      }
-      wave_lds_sync();
-      continue;
-    }
-    int written = 0;
-    for (int i0 = 0; i0 < size; i0 += 16) {
-      const int k = keys[g][i0 + gl];
-      const bool occ = live && k != EMPTY_KEY;
-      const unsigned long long mk = ballot64(occ);
-      const unsigned gm = (unsigned)(mk >> (lane_id() - gl)) & 0xffffu;
-      const int rank = __popc(gm & ((1u << gl) - 1u));
-      if (occ && written + rank < want) { st_out(JC + off + written + rank, k); st_out(C + off + written + rank, vals[g][i0 + gl]); }
-      written += __popc(gm);
-    }
-    if (live && gl == 0 && written != want) atomicOr(err, ERRF_COUNT_MISMATCH);
-    wave_lds_sync();
-  }
-}
 
 // ---- bins 5-8: one block per row ------------------------------------------------------------------------------------
 template <int NT> struct Row64Stage { int incl[NT]; int off[NT]; double aval[NT]; int wsum[NT / WAVE]; int cnt; };
@@ -251,12 +113,13 @@ __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPt
                                                    int* __restrict__ JC, double* __restrict__ C, int* __restrict__ err,
                                                    int lmin, int lmax, int* gkeys, double* gvals, int gslots,
                                                    int* __restrict__ pcnt) {
-  __shared__ PruneShared64<PRUNE ? NT / WAVE : 1> ps;
+  __shared__ PruneShared<double, PRUNE ? NT / WAVE : 1> ps;
   __shared__ int skeys[GLOBAL ? 1 : TBL];
   __shared__ double svals[GLOBAL ? 1 : TBL];
   __shared__ Row64Stage<NT> st;
   int* keys = GLOBAL ? gkeys + (size_t)blockIdx.x * gslots : skeys;
   double* vals = GLOBAL ? gvals + (size_t)blockIdx.x * gslots : svals;
+  const RowTab<double> tab{keys, vals};
   const int tid = threadIdx.x;
   const int first = binPtr[bin], count = binPtr[bin + 1] - first;
   for (int q = blockIdx.x; q < count; q += gridDim.x) {
@@ -270,14 +133,10 @@ __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPt
     const int shift = 32 - log2_pow2(size);
     if (tid == 0) st.cnt = 0;
     for (int pass = 0; pass < npass; ++pass) {
-      for (int i = tid; i < size; i += NT) { keys[i] = EMPTY_KEY; vals[i] = 0.0; }
+      for (int i = tid; i < size; i += NT) tab.clear(i);
       if (GLOBAL) __threadfence();
       __syncthreads();
-      auto accum = [&](int col, double v) {
-        bool isnew;
-        const int s = hash_insert(keys, size, shift, col, &isnew, err);
-        atomicAdd(&vals[s], v);
-      };
+      auto accum = [&](int col, double v) { tab.accum(size, shift, col, v, err); };
       if (npass == 1)
         row64_walk<NT, true>(st, IA[row], IA[row + 1], SBL, VA, JB, VB, [&](int col, int, double a, double b) { accum(col, a * b); });
       else
@@ -288,7 +147,7 @@ __global__ __launch_bounds__(NT) void k_num64_rows(const int* __restrict__ binPt
       __syncthreads();
       if constexpr (PRUNE && !GLOBAL) {
         if (npass == 1) {                                  // block-uniform
-          prune_emit_block64<NT, (TBL + NT - 1) / NT>(keys, vals, size, want, ps, JC + off, C + off, pcnt + row, err);
+          prune_emit_block<NT / WAVE, (TBL + NT - 1) / NT>(tab, BlockStrided<NT>{size}, want, ps, JC + off, C + off, pcnt + row, err);
           if (tid == 0) st.cnt = want;                     // (the epilogue has checked the count itself)
           break;
         }

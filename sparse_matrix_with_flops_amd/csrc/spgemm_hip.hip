@@ -1057,11 +1057,11 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
                          rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 7 * 32, h->rowFlops); }
   if (rows(4, 5) > 0) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_NUM_G16, st);
     with_prune_arg(pcnt, pmode, [&](auto prune) {
-      hipLaunchKernelGGL((k_num_g16<128, 4, decltype(prune)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
+      hipLaunchKernelGGL((k_num_g16<float, 128, 4, decltype(prune)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st,
                          bp, 4, 5, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   if (minBin <= 1 && rows(1, 4) > 0) { KTimer t(h, SPGEMM_K_NUM_SMALL4);   // 1..16 products: 16-lane flattened kernel, one round per row
     with_prune_arg(pcnt, pmode, [&](auto prune) {
-      hipLaunchKernelGGL((k_num_g16<32, 1, decltype(prune)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
+      hipLaunchKernelGGL((k_num_g16<float, 32, 1, decltype(prune)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, h->stream,
                          bp, 1, 4, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   join_streams(h);
   HIPCHK(hipGetLastError());
@@ -1293,7 +1293,7 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   const int cu = h->numCU;
   hipStream_t s = h->stream;
   auto rows = [&](int lo, int hi) { return hostBinPtr[hi] - hostBinPtr[lo]; };
-  // pcnt: the fused R-MCL step (rmcl_f64_device.hpp) -- the same launches with the row rule in their epilogues
+  // pcnt: the fused R-MCL step (PRUNE of the numeric kernels) --the same launches with the row rule in their epilogues
   auto fused = [&](auto launch) { if (pcnt) launch(std::true_type()); else launch(std::false_type()); };
   int wide[2] = {0, 0};                                // largest L_i of the rows beyond F64_PASS_MAXL, their number
   int* gkeys = nullptr;
@@ -1353,11 +1353,11 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
                          rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, 0, 0x7fffffff, (int*)nullptr, (double*)nullptr, 0, pcnt); }); }
   if (rows(4, 5) > 0) { hipStream_t st = h->side[0]; KTimer t(h, SPGEMM_K_NUM_G16, st);
     fused([&](auto P) {
-      hipLaunchKernelGGL((k_num64_g16<128, 4, decltype(P)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st, bp, 4, 5,
+      hipLaunchKernelGGL((k_num_g16<double, 128, 4, decltype(P)::value>), dim3(grid8(cdiv(rows(4, 5), 16), cu * 16)), dim3(256), 0, st, bp, 4, 5,
                          rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   if (rows(1, 4) > 0) { KTimer t(h, SPGEMM_K_NUM_SMALL4);
     fused([&](auto P) {
-      hipLaunchKernelGGL((k_num64_g16<32, 1, decltype(P)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, s, bp, 1, 4,
+      hipLaunchKernelGGL((k_num_g16<double, 32, 1, decltype(P)::value>), dim3(grid8(cdiv(rows(1, 4), 16), cu * 16)), dim3(256), 0, s, bp, 1, 4,
                          rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, h->rowFlops, pcnt); }); }
   join_streams(h);
   HIPCHK(hipGetLastError());

@@ -13,13 +13,19 @@ fused: by column of B), so that every threshold falls between the bands: each ca
 alone, that every row's gap (min |v^2 - th| / th) is at least 1000 times the value bound.  Under that precondition the
 device must keep exactly the reference's entries (no tie allowance), every value within bound * reference.
 Bound: rmcl_f64_ref.step_bound(N, n, u) = (8 N + 2 n + 16) u with u = 2^-24 (float) or 2^-53 (double), n the longest
-row, N the terms per product entry (0 for the prune: the same C on both sides)."""
+row, N the terms per product entry (0 for the prune: the same C on both sides).
+
+Fused epilogues (csrc/spgemm_device.hpp: prune_emit_group / prune_emit_block, one body for both value types, inside
+k_num_g16<V>, k_num_hash and k_num64_rows): three small products whose rows sit on the edges of those bodies, see EPILOGUE_ROWS,
+each run as the float step with and without its symbolic pass and as the double step.  Float results go against the oracle's
+rule (helpers.assert_rmcl_step) with no row allowed to differ, double ones against rmcl_f64_ref.step64."""
 import functools
 
 import numpy as np
 import pytest
 
 from f64ref import Host64, sorted_rows
+from helpers import assert_rmcl_step, po
 from rmcl_f64_ref import row_rule64, step64, step_bound
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
@@ -39,10 +45,10 @@ def handle():
     return hs.Handle(0)
 
 
-def banded(rng, position, dtype):
+def banded(rng, position, dtype, low=(0.15, 0.25)):
     """high band at even positions, low band at odd ones, rounded to dtype"""
     hi = rng.uniform(0.63, 0.77, len(position))
-    lo = rng.uniform(0.15, 0.25, len(position))
+    lo = rng.uniform(low[0], low[1], len(position))
     return np.where(position % 2 == 0, hi, lo).astype(dtype)
 
 
@@ -152,3 +158,84 @@ def test_fused_float_step_fixes_full_rows_in_place(handle):
     err = np.abs(gv.astype(np.float64) - wv)
     print(f"fix_rows<float>: kept {len(wv)}, worst relative error {float((err / wv).max()):.3e}, bound {bound:.3e}")
     assert np.all(err <= bound * wv)
+
+
+# ---- the fused epilogues at their edges ----------------------------------------------------------------------------
+# (terms, columns) per row: the row of A has `terms` entries, each on a B row of its own with the columns 0..columns-1, so
+# the product row has terms * columns products on `columns` distinct columns.  The rows of a 16-lane wave take one path
+# together, so rows with repeated columns (hashed) are kept out of the products whose rows are plain lists.
+EPILOGUE_ROWS = {
+    # 16 lanes per row, the products as a plain list (float: with the symbolic pass; hashed without it): lengths that are
+    # no multiple of 16, both table sizes (up to 16 and 17..64 products); 3 and 2 rows per launch, so the block's other
+    # 16-lane groups are dead beside live ones
+    "list16": [(1, 1), (1, 15), (1, 16), (1, 17), (1, 64)],
+    # a wave per row at 65 and 512 products (float: list with the symbolic pass, else hashed); float blocks of 4 and 8
+    # waves at 513, 2048, 2049 and 4096 products; double: one block per row, tables of 256 to 8192 slots
+    "long": [(1, 65), (1, 512), (1, 513), (1, 2048), (1, 2049), (1, 4096)],
+    # fewer distinct columns than products, hashed in every mode: 16 lanes at both table sizes (14 and 40 products), a
+    # wave per row at 65 and 512 products, 513 products on 19 columns (double: a 64-slot table under 256 threads and 16
+    # steps, of which one is live and three quarters of its threads hold no slot)
+    "hashed": [(2, 7), (2, 20), (5, 13), (2, 256), (27, 19)],
+}
+
+
+@functools.lru_cache(maxsize=None)
+def epilogue_case(name):
+    """-> (A, B as Host64 of float32-rounded values, Step64 of A * B): built once, shared, never modified"""
+    spec = EPILOGUE_ROWS[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    terms = np.array([t for t, _ in spec])
+    arp = np.zeros(len(spec) + 1, np.int32)
+    np.cumsum(terms, out=arp[1:])
+    aval = (rng.uniform(0.98, 1.02, arp[-1]) / np.repeat(terms, terms)).astype(np.float32)
+    A = Host64(arp, np.arange(arp[-1]), aval, len(spec), arp[-1])
+    blen = np.repeat([l for _, l in spec], terms)
+    brp = np.zeros(len(blen) + 1, np.int32)
+    np.cumsum(blen, out=brp[1:])
+    bci = np.concatenate([np.arange(l) for l in blen])
+    B = Host64(brp, bci, banded(rng, bci, np.float32, low=(0.05, 0.10)), len(blen), int(blen.max()))
+    return A, B, step64(A, B)
+
+
+@pytest.mark.parametrize("name", list(EPILOGUE_ROWS))
+@pytest.mark.parametrize("mode", ["float", "float-symbolic", "double"])
+def test_fused_epilogues_at_their_edges(handle, mode, name, monkeypatch):
+    dtype = np.float64 if mode == "double" else np.float32
+    if mode == "float-symbolic":
+        monkeypatch.setenv("SPGEMM_RMCL_SYMBOLIC", "1")
+    else:
+        monkeypatch.delenv("SPGEMM_RMCL_SYMBOLIC", raising=False)
+    A, B, step = epilogue_case(name)
+    spec = EPILOGUE_ROWS[name]
+    bound = step_bound(step.N, step.n, UNIT[dtype])
+    assert step.N == max(t for t, _ in spec) and list(np.diff(step.product.rowPtr)) == [l for _, l in spec]
+    assert float(step.gap.min()) >= 1000.0 * bound, f"bad input, smallest gap {step.gap.min():.3e} < 1000 * bound {bound:.3e}"
+    kept = np.diff(step.kept.rowPtr)
+    assert all(0 < k < l or l == 1 for k, (_, l) in zip(kept, spec)), "a row keeps all or nothing"
+    dA = hs.CSR.from_arrays(A.rowPtr, A.colInd, A.values, A.rows, A.cols, dtype=dtype).toGpuCSR()
+    dB = hs.CSR.from_arrays(B.rowPtr, B.colInd, B.values, B.rows, B.cols, dtype=dtype).toGpuCSR()
+    call = hs.rmcl_expand_prune_raw_f64 if mode == "double" else hs.rmcl_expand_prune_raw
+    try:
+        got = take(call(handle, dA.rowPtr, dA.colInd, dA.values, dA.nnz, dB.rowPtr, dB.colInd, dB.values, dB.nnz,
+                        A.rows, A.cols, B.cols), A.rows, B.cols, dtype)
+        bins = handle.stats()["bin_rows"]
+    finally:
+        dA.deviceDispose()
+        dB.deviceDispose()
+    products = [t * l for t, l in spec]
+    edges = [16, 64, 512, 2048, 4096, 1 << 30]                          # the last five bins, one numeric launch each
+    assert bins[-5:] == [sum(lo < p <= hi for p in products) for lo, hi in zip(edges[:-1], edges[1:])], bins
+    assert sum(bins) == len(spec)
+    assert got.values.dtype == dtype
+    assert np.array_equal(got.rowPtr, step.kept.rowPtr)
+    gc, gv = sorted_rows(got.rowPtr, got.colInd, got.values)
+    wc, wv = sorted_rows(step.kept.rowPtr, step.kept.colInd, step.kept.values)
+    assert np.array_equal(gc, wc), "kept columns"
+    if mode == "double":
+        err = np.abs(gv - wv)
+        print(f"{name} {mode}: kept {len(wv)}, worst relative error {float((err / wv).max()):.3e}, bound {bound:.3e}")
+        assert np.all(err <= bound * wv)
+    else:
+        ndiff, _, _ = assert_rmcl_step(got, po.CSRHost(A.rowPtr, A.colInd, A.values, A.rows, A.cols),
+                                       po.CSRHost(B.rowPtr, B.colInd, B.values, B.rows, B.cols), what=f"{name} {mode}")
+        assert ndiff == 0, f"{ndiff} rows differ from the oracle's"
