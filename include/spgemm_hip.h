@@ -198,7 +198,13 @@ int hip_rmcl_prune_n(spgemm_handle* h, int m, int nnz, const int* dIC, const int
  * (nlibs/gpus/gpu_csr_kernel.cu:281-311 with :218-270).  The product is never materialised: the numeric kernels apply
  * the row rule to each finished row in LDS and write only the kept entries.  Same results as hip_gpuSpMM followed by
  * hip_rmcl_prune up to the summation order of the row sums (entries within float rounding of the threshold).
- * Outputs allocated here (release with spgemm_hip_free); rows keep the order the product kernels emit (unsorted). */
+ * Outputs allocated here (release with spgemm_hip_free); rows keep the order the product kernels emit (unsorted).
+ * Domain (this call, its _f64 twin and the loops built on them): the squares of the product's entries are zero or normal
+ * numbers of the value type, i.e. |entry| is 0 or at least 2^-63 (float) / 2^-511 (double).  A kept value is
+ * v * (1 / kept sum) with one rounded reciprocal per row; a row that keeps a single entry gets 1.0 as such.  Where
+ * several kept squares add up to at most 2^-128 (2^-1024), which takes subnormal squares, the reciprocal overflows and
+ * the row's values are inf; hip_rmcl_prune divides and has no such limit.  On the edge of the domain (squares of
+ * 2^-126 / 2^-1022) every kernel gives the reference's values (tests/test_gpu_rmcl_rule_branches.py). */
 int hip_rmcl_expand_prune(spgemm_handle* h,
                           const int* dIA, const int* dJA, const float* dA, int nnzA,
                           const int* dIB, const int* dJB, const float* dB, int nnzB,

@@ -622,8 +622,8 @@ __device__ __forceinline__ int prune_emit_group(Tab t, int per, int want, bool b
     ks += (occ && v >= th) ? v : V(0);
   }
   ks = rowL_sum<L>(ks);
-  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks
-  int pos = 0;
+  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks,
+  int pos = 0;                                        // except v == ks (the row keeps one entry): v/ks is 1.0, stored as such
   for (int i0 = 0; i0 < per; i0 += L) {
     const auto sv = t.at(i0 + gl);
     const bool occ = live && (byKey ? sv.key() != EMPTY_KEY : i0 + gl < want);
@@ -632,7 +632,7 @@ __device__ __forceinline__ int prune_emit_group(Tab t, int per, int want, bool b
     const unsigned long long gm = group_mask<L>(ballot64(keep), gl);
     if (keep) {
       const int o = pos + __popcll(gm & ((1ull << gl) - 1ull));
-      if (store_ok<Tab>(o, want)) { st_out(JCrow + o, sv.key()); st_out(Crow + o, v * inv); }
+      if (store_ok<Tab>(o, want)) { st_out(JCrow + o, sv.key()); st_out(Crow + o, v == ks ? V(1) : v * inv); }
     }
     pos += __popcll(gm);
   }
@@ -712,7 +712,7 @@ __device__ __forceinline__ void prune_emit_block(Tab t, Lay lay, int want, Prune
   int pos = 0, total = 0;                             // this wave's first place: the waves before it, in wave order
 #pragma unroll
   for (int i = 0; i < NW; ++i) { ks += ps.ks[i]; pos += i < w ? ps.kc[i] : 0; total += ps.kc[i]; }
-  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks
+  const V inv = V(1) / ks;                            // one division per row; v*inv is within an ulp of v/ks (v == ks: 1.0, as above)
 #pragma unroll
   for (int sidx = 0; sidx < MAXSTEPS; ++sidx) {
     if (lay.live(sidx)) {
@@ -720,7 +720,7 @@ __device__ __forceinline__ void prune_emit_block(Tab t, Lay lay, int want, Prune
       const unsigned long long mk = ballot64(keep);
       if (keep) {
         const int o = pos + mask_rank(mk);
-        if (store_ok<Tab>(o, want)) { st_out(JCrow + o, k[sidx]); st_out(Crow + o, v[sidx] * inv); }
+        if (store_ok<Tab>(o, want)) { st_out(JCrow + o, k[sidx]); st_out(Crow + o, v[sidx] == ks ? V(1) : v[sidx] * inv); }
       }
       pos += __popcll(mk);
     }
