@@ -934,6 +934,50 @@ int hip_csr_symmetrize_f64(spgemm_handle* h, int mode, double alpha, double beta
                            const int* dIA, const int* dJA, const double* dA, int nnz,
                            int** dIS, int** dJS, double** dS, int* nnzS);
 
+/* ---- selection: the k largest entries of every row (mcl's -S, HipMCL's select), and the R-MCL loop with that row cap ----
+ * The reference has no counterpart (its row rule only thresholds); the semantics are pinned by tests/topk_ref.py.  All
+ * arrays are device pointers; array outputs come from the library pool (release with spgemm_hip_free); h == NULL = the
+ * default handle; a call returns after its device work has completed.  Argument checks (a null output other than rowsCut,
+ * k < 1, a flag bit other than SPGEMM_TOPK_NORMALISE, negative sizes, null arrays) -> SPGEMM_ERR_ARG before any device
+ * work, with the outputs null / 0; a rowPtr that is not a monotone row pointer ending at nnz or a column outside [0,n)
+ * -> SPGEMM_ERR_INPUT.
+ *
+ * hip_csr_row_topk: row i of N keeps the min(len_i, k) best entries of row i of A IN THEIR STORAGE ORDER.  Entry a beats
+ * entry b iff va > vb, or va == vb and ca < cb, or both are equal and a is stored before b (rows may repeat a column).
+ * Values are compared in their own type.  -0.0 == +0.0 (the column decides); a NaN ranks below every number, -inf
+ * included, and among NaNs the column decides, then the position.  A row with len_i <= k is copied bit for bit (NaN
+ * payloads, -0.0, denormals), so k >= the longest row returns a bit-identical copy.  *rowsCut (optional) = the rows with
+ * len_i > k.  SPGEMM_TOPK_NORMALISE divides the kept values of the CUT rows, and of those only, by their sum: the sum is
+ * formed in double for both value types in a fixed reduction tree (the same bits on every call), rounded to the value
+ * type, and divides each kept value by one IEEE division in the value type.  That is meant for kept values that are
+ * finite and non-negative with a positive sum; otherwise the values are whatever the division gives, and no error is
+ * raised.  Selection, not a sort; no floating-point atomic.
+ * hip_csr_row_topk_limits (pure host): rows of up to *waveCap entries are cut by one wave each with the row in registers,
+ * rows of up to *blockCap entries by one block each with the row in LDS, longer rows by a block that re-reads them.
+ * spgemm_hip_debug_topk_paths (test hook): the rows hip_csr_row_topk has handled on this handle since it was created:
+ * copied uncut, cut by the wave / block / stream path (any pointer may be NULL).
+ *
+ * hip_gpuRmclIter_device_topk: hip_gpuRmclIter_device with a row cap.  Every iteration is
+ * X = hip_rmcl_expand_prune(Mgt, Mt), Mt = hip_csr_row_topk(X, k, SPGEMM_TOPK_NORMALISE): composed from the packed public
+ * step, so Mt is packed after every iteration.  iterNnz / iterCut: the caller's arrays of maxIter entries, or NULL: the
+ * entries of Mt after the selection of iteration i and the rows it cut.  maxIter == 0 returns a copy of Mt.  k < 1 ->
+ * SPGEMM_ERR_ARG; otherwise the argument checks of hip_gpuRmclIter_device. */
+#define SPGEMM_TOPK_NORMALISE 1
+int hip_csr_row_topk(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const float* dA,
+                     int k, int flags, int** dIN, int** dJN, float** dAN, int* nnzN, int* rowsCut);
+int hip_csr_row_topk_f64(spgemm_handle* h, int m, int n, int nnz, const int* dIA, const int* dJA, const double* dA,
+                         int k, int flags, int** dIN, int** dJN, double** dAN, int* nnzN, int* rowsCut);
+int hip_csr_row_topk_limits(int isDouble, int* waveCap, int* blockCap);
+int spgemm_hip_debug_topk_paths(spgemm_handle* h, long long* copied, long long* wave, long long* block, long long* stream);
+int hip_gpuRmclIter_device_topk(spgemm_handle* h, int maxIter, int k, int rows, int cols,
+                                const int* dgI, const int* dgJ, const float* dgA, int gnnz,
+                                const int* dtI, const int* dtJ, const float* dtA, int tnnz,
+                                int** oI, int** oJ, float** oA, int* onnz, long long* iterNnz, long long* iterCut);
+int hip_gpuRmclIter_device_topk_f64(spgemm_handle* h, int maxIter, int k, int rows, int cols,
+                                    const int* dgI, const int* dgJ, const double* dgA, int gnnz,
+                                    const int* dtI, const int* dtJ, const double* dtA, int tnnz,
+                                    int** oI, int** oJ, double** oA, int* onnz, long long* iterNnz, long long* iterCut);
+
 /* ---- (5) double values: the reference built with FDOUBLE (QValue double, nlibs/tools/macro.h:3-6) ----------------------
  * The same semantics as the float twins above (argument checks, status codes, h == NULL = the default handle, outputs
  * from the library pool / malloc(), rows of C column-unsorted); only the value type differs.  The classification,

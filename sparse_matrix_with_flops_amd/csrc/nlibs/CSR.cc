@@ -431,6 +431,25 @@ CSR gpuAddWrapper(const CSR& dA, const CSR& dB, QValue alpha, QValue beta) {
   return dC;
 }
 
+CSR CSR::gpuRowTopK(int k, int flags) const {
+  CSR dN;
+  hip_or_die(hip_csr_row_topk(NULL, rows, cols, nnz, rowPtr, colInd, values, k, flags, &dN.rowPtr, &dN.colInd, &dN.values,
+                              &dN.nnz, NULL), "gpuRowTopK");
+  dN.rows = rows;
+  dN.cols = cols;
+  return dN;
+}
+
+CSR gpuRmclIterTopK(const int maxIter, const int k, const CSR& dMgt, const CSR& dMt) {
+  CSR dN;
+  hip_or_die(hip_gpuRmclIter_device_topk(0, maxIter, k, dMt.rows, dMt.cols, dMgt.rowPtr, dMgt.colInd, dMgt.values, dMgt.nnz,
+                                         dMt.rowPtr, dMt.colInd, dMt.values, dMt.nnz, &dN.rowPtr, &dN.colInd, &dN.values,
+                                         &dN.nnz, NULL, NULL), "gpuRmclIterTopK");
+  dN.rows = dMt.rows;
+  dN.cols = dMt.cols;
+  return dN;
+}
+
 CSR gpuSymmetrize(const CSR& dA, int mode, QValue alpha, QValue beta) {
   if (dA.rows != dA.cols) {
     printf("gpuSymmetrize: the matrix is %d x %d, not square\n", dA.rows, dA.cols);

@@ -79,5 +79,11 @@ struct CSR {
   QValue gpuDiffers(const CSR& dB) const;
   std::vector<int> gpuDiffersStats(const CSR& dB, const std::vector<QValue>& percents) const;
   bool gpuIsEqual(const CSR& dB) const;
+
+  // selection on a DEVICE CSR (hip_csr_row_topk; no counterpart in the reference, whose row rule only thresholds): every
+  // row keeps its min(len, k) best entries in storage order -- larger value, then smaller column, then earlier position,
+  // NaN last -- as a new DEVICE CSR.  flags: 0 or SPGEMM_TOPK_NORMALISE (the kept values of the rows that were cut are
+  // divided by their sum).  Exits on error.
+  CSR gpuRowTopK(int k, int flags = 0) const;
 };
 #endif

@@ -17,6 +17,9 @@ CSR scudaSpMM(const CSR& hA, const CSR& hB);
 void gpuRmclIter(const int maxIter, const CSR Mgt, CSR& Mt);
 // the same loop on DEVICE CSRs (hip_gpuRmclIter_device): returns the new Mt as a device CSR, the inputs are left alone
 CSR gpuRmclIterDevice(const int maxIter, const CSR& dMgt, const CSR& dMt);
+// the same loop with a row cap (mcl's -S, HipMCL's select; hip_gpuRmclIter_device_topk): after every iteration each row of
+// Mt keeps its k largest entries (CSR::gpuRowTopK with SPGEMM_TOPK_NORMALISE).  DEVICE CSRs in, a DEVICE CSR out.
+CSR gpuRmclIterTopK(const int maxIter, const int k, const CSR& dMgt, const CSR& dMt);
 // Several GPUs (no counterpart in the reference, which is single-device: SURVEY.md section 2.4; the seam is the flops-balanced
 // row cut its CPU kernels make for their threads, nlibs/tools/util.cc:123-135).  HOST CSRs in, HOST CSR out: rows of A cut
 // into `shards` blocks of equal flops, one shard per device (shards > devices: logical shards share devices), B replicated,

@@ -370,6 +370,7 @@ struct spgemm_handle {
   spgemm_stats stats;
   spgemm_host_api_stats host_api = {};   // phases of the latest hip_CSR_SpMM
   int failNext = 0;                  // test hook (spgemm_hip_debug_fail_next): the next symbolic phase / R-MCL step on this handle fails
+  long long topkRows[4] = {0, 0, 0, 0};  // hip_csr_row_topk calls on this handle so far: rows copied / cut by the wave, block, stream path
   int prev_m = -1;                   // shape and sizes of the previous one-shot SpGEMM (allocation policy of the next one)
   unsigned long long prev_P = 0;
   long long prev_nnzC = -1;
@@ -2685,7 +2686,12 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
 // ------------------------------------------------------------------------------------------------
 #include "symmetrize_device.hpp"
 
-#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the eleven headers above
+// ------------------------------------------------------------------------------------------------
+// selection: the k largest entries of every row, and the R-MCL loop with that row cap
+// ------------------------------------------------------------------------------------------------
+#include "topk_device.hpp"
+
+#undef CSR_ALLOC                                   // csr_common_device.hpp's pair, used by the twelve headers above
 #undef CSR_HIP
 
 // ------------------------------------------------------------------------------------------------

@@ -85,7 +85,10 @@ EXPORTS = [
     "hip_gpuRmclIter_f64",
     "hip_csr_add", "hip_csr_add_f64", "hip_csr_scale", "hip_csr_scale_f64", "hip_csr_col_counts",
     "hip_degree_factors", "hip_degree_factors_f64", "hip_csr_symmetrize", "hip_csr_symmetrize_f64",
+    "hip_csr_row_topk", "hip_csr_row_topk_f64", "hip_csr_row_topk_limits", "spgemm_hip_debug_topk_paths",
+    "hip_gpuRmclIter_device_topk", "hip_gpuRmclIter_device_topk_f64",
 ]
+TOPK_NORMALISE = 1
 SYM_SUM, SYM_BIBLIOMETRIC, SYM_DEGREE_DISCOUNTED = 0, 1, 2
 PCSR_MAX_BLOCKS = 64
 BCSR_MAX_TILE = 4096
@@ -303,6 +306,14 @@ def lib():
         L.hip_csr_symmetrize.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int] + dev_in + \
             [C.POINTER(C.c_void_p)] * 3 + [_I]
         L.hip_csr_symmetrize_f64.argtypes = L.hip_csr_symmetrize.argtypes
+        L.hip_csr_row_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_int] + [C.POINTER(C.c_void_p)] * 3 + [_I, _I]
+        L.hip_csr_row_topk_f64.argtypes = L.hip_csr_row_topk.argtypes
+        L.hip_csr_row_topk_limits.argtypes = [C.c_int, _I, _I]
+        L.spgemm_hip_debug_topk_paths.argtypes = [C.c_void_p] + [C.POINTER(C.c_longlong)] * 4
+        L.hip_gpuRmclIter_device_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + dev_in + dev_in + \
+            [C.POINTER(C.c_void_p)] * 3 + [_I, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.hip_gpuRmclIter_device_topk_f64.argtypes = L.hip_gpuRmclIter_device_topk.argtypes
         L.spgemm_hip_selftest.argtypes = [C.c_void_p]
         L.spgemm_hip_set_kernel_timing.argtypes = [C.c_void_p, C.c_uint]
         host_in = [_I, _I, _F, C.c_int]
@@ -483,6 +494,11 @@ class Handle:
         k = [C.c_longlong(0) for _ in range(2)]
         _check(lib().spgemm_hip_debug_midrow_sym_paths(self._h, *[C.byref(x) for x in k]), "spgemm_hip_debug_midrow_sym_paths")
         return {"pair": k[0].value, "multiwave": k[1].value}
+
+    def topk_paths(self):
+        """test hook: the rows hip_csr_row_topk has handled on this handle since it was created: copied uncut / cut by the
+        wave, the block and the stream path"""
+        return topk_paths(self)
 
     def close(self):
         if self._h and self._own:
@@ -678,6 +694,19 @@ class CSR:
             i, j, v, nnz = csr_symmetrize_raw(handle, mode, alpha, beta, d.rows, d.rowPtr, d.colInd, d.values, d.nnz, dtype=dt)
             return CSR(v, j, i, d.rows, d.cols, nnz, True, dtype=d.dtype)
         return self._on_device(run)
+
+    def row_topk(self, k, normalise=False, handle=None):
+        """hip_csr_row_topk / _f64 on a device CSR -> device CSR: every row keeps its min(len, k) best entries in storage
+        order (larger value, then smaller column, then earlier position; NaN last); rows_cut on the result says how many
+        rows lost entries.  normalise: the kept values of the cut rows are divided by their sum."""
+        if not self.on_device:
+            raise SpgemmError("row_topk: takes a device CSR")
+        dt = _value_dtype(self.dtype)
+        i, j, v, nnz, cut = csr_row_topk_raw(handle, self.rows, self.cols, self.nnz, self.rowPtr, self.colInd, self.values,
+                                             k, TOPK_NORMALISE if normalise else 0, dtype=dt)
+        out = CSR(v, j, i, self.rows, self.cols, nnz, True, dtype=self.dtype)
+        out.rows_cut = cut
+        return out
 
     def rowDescendingOrderPermutation(self, handle=None):
         """CSR::rowDescendingOrderPermutation (nlibs/CSR.cc:484-494) -> host int32[rows]: rows by descending length, rows
@@ -1161,6 +1190,21 @@ def gpuRmclIter_device(maxIter, Mgt, Mt, handle=None):
     i_, j_, c_, n_ = _rmcl_iter_device(dtype, handle, maxIter, Mgt.rows, Mgt.cols, Mgt.rowPtr, Mgt.colInd, Mgt.values, Mgt.nnz,
                                        Mt.rowPtr, Mt.colInd, Mt.values, Mt.nnz)
     return CSR(c_, j_, i_, Mt.rows, Mt.cols, n_, on_device=True, dtype=dtype)
+
+
+def gpuRmclIterTopK_device(maxIter, k, Mgt, Mt, handle=None):
+    """hip_gpuRmclIter_device_topk / _f64 on device CSRs: gpuRmclIter_device with every row of Mt cut to its k largest
+    entries (and renormalised) after every iteration -> (Mt, iter_nnz, iter_cut): the new Mt as a device CSR, per iteration
+    the entries after the selection and the rows it cut."""
+    assert Mgt.on_device and Mt.on_device
+    dtype = _common_dtype(Mgt, Mt)
+    n = max(int(maxIter), 0)
+    out, inz, icut = _CsrOut(), (C.c_longlong * max(n, 1))(), (C.c_longlong * max(n, 1))()
+    _call("hip_gpuRmclIter_device_topk", dtype, _hp(handle), int(maxIter), int(k), Mgt.rows, Mgt.cols,
+          *_ptrs(Mgt.rowPtr, Mgt.colInd, Mgt.values), Mgt.nnz, *_ptrs(Mt.rowPtr, Mt.colInd, Mt.values), Mt.nnz, *out.refs(),
+          inz, icut)
+    i_, j_, c_, n_ = out.values()
+    return CSR(c_, j_, i_, Mt.rows, Mt.cols, n_, on_device=True, dtype=dtype), list(inz)[:n], list(icut)[:n]
 
 
 def gpuRmclIter(maxIter, Mgt, Mt):
@@ -2104,3 +2148,30 @@ def csr_symmetrize_raw(handle, mode, alpha, beta, m, IA, JA, VA, nnz, dtype=np.f
     _call("hip_csr_symmetrize", dtype, _hp(handle), int(mode), float(alpha), float(beta), int(m), *_ptrs(IA, JA, VA),
           int(nnz), *out.refs())
     return out.values()
+
+
+# ---------------------------------------------------------------------------------------------
+# selection (include/spgemm_hip.h "selection: the k largest entries of every row"); CSR.row_topk is the object form and
+# gpuRmclIterTopK_device the loop with the row cap.  The reference has no counterpart: its row rule only thresholds.
+# ---------------------------------------------------------------------------------------------
+def csr_row_topk_raw(handle, m, n, nnz, IA, JA, VA, k, flags=0, dtype=np.float32):
+    """hip_csr_row_topk / _f64 on raw device pointers -> (dIN, dJN, dAN, nnzN, rowsCut); the arrays are the library pool's"""
+    out, cut = _CsrOut(), C.c_int(0)
+    _call("hip_csr_row_topk", dtype, _hp(handle), int(m), int(n), int(nnz), *_ptrs(IA, JA, VA), int(k), int(flags),
+          *out.refs(), C.byref(cut))
+    return out.values() + (cut.value,)
+
+
+def row_topk_limits(dtype=np.float32):
+    """hip_csr_row_topk_limits (pure host) -> (waveCap, blockCap): the longest row the wave path / the block path cuts"""
+    w, b = C.c_int(0), C.c_int(0)
+    _check(lib().hip_csr_row_topk_limits(int(_value_dtype(dtype) == np.float64), C.byref(w), C.byref(b)),
+           "hip_csr_row_topk_limits")
+    return w.value, b.value
+
+
+def topk_paths(handle=None):
+    """spgemm_hip_debug_topk_paths of a Handle (None: the default handle) -> {"copied", "wave", "block", "stream"}"""
+    v = [C.c_longlong(0) for _ in range(4)]
+    _check(lib().spgemm_hip_debug_topk_paths(_hp(handle), *[C.byref(x) for x in v]), "spgemm_hip_debug_topk_paths")
+    return dict(zip(("copied", "wave", "block", "stream"), (x.value for x in v)))
