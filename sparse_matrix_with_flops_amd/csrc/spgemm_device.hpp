@@ -35,7 +35,7 @@ __device__ int g_ablate = 0;
 #define ABL(bit) (g_ablate & (bit))
 // error flags (int*) are not raised in this build: with pieces switched off every row "fails" and the flag word serialises
 __device__ __forceinline__ void smf_or(int*, int) {}
-__device__ __forceinline__ void smf_or(unsigned* p, unsigned v) { atomicOr(p, v); }
+__device__ __forceinline__ unsigned smf_or(unsigned* p, unsigned v) { return atomicOr(p, v); }   // (k_sym_big<true> reads the old word)
 #define atomicOr(p, v) smf_or((p), (v))
 #else
 #define ABL(bit) 0
@@ -1469,7 +1469,8 @@ __device__ __forceinline__ RowMeta load_meta_sym(const int* rows, int q, int cou
   if (q < count) { mtd.row = rows[q]; mtd.as = IA[mtd.row]; mtd.ae = IA[mtd.row + 1]; mtd.x0 = rowFlops[mtd.row]; }
   return mtd;
 }
-__device__ __forceinline__ RowMeta load_meta_num(const int* rows, int q, int count, const int* IA, const int* IC,
+template <class Rows>
+__device__ __forceinline__ RowMeta load_meta_num(const Rows& rows, int q, int count, const int* IA, const int* IC,
                                                  const int* rowFlops = nullptr) {
   RowMeta mtd{0, 0, 0, 0, 0, 0};
   if (q < count) {
@@ -1488,18 +1489,62 @@ __device__ __forceinline__ PreA load_pre(const RowMeta& mtd, const int2* SBL, co
 }
 
 // ------------------------------------------------------------------------------------------------
-// Medium rows (65..4096 products): one block of NW waves per row, LDS key table (symbolic) or
-// key+value table compacted by a table sweep (numeric).
+// The re-hit log kit: "log the repeats, store the rest direct", the default path of a float product's rows of 513 products
+// and more.  The scheme, once:
+// SYMBOLIC pass (k_sym_hash<.., true>, k_sym_midpair, k_sym_big<true>): the insert says which products are RE-HITS of a
+// column the row already has.  Every wave compacts the re-hit columns of a trip (ballot + rank + one LDS counter add) and
+// appends them to the row's stretch of a log in HBM (rehit_log_append); nothing is deduplicated, a column hit k times is
+// logged k-1 times, so a row logs exactly products - IC[row] entries.  The row's metadata is {first log entry, re-hits};
+// the count is -1 when the row logged more than `cap` entries or found no room -- such a row leaves the log as it found
+// it and goes on a fallback list for the kernel with the full table.  Where the log space comes from is the kernel's:
+// chunks off one global cursor for the mid rows (LogChunk), a region per block for the big ones.
+// NUMERIC pass (k_num_bigdirect, k_num_middirect, k_num_midwave): a table of at most S (key, value) slots that holds ONLY
+// the row's repeated columns.  The log is inserted first (fill_from_log), every key with the value bits of -0.0f (the
+// additive identity: a column hit twice ends as exactly a + b, as in the full-table kernels).  Then the products are
+// walked once and probe READ-ONLY (probe_rounds): a hit adds its value under EXEC; a miss -- the probe meets an empty
+// slot -- is a product whose column occurs once in the row, and goes straight to JC/C at the next free position of the
+// row's range (ballot rank; where the position comes from is the kernel's policy).  The table sweep then emits the
+// repeated columns behind them.  A row is taken only with 0 <= re-hits <= cap <= bd_cap(S) (load_meta_logged), so the
+// table can never fill up and every probe ends at an empty slot; the other rows are skipped, they are in the fallback
+// list.  A row without any repeated column (IC range = products) is EXPANDED (expanded_store): no table at all.
 // ------------------------------------------------------------------------------------------------
-// LOG (NW > 1, bins 6-7 of a float product, for k_num_middirect): the insert says which products are RE-HITS of a column the
-// row already has.  Every wave compacts the re-hit columns of a trip (ballot + rank + one LDS counter add) and appends them
-// to the row's stretch of the log in HBM; nothing is deduplicated, a column hit k times is logged k-1 times, so a row logs
-// exactly products - IC[row] entries.  Log space: a block reserves CHUNKS of MD_CHUNK ints from one global cursor (one
-// global atomic per chunk, not per row) and fills its chunk front to back over its rows; a row starts only with `cap` ints
-// left in the chunk, so it can run out of room only by passing the cap.  meta[row] = {first log entry, re-hits}; the count
-// is -1 when the row logged more than cap entries or its chunk lies beyond the log's capacity (the cursor keeps counting
-// there: its final value is the space the call would have used, which sizes the log of the handle's next call).  Such rows
-// go to fbList, *fbCount counts them, and they leave their chunk as they found it.
+// re-hits a row may log and still take a direct kernel with a table of S slots: the distinct repeated columns are at most
+// the re-hits, so the table is never more than 7/8 full
+__host__ __device__ constexpr int bd_cap(int S) { return S / 8 * 7; }
+
+// ---- symbolic side
+// The re-hit columns of one trip of a wave, appended to the row's log stretch of `room` ints from myLog[first] on.  *logCnt:
+// the row's re-hits so far (LDS); *logOvf: set when the row passes `room` -- then nothing more is stored, the row falls back.
+// (`first` is k_sym_big's place in its block's region, an index apart from the pointer: folded into it, that kernel comes
+// out with two more VGPRs; the chunk kernels pass their row's own pointer and 0.)
+template <int R>
+__device__ __forceinline__ void rehit_log_append(const bool (&rehit)[R], const int (&col)[R], int* logCnt, int* logOvf,
+                                                 int* myLog, int first, int room) {
+  unsigned long long mk[R];
+  int tot = 0;
+#pragma unroll
+  for (int u = 0; u < R; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
+  if (tot) {                                             // wave-uniform
+    int base = 0;
+    if (lane_id() == 0) base = atomicAdd(logCnt, tot);
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (base + tot > room) {                             // wave-uniform: a row for the fallback kernel
+      if (lane_id() == 0) *logOvf = 1;
+    } else {
+#pragma unroll
+      for (int u = 0; u < R; ++u) {                      // base + tot <= room: inside the stretch
+        if (rehit[u]) myLog[first + base + mask_rank(mk[u])] = col[u];
+        base += __popcll(mk[u]);
+      }
+    }
+  }
+}
+
+// Log space of the mid rows (bins 6-7): CHUNKS of MD_CHUNK ints reserved from one global cursor (one global atomic per
+// chunk, not per row) and filled front to back over the rows of a block (k_sym_midpair's light rows: of a half).  A row
+// starts only with `cap` ints left in the chunk, so it can run out of room only by passing the cap.  A chunk that lies
+// beyond the log's capacity logs nothing (the cursor keeps counting there: its final value is the space the call would
+// have used, which sizes the log of the handle's next call); its rows fall back, *fbCount counts them.
 constexpr int MD_CHUNK = 4096;                 // log ints per reservation: at least two rows at the largest cap (bd_cap(2048) = 1792),
                                                // about 50 rows of the headline matrix (60 re-hits per row on average)
 struct MidLogArgs {
@@ -1512,6 +1557,184 @@ struct MidLogArgs {
   int* fbCount;
   unsigned long long* logged;                  // sum of the re-hits of the rows that stay direct (test hook)
 };
+// The chunk in use, uniform over the threads that share a row.  A row: is_full() -> one thread reserve()s into an LDS word,
+// barrier, take(word); the walk appends to log() within room(); behind the barrier after the walk, finish().
+struct LogChunk {
+  unsigned long long start = 0ull;             // first int of the chunk
+  int used = MD_CHUNK;                         // ints of it in use (MD_CHUNK: none reserved yet)
+  unsigned long long directSum = 0ull;         // re-hits of the rows that stayed direct (test hook), kept by the threads that `sums`
+  __device__ __forceinline__ bool is_full(const MidLogArgs& ml) const { return used + ml.cap > MD_CHUNK; }   // may not hold another row
+  __device__ __forceinline__ static unsigned long long reserve(const MidLogArgs& ml) {
+    return atomicAdd(ml.cursor, (unsigned long long)MD_CHUNK);
+  }
+  __device__ __forceinline__ void take(unsigned long long s) { start = s; used = 0; }
+  __device__ __forceinline__ bool logging(const MidLogArgs& ml) const {
+    return start + (unsigned long long)MD_CHUNK <= (unsigned long long)ml.logCap;
+  }
+  __device__ __forceinline__ int* log(const MidLogArgs& ml) const { return ml.log + start + used; }
+  __device__ __forceinline__ int room(const MidLogArgs& ml) const { return min(ml.cap, MD_CHUNK - used); }   // (= cap; the chunk bounds every store whatever cap is)
+  // The row is done (logging: what logging() said before its walk): `products` of them on `cnt` distinct columns, `logged`
+  // re-hits counted, ovf: it passed room().  The `leader` thread writes the row's count and metadata.  A row that stays
+  // direct has logged <= room <= cap.  (The sum is kept in here and the flag handed in: with finish() returning `direct`
+  // to a sum of the caller's, k_sym_midpair spills nine more SGPRs.)
+  __device__ __forceinline__ void finish(const MidLogArgs& ml, bool logging, bool leader, bool sums, int row, int products,
+                                         int cnt, int logged, bool ovf, int* __restrict__ IC) {
+    const int rehits = products - cnt;                   // what the row logs when it has room
+    const bool direct = logging && !ovf;
+    if (leader) {
+      IC[row] = cnt;
+      ml.meta[row] = make_int2((int)start + used, direct ? logged : -1);
+      if (!direct) ml.fbList[atomicAdd(ml.fbCount, 1)] = row;
+    }
+    if (direct) { used += logged; if (sums) directSum += (unsigned long long)logged; }
+    else if (!logging && rehits >= 0 && rehits <= ml.cap) used += rehits;   // no log yet: count the demand
+  }
+};
+
+// ---- numeric side
+// A row's log into its cleared table: distinct keys <= lc <= cap < S, or size >= 4 * lc
+__device__ __forceinline__ void fill_from_log(slot_t* tab, int size, int shift, const int* __restrict__ lg, int lc, int tid,
+                                              int nthreads) {
+  const unsigned mask = (unsigned)size - 1u;
+  for (int i = tid; i < lc; i += nthreads) {
+    const int c = lg[i];
+    const slot_t own = make_slot(c, -0.0f);
+    unsigned h = ((unsigned)c * 2654435761u) >> shift;
+    for (int probe = 0; probe < size; ++probe) {
+      const slot_t old = atomicCAS(&tab[h], EMPTY_SLOT, own);
+      if (old == EMPTY_SLOT || slot_key(old) == c) break;
+      h = (h + 1u) & mask;
+    }
+  }
+}
+
+// U rounds of products against the table of the row's repeated columns (`base`; dumB: this lane's dummy word, as a byte
+// offset from it), keys read-only: a hit adds under EXEC, missOut[u] says that the product met an empty slot.  (The misses
+// are gathered in an array of the helper's own and copied out once: gathered through the reference, or handed on to a
+// functor, the compiler keeps them packed in bytes -- 16 to 116 more instructions per kernel, and a lower occupancy.)
+template <int U>
+__device__ __forceinline__ void probe_rounds(char* base, int dumB, int size, int shift, const bool (&act)[U],
+                                             const int (&col)[U], const float (&val)[U], int* __restrict__ err,
+                                             bool (&missOut)[U]) {
+  const int maskB = size * 8 - 1;
+  int hB[U], hitB[U];                                  // byte offsets; dumB = "done" / "no hit"
+  bool miss[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
+    hB[u] = act[u] ? (int)(h * 8u) : dumB;
+    hitB[u] = dumB;
+    miss[u] = false;
+  }
+  for (int probe = 0;;) {                              // the keys do not change during the walk: plain reads
+    int key[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
+    ++probe;
+    int pendBits = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool pend = hB[u] != dumB;
+      const bool hit = pend && key[u] == col[u];
+      const bool emp = pend && key[u] == EMPTY_KEY;
+      hitB[u] = hit ? hB[u] : hitB[u];
+      miss[u] = miss[u] || emp;
+      hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like fill_from_log
+      pendBits |= hB[u] ^ dumB;
+    }
+    if (ballot64(pendBits != 0) == 0ull) break;
+    if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
+#pragma unroll
+  for (int u = 0; u < U; ++u) missOut[u] = miss[u];
+}
+// The misses of U rounds go to the next free positions of the row's range of `lim` entries, in ballot rank order.  Where
+// the position comes from is the kernel's: a register of the wave kernel -- returns the position behind the misses --
+template <int U>
+__device__ __forceinline__ int store_misses(const bool (&miss)[U], const int (&col)[U], const float (&val)[U], int pos,
+                                            unsigned lim, int* __restrict__ JCrow, float* __restrict__ Crow) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned long long mk = ballot64(miss[u]);
+    const unsigned o = (unsigned)(pos + mask_rank(mk));
+    if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+    pos += __popcll(mk);
+  }
+  return pos;
+}
+// ... or the row's LDS counter of the block kernels, drawn from once per trip for all U rounds together
+template <int U>
+__device__ __forceinline__ void store_misses_claimed(const bool (&miss)[U], const int (&col)[U], const float (&val)[U],
+                                                     int* emitted, unsigned lim, int* JCrow, float* Crow) {
+  unsigned long long mk[U];
+  int tot = 0;
+#pragma unroll
+  for (int u = 0; u < U; ++u) { mk[u] = ballot64(miss[u]); tot += __popcll(mk[u]); }
+  if (tot) {                                           // wave-uniform
+    int pos = 0;
+    if (lane_id() == 0) pos = atomicAdd(emitted, tot);
+    pos = __builtin_amdgcn_readfirstlane(pos);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const unsigned o = (unsigned)(pos + mask_rank(mk[u]));
+      if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+      pos += __popcll(mk[u]);
+    }
+  }
+}
+
+// An expanded row: no repeated column, so every product goes to its number in the walk.  The walk's functor for such a
+// row, over the caller's own variables (`lane`: its lane id) like the lambdas it stands for: as a helper called from a
+// lambda, or with copies of them, k_num_middirect and k_num_midwave come out with three to five VGPRs fewer -- another
+// occupancy figure than the kernels were measured with, which is not this code's to change.
+__device__ __forceinline__ auto expanded_store(const int& lane, const unsigned& lim, int* const& JCrow, float* const& Crow) {
+  return [&](const auto& act, const auto& col, const auto& val, int p0) {
+    constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
+#pragma unroll
+    for (int u = 0; u < R; ++u) {
+      const unsigned o = (unsigned)(p0 + u * WAVE + lane);
+      if (act[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
+    }
+  };
+}
+
+// Bin 6 has two direct kernels: k_num_midwave (one wave per row, a table of MW_SLOTS slots) and k_num_middirect.  THE rule
+// for which of the two takes a row, read by both: the wave kernel takes the rows that logged (lm = the row's {first log
+// entry, re-hits}) at most waveCap <= bd_cap(MW_SLOTS) re-hits and whose log lies inside the log; k_num_middirect keeps the
+// other rows up to its own cap.  waveCap < 0: no wave kernel in this call (bin 7, SPGEMM_MD_WAVE=0, a bin below the row
+// threshold).
+constexpr int MW_SLOTS = 512;
+__device__ __forceinline__ bool midwave_takes(int2 lm, long long logCap, int waveCap) {
+  return lm.y >= 0 && lm.y <= waveCap && lm.x >= 0 && (long long)lm.x + lm.y <= logCap;
+}
+// Row q of `rows` (rows[q], q < count) with its log, fetched one row ahead like RowMeta: ls = first log entry, lc = re-hits,
+// or -1 for a row that is not this kernel's.  lm = meta[q] (byRow: meta[row id]); take(lm) is the kernel's rule: > 0 the
+// row is taken, 0 it is skipped, < 0 (k_num_midwave) it is left to another list: lc = -1, ls = 1 and the row id.
+struct LoggedMeta { RowMeta m; int ls, lc; };
+template <class Rows, class Take>
+__device__ __forceinline__ LoggedMeta load_meta_logged(const Rows& rows, int q, int count, const int* IA, const int* IC,
+                                                       const int* rowFlops, const int2* meta, bool byRow, Take take) {
+  LoggedMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
+  if (q < count) {
+    const int row = rows[q];
+    const int2 lm = meta[byRow ? row : q];
+    const int t = take(lm);
+    if (t > 0) {
+      d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC, rowFlops);
+    } else if (t < 0) { d.ls = 1; d.m.row = row; }
+  }
+  return d;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Medium rows (65..4096 products): one block of NW waves per row, LDS key table (symbolic) or
+// key+value table compacted by a table sweep (numeric).
+// ------------------------------------------------------------------------------------------------
+// LOG (NW > 1, bins 6-7 of a float product, for k_num_middirect): the logging symbolic pass of the kit above, log space in
+// chunks (LogChunk).
 
 template <int NW, int TBL, int U, bool LOG = false>
 __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ binPtr, int bin,
@@ -1527,10 +1750,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
   __shared__ int qslot;
   __shared__ int logCnt_s, logOvf_s;             // LOG: re-hits of the current row so far; the row passed the cap
   __shared__ unsigned long long chunk_s;         // LOG: the chunk reserved last
-  // LOG, block-uniform: first int of the block's chunk, ints of it in use (MD_CHUNK: none reserved yet), re-hits of direct rows
-  unsigned long long chunkStart = 0ull;
-  int cursor = MD_CHUNK;
-  unsigned long long loggedSum = 0ull;
+  LogChunk chunk;                                // LOG, block-uniform: the block's chunk
   const int tid = threadIdx.x, lane = lane_id();
   if (tid < WAVE) st.dummy[tid] = DUMMY_SLOT;    // (ordered before the first insert by the barrier / wave order below)
   int first = binPtr[bin], count = binPtr[bin + 1] - first;
@@ -1562,17 +1782,17 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
     const int shift = 32 - log2_pow2(size);
     clear_table(keys, nullptr, size, tid, WAVE * NW);
     if (tid == 0) cnt_s = 0;
-    const bool newChunk = LOG && cursor + ml.cap > MD_CHUNK;   // block-uniform: the chunk may not hold another row
+    const bool newChunk = LOG && chunk.is_full(ml);   // block-uniform
     if constexpr (LOG) if (tid == 0) {
       logCnt_s = 0; logOvf_s = 0;
-      if (newChunk) chunk_s = atomicAdd(ml.cursor, (unsigned long long)MD_CHUNK);
+      if (newChunk) chunk_s = LogChunk::reserve(ml);
     }
     __syncthreads();
-    if constexpr (LOG) if (newChunk) { chunkStart = chunk_s; cursor = 0; }
+    if constexpr (LOG) if (newChunk) chunk.take(chunk_s);
     // (chunk_s is written again at the start of a later row, behind this row's barriers)
-    const bool logging = LOG && chunkStart + (unsigned long long)MD_CHUNK <= (unsigned long long)ml.logCap;
-    int* const myLog = LOG && logging ? ml.log + chunkStart + cursor : nullptr;
-    const int room = LOG ? min(ml.cap, MD_CHUNK - cursor) : 0;   // (= cap; the chunk bounds every store whatever cap is)
+    const bool logging = LOG && chunk.logging(ml);
+    int* const myLog = LOG && logging ? chunk.log(ml) : nullptr;
+    const int room = LOG ? chunk.room(ml) : 0;
     int mine = 0;
     for_each_product<NW, U, false>(st, cur.as, cur.ae, SBL, nullptr, JB, nullptr,
                                    [&](const auto& act, const auto& col, const auto& val, int) {
@@ -1583,26 +1803,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
         bool rehit[R];
         mine += hash_insert_chunked<InsChunk<NW>::value, true>(keys, size, shift, act, col,
                                                                reinterpret_cast<int*>(&st.dummy[lane_id()]), err, &rehit);
-        if (logging) {                                   // block-uniform
-          unsigned long long mk[R];
-          int tot = 0;
-#pragma unroll
-          for (int u = 0; u < R; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
-          if (tot) {                                     // wave-uniform
-            int base = 0;
-            if (lane_id() == 0) base = atomicAdd(&logCnt_s, tot);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + tot > room) {                     // wave-uniform: a row for the fallback kernel
-              if (lane_id() == 0) logOvf_s = 1;
-            } else {
-#pragma unroll
-              for (int u = 0; u < R; ++u) {              // cursor + base + tot <= cursor + room <= MD_CHUNK
-                if (rehit[u]) myLog[base + mask_rank(mk[u])] = col[u];
-                base += __popcll(mk[u]);
-              }
-            }
-          }
-        }
+        if (logging) rehit_log_append(rehit, col, &logCnt_s, &logOvf_s, myLog, 0, room);   // block-uniform
       }
     }, pc, err);
     const int ws = wave_sum(mine);                           // hash_insert_multi counts per lane
@@ -1611,25 +1812,17 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
     } else {
       if (lane == 0 && ws) atomicAdd(&cnt_s, ws);
       __syncthreads();
-      if (tid == 0) IC[cur.row] = cnt_s;
       if constexpr (LOG) {
         const int logged = logCnt_s;                     // (reset at the start of the next row, behind the barrier below)
-        const int rehits = cur.x0 - cnt_s;               // what the row logs when it has room
-        const bool direct = logging && !logOvf_s;        // then logged <= room <= cap
-        if (tid == 0) {
-          ml.meta[cur.row] = make_int2((int)chunkStart + cursor, direct ? logged : -1);
-          if (!direct) ml.fbList[atomicAdd(ml.fbCount, 1)] = cur.row;
-        }
-        if (direct) { cursor += logged; loggedSum += (unsigned long long)logged; }
-        else if (!logging && rehits >= 0 && rehits <= ml.cap) cursor += rehits;   // no log yet: count the demand
-      }
+        chunk.finish(ml, logging, tid == 0, true, cur.row, cur.x0, cnt_s, logged, logOvf_s, IC);
+      } else if (tid == 0) IC[cur.row] = cnt_s;
     }
     __syncthreads();
     cur = nxt;
     if (NW == 1) { nxt = nn; pc = pn; }
     q = qn;
   }
-  if constexpr (LOG) if (tid == 0 && loggedSum) atomicAdd(ml.logged, loggedSum);
+  if constexpr (LOG) if (tid == 0 && chunk.directSum) atomicAdd(ml.logged, chunk.directSum);
 }
 
 // ---- bin 6 of a logging symbolic pass: k_sym_midpair.  k_sym_hash<4,4096,2,true> gives every row of 513-2048 products four
@@ -1650,8 +1843,8 @@ __global__ __launch_bounds__(WAVE * NW) void k_sym_hash(const int* __restrict__ 
 // Measured on the headline matrix (profiles/README.md, "Mid rows, symbolic"): HW = 4 equals the four-wave kernel's time, HW = 2
 // is 12 % behind it -- so the launch is opt-in (SPGEMM_SYM_PAIR=1).
 // The log is k_sym_hash<.., true>'s in meaning: IC exact, a row logs products - IC columns, meta / fbList / cursor / logged
-// as there.  Chunks are reserved by the block for heavy rows and by each half for light ones (half 0 goes on in the block's
-// chunk).  `took`: rows this launch processed (test hook).
+// as there (the kit).  Chunks are reserved by the block for heavy rows and by each half for light ones (half 0 goes on in
+// the block's chunk).  `took`: rows this launch processed (test hook).
 #ifndef SMF_SP_CH
 #define SMF_SP_CH 1
 #endif
@@ -1738,11 +1931,8 @@ __global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict
   int* const dummy = reinterpret_cast<int*>(&st.dummy[lane]);
   st.dummy[lane] = DUMMY_SLOT;
   wave_lds_sync();
-  // first int of the chunk in use, ints of it in use (MD_CHUNK: none reserved yet): uniform over the waves of a row;
-  // re-hits of direct rows and rows processed: kept by the first wave of a row
-  unsigned long long chunkStart = 0ull;
-  int cursor = MD_CHUNK;
-  unsigned long long loggedSum = 0ull;
+  // the chunk in use: uniform over the waves of a row; its sum and the rows processed: kept by the first wave of a row
+  LogChunk chunk;
   int tookRows = 0;
   int par = 0;
   const XcdRange xh = xcd_range(slotBase[slotHi + 1] - slotBase[slotHi]);
@@ -1760,45 +1950,26 @@ __global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict
     MidPairCtr& rc = sets[par];
     const int size = table_size<2>(cur.x0, 64, tblMax);
     const int shift = 32 - log2_pow2(size);
-    const bool newChunk = have && cursor + ml.cap > MD_CHUNK;   // row-uniform: the chunk may not hold another row
+    const bool newChunk = have && chunk.is_full(ml);     // row-uniform
     if (have) {
       clear_table(keys, nullptr, size, gt, K * WAVE);
       if (gt == 0) {
         rc.cnt = 0; rc.logCnt = 0; rc.logOvf = 0;
-        if (newChunk) *chunkSlot = atomicAdd(ml.cursor, (unsigned long long)MD_CHUNK);
+        if (newChunk) *chunkSlot = LogChunk::reserve(ml);
       }
     }
     sync();
-    if (newChunk) { chunkStart = *chunkSlot; cursor = 0; }   // (written again at the start of a later row, behind this row's barriers)
-    const bool logging = chunkStart + (unsigned long long)MD_CHUNK <= (unsigned long long)ml.logCap;
+    if (newChunk) chunk.take(*chunkSlot);                // (written again at the start of a later row, behind this row's barriers)
+    const bool logging = chunk.logging(ml);
     if (have) {
-      int* const myLog = logging ? ml.log + chunkStart + cursor : nullptr;
-      const int room = min(ml.cap, MD_CHUNK - cursor);   // (= cap; the chunk bounds every store whatever cap is)
+      int* const myLog = logging ? chunk.log(ml) : nullptr;
+      const int room = chunk.room(ml);
       int mine = 0;
       for_each_column_dealt<K>(st, k, cur.as, cur.ae, SBL, JB, [&](const auto& act, const auto& col) {
         constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
         bool rehit[R];
         mine += hash_insert_chunked<SP_CH, true>(keys, size, shift, act, col, dummy, err, &rehit);
-        if (logging) {                                   // row-uniform
-          unsigned long long mk[R];
-          int tot = 0;
-#pragma unroll
-          for (int u = 0; u < R; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
-          if (tot) {                                     // wave-uniform
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&rc.logCnt, tot);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + tot > room) {                     // wave-uniform: a row for the fallback kernel
-              if (lane == 0) rc.logOvf = 1;
-            } else {
-#pragma unroll
-              for (int u = 0; u < R; ++u) {              // cursor + base + tot <= cursor + room <= MD_CHUNK
-                if (rehit[u]) myLog[base + mask_rank(mk[u])] = col[u];
-                base += __popcll(mk[u]);
-              }
-            }
-          }
-        }
+        if (logging) rehit_log_append(rehit, col, &rc.logCnt, &rc.logOvf, myLog, 0, room);   // row-uniform
       }, pc, err);
       const int ws = wave_sum(mine);                     // hash_insert_multi counts per lane
       if (lane == 0 && ws) atomicAdd(&rc.cnt, ws);
@@ -1807,15 +1978,7 @@ __global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict
     sync();                                              // (every wave's inserts are behind it: the table is free, too)
     if (have) {
       const int cnt = rc.cnt, logged = rc.logCnt;        // (this set is reset two rows on, behind the next row's barrier)
-      const int rehits = cur.x0 - cnt;                   // what the row logs when it has room
-      const bool direct = logging && !rc.logOvf;         // then logged <= room <= cap
-      if (gt == 0) {
-        IC[cur.row] = cnt;
-        ml.meta[cur.row] = make_int2((int)chunkStart + cursor, direct ? logged : -1);
-        if (!direct) ml.fbList[atomicAdd(ml.fbCount, 1)] = cur.row;
-      }
-      if (direct) { cursor += logged; if (k == 0) loggedSum += (unsigned long long)logged; }
-      else if (!logging && rehits >= 0 && rehits <= ml.cap) cursor += rehits;   // no log yet: count the demand
+      chunk.finish(ml, logging, gt == 0, k == 0, cur.row, cur.x0, cnt, logged, rc.logOvf, IC);
       if (k == 0) ++tookRows;
     }
     par ^= 1;
@@ -1838,7 +2001,7 @@ __global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict
   // ---- light rows: half h of block b takes rows 2b + h, 2b + h + 2 nb, ... of the XCD's share
   {
     const int h = w / LW, k = w % LW;
-    if (h != 0) { chunkStart = 0ull; cursor = MD_CHUNK; }   // (half 0 keeps the block's chunk)
+    if (h != 0) chunk = LogChunk();                      // (half 0 keeps the block's chunk; the others have summed nothing yet)
     const int stride = 2 * nb;
     int q0 = 2 * xl.bi;
     RowMeta cur = load_meta_sym(loRows, q0 + h, nlo, IA, rowFlops);
@@ -1855,7 +2018,7 @@ __global__ __launch_bounds__(HW * WAVE) void k_sym_midpair(const int* __restrict
     }
   }
   if (lane == 0) {
-    if (loggedSum) atomicAdd(ml.logged, loggedSum);
+    if (chunk.directSum) atomicAdd(ml.logged, chunk.directSum);
     if (tookRows) atomicAdd(took, (unsigned long long)tookRows);
   }
 }
@@ -2056,16 +2219,12 @@ constexpr int BH_CAP = 11264;                  // distinct columns per hash pass
 constexpr int BH_CAP_MAX = 12288;              // SPGEMM_BHCAP may raise the cap to this (load 0.74)
 constexpr int BH_SPILL = 1 << 18;              // (col,val) pairs a multi-pass row may park in HBM per block (2 MB)
 constexpr int BH_MAXCLS = 32;                  // hash classes (passes) with their own parking region
-// direct big-row kernel (k_num_bigdirect): the symbolic pass logs every product that lands on a column its row has already
-// seen (a "re-hit"); only those columns get a table slot, every other product is stored straight to C.
+// direct big-row kernel (k_num_bigdirect; the scheme: "the re-hit log kit" above)
 #ifndef SMF_BD_U
 #define SMF_BD_U 4
 #endif
 constexpr int BD_U = SMF_BD_U;                  // rounds in flight per wave (read-only probes: no CAS chains to keep short)
 constexpr int BD_MIN_SLOTS = 1024;             // smallest table of a row (a row without re-hits still sweeps it)
-// re-hits a row may log and still take the direct kernel with a table of S slots: the distinct repeated columns are at most
-// the re-hits, so the table is never more than 7/8 full and a probe always meets an empty slot
-__host__ __device__ constexpr int bd_cap(int S) { return S / 8 * 7; }
 constexpr int RL_ROW_BUDGET = 2048;            // log ints per big row when the workspace is sized (see grow_rehit_log)
 constexpr int RL_MIN_REGION = 1 << 15;         // ... and the smallest region of a block
 
@@ -2111,13 +2270,11 @@ __device__ __forceinline__ int block_sum_16(int v, int* red) {
 }
 
 // saveBitmaps: device buffer of saveCap row slots x BIG_WORDS words (may be null / 0); only used when n <= BIG_WC
-// LOG (n > BIG_WC, for k_num_bigdirect): the bitmap update returns the old word, and a product whose bit was already set is a
-// RE-HIT of its column.  Every wave compacts the re-hit columns of a trip (ballot + rank) and appends them to the block's
-// own region of rlLog (rlRegion ints per block, filled front to back over the block's rows).  Row q of the bin (queue order)
-// gets rlMeta[q] = {first log entry (index into rlLog), re-hits}; the count is -1 when the row logged more than rlCap
-// entries or the region had no room left -- such a row leaves the region as it found it.  A column hit k times is logged
-// k-1 times, nothing is deduplicated.  Rows that will not take the direct kernel (count -1, or q >= rlRows: no metadata
-// slot) are appended to fbList, *fbCount counts them.  The row's IC entry is the popcount either way.
+// LOG (n > BIG_WC, for k_num_bigdirect): the logging symbolic pass of the kit.  The bitmap update returns the old word, and
+// a product whose bit was already set is a re-hit.  Log space: the block's own region of rlLog (rlRegion ints per block,
+// filled front to back over the block's rows).  Row q of the bin (queue order) gets rlMeta[q] = {first log entry (index
+// into rlLog), re-hits or -1}.  Rows that will not take the direct kernel (count -1, or q >= rlRows: no metadata slot) are
+// appended to fbList, *fbCount counts them.  The row's IC entry is the popcount either way.
 template <bool LOG>
 __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__ binPtr, int bin,
                                                          const int* __restrict__ rowIds,
@@ -2171,26 +2328,8 @@ __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__
             rehit[u] = false;
           }
         }
-        if constexpr (LOG) if (logging) {              // block-uniform
-          unsigned long long mk[BIG_U];
-          int tot = 0;
-#pragma unroll
-          for (int u = 0; u < BIG_U; ++u) { mk[u] = ballot64(rehit[u]); tot += __popcll(mk[u]); }
-          if (tot) {                                   // wave-uniform
-            int base = 0;
-            if (lane_id() == 0) base = atomicAdd(&sh.logCnt, tot);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base + tot > room) {                   // wave-uniform: no room (or a row for the fallback kernel anyway)
-              if (lane_id() == 0) sh.logOvf = 1;
-            } else {
-#pragma unroll
-              for (int u = 0; u < BIG_U; ++u) {        // cursor + base + tot <= cursor + room <= rlRegion
-                if (rehit[u]) myLog[cursor + base + mask_rank(mk[u])] = col[u];
-                base += __popcll(mk[u]);
-              }
-            }
-          }
-        }
+        // block-uniform; no room: a row for the fallback kernel anyway
+        if constexpr (LOG) if (logging) rehit_log_append(rehit, col, &sh.logCnt, &sh.logOvf, myLog, cursor, room);
       });
       if constexpr (LOG) { logged = sh.logCnt; logOvf = sh.logOvf; }   // after the walk's closing barrier; reset only behind block_sum_16's
       int mine = 0;
@@ -2532,14 +2671,9 @@ __global__ __launch_bounds__(BIG_THREADS) void k_num_bighash(const int* __restri
 #endif
 }
 
-// numeric C (n > BIG_WC, rows whose re-hits k_sym_big<true> logged): one block of NW waves per row, a table of at most S
-// (key, value) slots that holds ONLY the row's repeated columns.  The log is inserted first, every key with the value bits
-// of -0.0f (the additive identity: a column hit twice ends as exactly a + b, as in k_num_bighash).  Then the products are
-// walked once and probe READ-ONLY: a hit adds its value under EXEC; a miss -- the probe meets an empty slot -- is a product
-// whose column occurs once in the row, and goes straight to JC/C at a position drawn from the row's counter (ballot rank +
-// one LDS atomic per wave and trip).  The table sweep then emits the repeated columns on the same counter.  A row is taken
-// only if 0 <= re-hits <= cap < S, so the table can never fill up; every other row of the bin is skipped here and is in
-// the fallback list k_num_bighash runs over.  The queue is the bin's own (largest rows first).
+// numeric C (n > BIG_WC, rows whose re-hits k_sym_big<true> logged): the kit's numeric pass with one block of NW waves per
+// row; the position of a trip's misses is drawn from the row's counter (one LDS atomic per wave and trip).  The rows it
+// skips are in the fallback list k_num_bighash runs over.  The queue is the bin's own (largest rows first).
 template <int NW, int S>
 struct BigDirectShared {
   slot_t tab[S];
@@ -2547,16 +2681,6 @@ struct BigDirectShared {
   int red[NW];
   int emitted;
 };
-struct DirectMeta { RowMeta m; int ls, lc; };            // + first log entry, re-hits (-1: not a row of this kernel)
-__device__ __forceinline__ DirectMeta load_meta_direct(const int* rows, int q, int count, const int* IA, const int* IC,
-                                                       const int2* rlMeta, int rlRows, int cap) {
-  DirectMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
-  if (q < count && q < rlRows) {
-    const int2 lm = rlMeta[q];
-    if (lm.y >= 0 && lm.y <= cap) { d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC); }
-  }
-  return d;
-}
 
 template <int NW, int S>
 __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restrict__ binPtr, int bin,
@@ -2577,11 +2701,16 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restri
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int first = binPtr[bin], count = binPtr[bin + 1] - first;
   if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
-  int q = next_row(qctr, &sh.red[0]);                 // one row ahead, as in k_sym_big
-  DirectMeta cur = load_meta_direct(rowIds + first, q, count, IA, IC, rlMeta, rlRows, CAP);
+  // one row ahead, as in k_sym_big; rlMeta goes by the queue position and has rlRows entries
+  auto load = [&](int qq) {
+    return load_meta_logged(rowIds + first, qq, min(count, rlRows), IA, IC, nullptr, rlMeta, false,
+                            [&](int2 lm) { return lm.y >= 0 && lm.y <= CAP; });
+  };
+  int q = next_row(qctr, &sh.red[0]);
+  LoggedMeta cur = load(q);
   while (q < count) {
     const int qn = next_row(qctr, &sh.red[0]);
-    const DirectMeta nxt = load_meta_direct(rowIds + first, qn, count, IA, IC, rlMeta, rlRows, CAP);
+    const LoggedMeta nxt = load(qn);
     if (cur.lc >= 0) {                                 // block-uniform
       const int as = cur.m.as, ae = cur.m.ae;
       const int outBase = cur.m.x0, outEnd = cur.m.x1;
@@ -2594,20 +2723,7 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restri
       clear_slots(sh.tab, size, tid, T);
       if (tid == 0) sh.emitted = 0;
       __syncthreads();
-      {                                                // the row's log: distinct keys <= lc <= CAP < S, or size >= 4 * lc
-        const int* const lg = rlLog + cur.ls;
-        const unsigned mask = (unsigned)size - 1u;
-        for (int i = tid; i < lc; i += T) {
-          const int c = lg[i];
-          const slot_t mine = make_slot(c, -0.0f);
-          unsigned h = ((unsigned)c * 2654435761u) >> shift;
-          for (int probe = 0; probe < size; ++probe) {
-            const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, mine);
-            if (old == EMPTY_SLOT || slot_key(old) == c) break;
-            h = (h + 1u) & mask;
-          }
-        }
-      }
+      fill_from_log(sh.tab, size, shift, rlLog + cur.ls, lc, tid, T);
       __syncthreads();
       int* const JCrow = JC + outBase;
       float* const Crow = C + outBase;
@@ -2616,53 +2732,9 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restri
                                        [&](const bool (&act)[BD_U], const int (&col)[BD_U], const float (&val)[BD_U], int) {
         char* const base = reinterpret_cast<char*>(sh.tab);
         const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
-        const int maskB = size * 8 - 1;
-        int hB[BD_U], hitB[BD_U];                       // byte offsets; dumB = "done" / "no hit"
         bool miss[BD_U];
-#pragma unroll
-        for (int u = 0; u < BD_U; ++u) {
-          const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
-          hB[u] = act[u] ? (int)(h * 8u) : dumB;
-          hitB[u] = dumB;
-          miss[u] = false;
-        }
-        for (int probe = 0;;) {                         // the keys do not change during the walk: plain reads
-          int key[BD_U];
-#pragma unroll
-          for (int u = 0; u < BD_U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
-          ++probe;
-          int pendBits = 0;
-#pragma unroll
-          for (int u = 0; u < BD_U; ++u) {
-            const bool pend = hB[u] != dumB;
-            const bool hit = pend && key[u] == col[u];
-            const bool emp = pend && key[u] == EMPTY_KEY;
-            hitB[u] = hit ? hB[u] : hitB[u];
-            miss[u] = miss[u] || emp;
-            hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the insert above
-            pendBits |= hB[u] ^ dumB;
-          }
-          if (ballot64(pendBits != 0) == 0ull) break;
-          if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
-        }
-#pragma unroll
-        for (int u = 0; u < BD_U; ++u)
-          if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
-        unsigned long long mk[BD_U];
-        int tot = 0;
-#pragma unroll
-        for (int u = 0; u < BD_U; ++u) { mk[u] = ballot64(miss[u]); tot += __popcll(mk[u]); }
-        if (tot) {                                      // wave-uniform
-          int pos = 0;
-          if (lane == 0) pos = atomicAdd(&sh.emitted, tot);
-          pos = __builtin_amdgcn_readfirstlane(pos);
-#pragma unroll
-          for (int u = 0; u < BD_U; ++u) {
-            const unsigned o = (unsigned)(pos + mask_rank(mk[u]));
-            if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
-            pos += __popcll(mk[u]);
-          }
-        }
+        probe_rounds(base, dumB, size, shift, act, col, val, err, miss);
+        store_misses_claimed(miss, col, val, &sh.emitted, lim, JCrow, Crow);
       });
       // (the walk ends with a barrier behind its last LDS atomics)
       emit_claimed<S / NW / WAVE>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
@@ -2675,10 +2747,9 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_bigdirect(const int* __restri
   }
 }
 
-// numeric, bins 6-7 (513-4096 products) of a float product whose symbolic pass logged (k_sym_hash<.., true>): the scheme of
-// k_num_bigdirect with a table of at most S slots (1024: 8 KB, where k_num_hash clears, fills and sweeps 16-64 KB per row).
-// A row is taken with 0 <= re-hits <= cap <= bd_cap(S); rows with count -1 are skipped, they are in the bin's fallback list
-// that k_num_hash runs over.  A row without any repeated column (IC range = products) is expanded as in k_num_hash: no table,
+// numeric, bins 6-7 (513-4096 products) of a float product whose symbolic pass logged (k_sym_hash<.., true>): the kit's
+// numeric pass like k_num_bigdirect, with a table of at most S slots (1024: 8 KB, where k_num_hash clears, fills and sweeps
+// 16-64 KB per row).  The rows it skips are in the bin's fallback list that k_num_hash runs over.  An expanded row takes its
 // positions from the walk's dense numbering, which lives in the table's memory.
 #ifndef SMF_MD_U
 #define SMF_MD_U 4
@@ -2691,28 +2762,6 @@ struct MidDirectShared {
   int qslot;
   int emitted;
 };
-struct MidMeta { RowMeta m; int ls, lc; };              // + first log entry, re-hits (-1: not a row of this kernel)
-// Bin 6 has a second direct kernel, k_num_midwave (one wave per row, a table of MW_SLOTS slots).  THE rule for which of the
-// two takes a row, read by both: the wave kernel takes the rows that logged (lm = the row's {first log entry, re-hits}) at
-// most waveCap <= bd_cap(MW_SLOTS) re-hits and whose log lies inside the log; k_num_middirect keeps the other rows up to
-// its own cap.  waveCap < 0: no wave kernel in this call (bin 7, SPGEMM_MD_WAVE=0, a bin below the row threshold).
-constexpr int MW_SLOTS = 512;
-__device__ __forceinline__ bool midwave_takes(int2 lm, long long logCap, int waveCap) {
-  return lm.y >= 0 && lm.y <= waveCap && lm.x >= 0 && (long long)lm.x + lm.y <= logCap;
-}
-__device__ __forceinline__ MidMeta load_meta_mid(const int* rows, int q, int count, const int* IA, const int* IC,
-                                                 const int* rowFlops, const int2* meta, int cap, long long logCap, int waveCap) {
-  MidMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
-  if (q < count) {
-    const int row = rows[q];
-    const int2 lm = meta[row];
-    if (lm.y >= 0 && lm.y <= cap && !midwave_takes(lm, logCap, waveCap)) {
-      d.ls = lm.x; d.lc = lm.y; d.m = load_meta_num(rows, q, count, IA, IC, rowFlops);
-    }
-  }
-  return d;
-}
-
 template <int NW, int S>
 __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restrict__ binPtr, int bin,
                                                              const int* __restrict__ rowIds,
@@ -2737,12 +2786,16 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
   constexpr int QB = NW >= 8 ? 2 : 4;                  // rows per dequeue, as in k_num_hash
   if (surplus_block(count, QB)) return;
   if (tid < WAVE) sh.st.dummy[tid] = DUMMY_SLOT;
+  auto load = [&](int qq) {                            // the wave kernel's rows are not this one's
+    return load_meta_logged(rows, qq, count, IA, IC, rowFlops, meta, true,
+                            [&](int2 lm) { return lm.y >= 0 && lm.y <= cap && !midwave_takes(lm, logCap, waveCap); });
+  };
   int q = next_row<QB>(qctr, &sh.qslot, -1);
-  MidMeta cur = load_meta_mid(rows, q, count, IA, IC, rowFlops, meta, cap, logCap, waveCap);
+  LoggedMeta cur = load(q);
   int tookRows = 0;                                    // rows of this block that went direct here (test hook)
   while (q < count) {
     const int qn = next_row<QB>(qctr, &sh.qslot, q);
-    const MidMeta nxt = load_meta_mid(rows, qn, count, IA, IC, rowFlops, meta, cap, logCap, waveCap);
+    const LoggedMeta nxt = load(qn);
     const int as = cur.m.as, ae = cur.m.ae;
     const int outBase = cur.m.x0, outEnd = cur.m.x1;
     const int want = outEnd - outBase;
@@ -2753,14 +2806,8 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
     const bool mine = cur.lc >= 0 && (long long)cur.ls >= 0 && (long long)cur.ls + cur.lc <= logCap;
     tookRows += __builtin_amdgcn_readfirstlane(mine ? 1 : 0);   // (block-uniform: kept in a scalar register)
     if (mine && want == cur.m.x2) {
-      for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
-                                       [&](const bool (&act)[MD_U], const int (&col)[MD_U], const float (&val)[MD_U], int p0) {
-#pragma unroll
-        for (int u = 0; u < MD_U; ++u) {
-          const unsigned o = (unsigned)(p0 + u * WAVE + lane);
-          if (act[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
-        }
-      }, PreA{0, 0, 0.f, false}, err, reinterpret_cast<WalkNumber<NW>*>(sh.tab));
+      for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB, expanded_store(lane, lim, JCrow, Crow),
+                                       PreA{0, 0, 0.f, false}, err, reinterpret_cast<WalkNumber<NW>*>(sh.tab));
     } else if (mine) {
       const int lc = cur.lc;
       // four slots per logged re-hit when that fits (the clear and the sweep are what a small table saves)
@@ -2770,72 +2817,15 @@ __global__ __launch_bounds__(WAVE * NW) void k_num_middirect(const int* __restri
       clear_slots(sh.tab, size, tid, T);
       if (tid == 0) sh.emitted = 0;
       __syncthreads();
-      {                                                // the row's log: distinct keys <= lc <= cap < S, or size >= 4 * lc
-        const int* const lg = mlog + cur.ls;
-        const unsigned mask = (unsigned)size - 1u;
-        for (int i = tid; i < lc; i += T) {
-          const int c = lg[i];
-          const slot_t own = make_slot(c, -0.0f);
-          unsigned h = ((unsigned)c * 2654435761u) >> shift;
-          for (int probe = 0; probe < size; ++probe) {
-            const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, own);
-            if (old == EMPTY_SLOT || slot_key(old) == c) break;
-            h = (h + 1u) & mask;
-          }
-        }
-      }
+      fill_from_log(sh.tab, size, shift, mlog + cur.ls, lc, tid, T);
       __syncthreads();
       for_each_product<NW, MD_U, true>(sh.st, as, ae, SBL, VA, JB, VB,
                                        [&](const bool (&act)[MD_U], const int (&col)[MD_U], const float (&val)[MD_U], int) {
         char* const base = reinterpret_cast<char*>(sh.tab);
         const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
-        const int maskB = size * 8 - 1;
-        int hB[MD_U], hitB[MD_U];                       // byte offsets; dumB = "done" / "no hit"
         bool miss[MD_U];
-#pragma unroll
-        for (int u = 0; u < MD_U; ++u) {
-          const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
-          hB[u] = act[u] ? (int)(h * 8u) : dumB;
-          hitB[u] = dumB;
-          miss[u] = false;
-        }
-        for (int probe = 0;;) {                         // the keys do not change during the walk: plain reads
-          int key[MD_U];
-#pragma unroll
-          for (int u = 0; u < MD_U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
-          ++probe;
-          int pendBits = 0;
-#pragma unroll
-          for (int u = 0; u < MD_U; ++u) {
-            const bool pend = hB[u] != dumB;
-            const bool hit = pend && key[u] == col[u];
-            const bool emp = pend && key[u] == EMPTY_KEY;
-            hitB[u] = hit ? hB[u] : hitB[u];
-            miss[u] = miss[u] || emp;
-            hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the insert above
-            pendBits |= hB[u] ^ dumB;
-          }
-          if (ballot64(pendBits != 0) == 0ull) break;
-          if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
-        }
-#pragma unroll
-        for (int u = 0; u < MD_U; ++u)
-          if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
-        unsigned long long mk[MD_U];
-        int tot = 0;
-#pragma unroll
-        for (int u = 0; u < MD_U; ++u) { mk[u] = ballot64(miss[u]); tot += __popcll(mk[u]); }
-        if (tot) {                                      // wave-uniform
-          int pos = 0;
-          if (lane == 0) pos = atomicAdd(&sh.emitted, tot);
-          pos = __builtin_amdgcn_readfirstlane(pos);
-#pragma unroll
-          for (int u = 0; u < MD_U; ++u) {
-            const unsigned o = (unsigned)(pos + mask_rank(mk[u]));
-            if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
-            pos += __popcll(mk[u]);
-          }
-        }
+        probe_rounds(base, dumB, size, shift, act, col, val, err, miss);
+        store_misses_claimed(miss, col, val, &sh.emitted, lim, JCrow, Crow);
       });
       // (the walk ends with s_waitcnt lgkmcnt(0) and a barrier behind its last LDS atomics)
       emit_claimed<S / T>(sh.tab, w * per, per, &sh.emitted, outBase, outEnd, JC, C);
@@ -2873,71 +2863,8 @@ struct MidWaveRows {
   const int* hi; int nhi;                              // (second slot)
   const int* lo; int nlo;
   __device__ __forceinline__ int count() const { return nhi + nlo; }
-  __device__ __forceinline__ int at(int q) const { return q < nhi ? hi[q] : lo[q - nhi]; }
+  __device__ __forceinline__ int operator[](int q) const { return q < nhi ? hi[q] : lo[q - nhi]; }
 };
-// (a row with a log that this kernel does not take: lc = -1, ls = 1 and the row id -- it goes on k_num_middirect's list)
-__device__ __forceinline__ MidMeta load_meta_midwave(const MidWaveRows& rows, int q, const int* IA, const int* IC,
-                                                     const int* rowFlops, const int2* meta, long long logCap, int waveCap) {
-  MidMeta d{{0, 0, 0, 0, 0, 0}, 0, -1};
-  if (q < rows.count()) {
-    const int row = rows.at(q);
-    const int2 lm = meta[row];
-    if (midwave_takes(lm, logCap, waveCap)) {
-      d.ls = lm.x; d.lc = lm.y;
-      d.m.row = row; d.m.as = IA[row]; d.m.ae = IA[row + 1]; d.m.x0 = IC[row]; d.m.x1 = IC[row + 1]; d.m.x2 = rowFlops[row];
-    } else if (lm.y >= 0) { d.ls = 1; d.m.row = row; }
-  }
-  return d;
-}
-
-// U rounds of products against the table of the row's repeated columns, keys read-only: a hit adds under EXEC, a miss is
-// stored at `pos` + its ballot rank.  Returns the position behind the misses.
-template <int U>
-__device__ __forceinline__ int midwave_rounds(char* base, int dumB, int size, int shift, const bool (&act)[U],
-                                              const int (&col)[U], const float (&val)[U], int pos, unsigned lim,
-                                              int* __restrict__ JCrow, float* __restrict__ Crow, int* __restrict__ err) {
-  const int maskB = size * 8 - 1;
-  int hB[U], hitB[U];                                  // byte offsets; dumB = "done" / "no hit"
-  bool miss[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const unsigned h = ((unsigned)col[u] * 2654435761u) >> shift;
-    hB[u] = act[u] ? (int)(h * 8u) : dumB;
-    hitB[u] = dumB;
-    miss[u] = false;
-  }
-  for (int probe = 0;;) {
-    int key[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) key[u] = *reinterpret_cast<const int*>(base + hB[u]);
-    ++probe;
-    int pendBits = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool pend = hB[u] != dumB;
-      const bool hit = pend && key[u] == col[u];
-      const bool emp = pend && key[u] == EMPTY_KEY;
-      hitB[u] = hit ? hB[u] : hitB[u];
-      miss[u] = miss[u] || emp;
-      hB[u] = (pend && !hit && !emp) ? ((hB[u] + 8) & maskB) : dumB;   // linear, like the log insert
-      pendBits |= hB[u] ^ dumB;
-    }
-    if (ballot64(pendBits != 0) == 0ull) break;
-    if (probe >= size) { atomicOr(err, ERRF_TABLE_FULL); break; }
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (hitB[u] != dumB) atomicAdd(reinterpret_cast<float*>(base + hitB[u] + 4), val[u]);
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const unsigned long long mk = ballot64(miss[u]);
-    const unsigned o = (unsigned)(pos + mask_rank(mk));
-    if (miss[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
-    pos += __popcll(mk);
-  }
-  return pos;
-}
-
 __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ slotBase, int slotLo, int slotHi,
                                                       const int* __restrict__ rowIds,
                                                       const int* __restrict__ IA, const int2* __restrict__ SBL,
@@ -2966,13 +2893,19 @@ __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ sl
   const int stride = xh.nb;
   int q = xh.bi;
   // two rows of metadata and one row of A entries are in flight ahead of the row being processed
-  MidMeta cur = load_meta_midwave(rows, q, IA, IC, rowFlops, meta, logCap, waveCap);
-  MidMeta nxt = load_meta_midwave(rows, q + stride, IA, IC, rowFlops, meta, logCap, waveCap);
+  // (a row with a log that this kernel does not take goes on k_num_middirect's list)
+  __builtin_assume(rowFlops != nullptr);
+  auto load = [&](int qq) {
+    return load_meta_logged(rows, qq, count, IA, IC, rowFlops, meta, true,
+                            [&](int2 lm) { return midwave_takes(lm, logCap, waveCap) ? 1 : lm.y >= 0 ? -1 : 0; });
+  };
+  LoggedMeta cur = load(q);
+  LoggedMeta nxt = load(q + stride);
   PreA pc = load_pre(cur.m, SBL, VA, true);            // (a row of the other kernels: as = ae = 0, nothing is read)
   int tookRows = 0;
   while (q < count) {
     const int qn = q + stride;
-    const MidMeta nn = load_meta_midwave(rows, qn + stride, IA, IC, rowFlops, meta, logCap, waveCap);
+    const LoggedMeta nn = load(qn + stride);
     const PreA pn = load_pre(nxt.m, SBL, VA, true);
     if (cur.lc >= 0) {                                 // wave-uniform
       ++tookRows;
@@ -2982,15 +2915,7 @@ __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ sl
       const unsigned lim = (unsigned)max(want, 0);     // every store stays inside the row's own range
       if (want == cur.m.x2) {
         // no repeated column: expanded, every product at its place in the walk's numbering of the row
-        for_each_product<1, 2, true>(sh.st, cur.m.as, cur.m.ae, SBL, VA, JB, VB,
-                                     [&](const auto& act, const auto& col, const auto& val, int p0) {
-          constexpr int R = (int)(sizeof(col) / sizeof(col[0]));
-#pragma unroll
-          for (int u = 0; u < R; ++u) {
-            const unsigned o = (unsigned)(p0 + u * WAVE + lane);
-            if (act[u] && o < lim) { st_out(JCrow + o, col[u]); st_out(Crow + o, val[u]); }
-          }
-        }, pc, err);
+        for_each_product<1, 2, true>(sh.st, cur.m.as, cur.m.ae, SBL, VA, JB, VB, expanded_store(lane, lim, JCrow, Crow), pc, err);
       } else {
         const int lc = cur.lc;
         // four slots per logged re-hit when that fits (the clear and the sweep are what a small table saves)
@@ -2998,20 +2923,7 @@ __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ sl
         const int shift = 32 - log2_pow2(size);
         clear_slots(sh.tab, size, lane, WAVE);
         wave_lds_sync();
-        {                                              // the row's log: distinct keys <= lc <= waveCap < S, or size >= 4 * lc
-          const int* const lg = mlog + cur.ls;
-          const unsigned mask = (unsigned)size - 1u;
-          for (int i = lane; i < lc; i += WAVE) {
-            const int c = lg[i];
-            const slot_t own = make_slot(c, -0.0f);
-            unsigned h = ((unsigned)c * 2654435761u) >> shift;
-            for (int probe = 0; probe < size; ++probe) {
-              const slot_t old = atomicCAS(&sh.tab[h], EMPTY_SLOT, own);
-              if (old == EMPTY_SLOT || slot_key(old) == c) break;
-              h = (h + 1u) & mask;
-            }
-          }
-        }
+        fill_from_log(sh.tab, size, shift, mlog + cur.ls, lc, lane, WAVE);
         wave_lds_sync();
         char* const base = reinterpret_cast<char*>(sh.tab);
         const int dumB = (int)(reinterpret_cast<char*>(&sh.st.dummy[lane]) - base);
@@ -3028,7 +2940,9 @@ __global__ __launch_bounds__(WAVE) void k_num_midwave(const int* __restrict__ sl
               const int i = c0 + u < R ? c0 + u : 0;
               a_[u] = c0 + u < R ? act[i] : false; c_[u] = col[i]; v_[u] = val[i];
             }
-            pos = midwave_rounds<CH>(base, dumB, size, shift, a_, c_, v_, pos, lim, JCrow, Crow, err);
+            bool miss[CH];
+            probe_rounds(base, dumB, size, shift, a_, c_, v_, err, miss);
+            pos = store_misses(miss, c_, v_, pos, lim, JCrow, Crow);
           }
         }, pc, err);
         wave_lds_sync();                               // the adds have landed: the sweep reads their sums

@@ -423,33 +423,20 @@ static int ws_ensure(spgemm_handle* h, int m) {
   return SPGEMM_OK;
 }
 
-// k_num_bigdirect's geometry as compile-time constants: f(waves, table slots)
-template <class F>
-static auto with_bd_cfg(int cfg, F f) {
-  typedef std::integral_constant<int, 4> W4; typedef std::integral_constant<int, 8> W8; typedef std::integral_constant<int, 16> W16;
-  typedef std::integral_constant<int, 4096> S4; typedef std::integral_constant<int, 8192> S8;
-  switch (cfg) {
-    case 0: return f(W4(), S4());
-    case 1: return f(W8(), S4());
-    case 2: return f(W4(), S8());
-    case 4: return f(W16(), S4());
-    default: return f(W8(), S8());
-  }
+// The direct kernels' geometries, waves x table slots, in the order of their knob's values
+template <int NW, int S> struct Geo {};
+template <class... G> struct GeoTable {};
+typedef GeoTable<Geo<4, 4096>, Geo<8, 4096>, Geo<4, 8192>, Geo<8, 8192>, Geo<16, 4096>> BdGeos;   // SPGEMM_BD_CFG 0..4: k_num_bigdirect
+typedef GeoTable<Geo<4, 1024>, Geo<8, 1024>, Geo<4, 2048>, Geo<8, 2048>> MdGeos;                  // SPGEMM_MD_CFG 0..3: k_num_middirect
+// entry `cfg` of a table as compile-time constants: f(waves, table slots)
+template <class F, int NW, int S, class... Gs>
+static auto with_geometry(GeoTable<Geo<NW, S>, Gs...>, int cfg, F f) {
+  if constexpr (sizeof...(Gs) > 0) if (cfg > 0) return with_geometry(GeoTable<Gs...>(), cfg - 1, f);
+  return f(std::integral_constant<int, NW>(), std::integral_constant<int, S>());
 }
-static int bd_cap_of(int cfg) { return bd_cap(cfg == 2 || cfg == 3 ? 8192 : 4096); }
-// ... and k_num_middirect's
-template <class F>
-static auto with_md_cfg(int cfg, F f) {
-  typedef std::integral_constant<int, 4> W4; typedef std::integral_constant<int, 8> W8;
-  typedef std::integral_constant<int, 1024> S1; typedef std::integral_constant<int, 2048> S2;
-  switch (cfg) {
-    case 1: return f(W8(), S1());
-    case 2: return f(W4(), S2());
-    case 3: return f(W8(), S2());
-    default: return f(W4(), S1());
-  }
-}
-static int md_slots_of(int cfg) { return cfg >= 2 ? 2048 : 1024; }
+template <class Table> static int slots_of(Table t, int cfg) { return with_geometry(t, cfg, [](auto, auto slots) { return (int)slots; }); }
+// blocks per CU of a kernel with `lds` bytes per block and nw waves: what 160 KB of LDS and 32 waves hold
+static int blocks_per_cu(int lds, int nw) { return std::max(1, std::min((160 * 1024) / lds, 32 / nw)); }
 
 // an integer knob of the handle from the environment; a value outside [lo, hi] is ignored
 static void env_int(const char* name, int lo, int hi, int* field) {
@@ -497,7 +484,7 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   env_int("SPGEMM_RLREGION", 64, 1 << 24, &h->rlRegionEnv);
   { int v = 1; env_int("SPGEMM_MIDDIRECT", 0, 1, &v); h->midDirect = v != 0; }
   env_int("SPGEMM_MD_CFG", 0, 3, &h->mdCfg);
-  h->mdCap = bd_cap(md_slots_of(h->mdCfg));
+  h->mdCap = bd_cap(slots_of(MdGeos(), h->mdCfg));
   env_int("SPGEMM_MD_CAP", 0, h->mdCap, &h->mdCap);
   h->mdMinRows = 4 * h->numCU;
   env_int("SPGEMM_MD_MINROWS", 1, 1 << 30, &h->mdMinRows);
@@ -530,7 +517,7 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   // the big-row kernels use more than the default 64 KB of dynamic LDS
   HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
   HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
-  HIPCHK(with_bd_cfg(h->bdCfg, [&](auto nw, auto slots) {
+  HIPCHK(with_geometry(BdGeos(), h->bdCfg, [&](auto nw, auto slots) {
     return hipFuncSetAttribute((const void*)k_num_bigdirect<nw, slots>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)sizeof(BigDirectShared<nw, slots>)); }));
   HIPCHK(hipFuncSetAttribute((const void*)k_num_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigNumShared)));
@@ -586,7 +573,7 @@ extern "C" int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows,
   const int nbig = h->mirror.binPtr[NBINS] - h->mirror.binPtr[NBINS - 1];
   *fallback_rows = h->bdRan ? h->mirror.fbBin[1] : nbig;
   *direct_rows = nbig - *fallback_rows;
-  *rehit_cap = bd_cap_of(h->bdCfg);
+  *rehit_cap = bd_cap(slots_of(BdGeos(), h->bdCfg));
   *region_ints = h->rl_region;
   return SPGEMM_OK;
 }
@@ -883,7 +870,7 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
     if (h->bdLogged)
       hipLaunchKernelGGL(k_sym_big<true>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
                          rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
-                         h->rlMeta, h->rlLog ? h->rl_rows : 0, h->rlLog, h->rl_region, bd_cap_of(h->bdCfg), h->bigFallback,
+                         h->rlMeta, h->rlLog ? h->rl_rows : 0, h->rlLog, h->rl_region, bd_cap(slots_of(BdGeos(), h->bdCfg)), h->bigFallback,
                          &h->dsmall->fbBin[1]);
     else
       hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
@@ -988,9 +975,9 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
                          dB, dIC, dJC, dC, err, qc + 4 * 32, h->rowFlops,
                          h->spill_blocks >= blocks ? h->spill : (int2*)nullptr, BH_SPILL, h->bhCap, h->bhMargin);
       if (direct && h->rlLog)                          // (no workspace yet: every row is in the fallback list)
-        with_bd_cfg(h->bdCfg, [&](auto nw, auto slots) {
+        with_geometry(BdGeos(), h->bdCfg, [&](auto nw, auto slots) {
           const int lds = (int)sizeof(BigDirectShared<nw, slots>);
-          const int perCU = std::max(1, std::min((160 * 1024) / lds, 32 / (int)nw));
+          const int perCU = blocks_per_cu(lds, nw);
           hipLaunchKernelGGL((k_num_bigdirect<nw, slots>), dim3(clampi(rows(8, 9), 1, cu * perCU)), dim3(WAVE * nw), lds, st,
                              bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 8 * 32,
                              (const int2*)h->rlMeta, h->rl_rows, (const int*)h->rlLog);
@@ -1013,9 +1000,8 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
   h->mwRan = waveCap >= 0;
   auto launch_mid = [&](int bin, int nrows, int* qd, hipStream_t st, int wcap, unsigned long long* took,
                         const int* lbp, int lbin, const int* lrows) {       // (the rows: bin `lbin` of lbp over lrows)
-    with_md_cfg(h->mdCfg >= 0 ? h->mdCfg : bin == 7 ? 1 : 0, [&](auto nw, auto slots) {
-      const int lds = (int)sizeof(MidDirectShared<nw, slots>);
-      const int perCU = std::max(1, std::min((160 * 1024) / lds, 32 / (int)nw));
+    with_geometry(MdGeos(), h->mdCfg >= 0 ? h->mdCfg : bin == 7 ? 1 : 0, [&](auto nw, auto slots) {
+      const int perCU = blocks_per_cu((int)sizeof(MidDirectShared<nw, slots>), nw);
       hipLaunchKernelGGL((k_num_middirect<nw, slots>), dim3(clampi(nrows, 1, cu * perCU)), dim3(WAVE * nw), 0, st,
                          lbp, lbin, lrows, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qd, (const int*)h->rowFlops,
                          (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, h->mdCap, wcap, took);

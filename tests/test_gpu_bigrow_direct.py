@@ -109,8 +109,8 @@ def _flops(A, B):
     return np.array([per[rp[i]:rp[i + 1]].sum() for i in range(A.rows)])
 
 
-def _cap():
-    h = hs.Handle(0)
+def _cap(**env):
+    h = _handle(**env)
     try:
         return h.bigrow_paths()["cap"]
     finally:
@@ -188,13 +188,35 @@ def test_few_big_rows_keep_the_hash_kernel_by_default():
     twice(A, B, "default threshold", direct=0, SPGEMM_BD_MINROWS=100000)
 
 
+def _cap_and_one_more(**env):
+    cap = _cap(**env)
+    A, B = case_copies(cap)
+    twice(A, B, "cap", direct=1, **env)
+    A, B = case_copies(cap + 1)
+    twice(A, B, "cap + 1", direct=0, **env)
+    return cap
+
+
 def test_rehits_at_the_cap_and_one_more():
     """case 4: exactly cap re-hits take the direct kernel, cap + 1 the hash kernel; the results are the oracle's either way"""
-    cap = _cap()
-    A, B = case_copies(cap)
-    twice(A, B, "cap", direct=1)
-    A, B = case_copies(cap + 1)
-    twice(A, B, "cap + 1", direct=0)
+    _cap_and_one_more()
+
+
+# SPGEMM_BD_CFG: waves x table slots of the direct kernel (1, 8 x 4096, is the default that every other test here runs)
+GEOMETRIES = {0: 4096, 2: 8192, 3: 8192, 4: 4096}
+
+
+@pytest.mark.parametrize("cfg", sorted(GEOMETRIES))
+def test_rehits_at_the_cap_and_one_more_in_every_geometry(cfg):
+    """case 4 in the other instantiations of the direct kernel; the cap is 7/8 of the table's slots"""
+    assert _cap_and_one_more(SPGEMM_BD_CFG=cfg) == GEOMETRIES[cfg] // 8 * 7
+
+
+@pytest.mark.parametrize("cfg", sorted(GEOMETRIES))
+def test_logged_row_in_every_geometry(cfg):
+    """case 3 in the other instantiations of the direct kernel"""
+    A, B = case_3_and_64()
+    twice(A, B, f"3 and 64, geometry {cfg}", direct=1, SPGEMM_BD_CFG=cfg)
 
 
 def test_logged_and_fallback_rows_in_one_call():

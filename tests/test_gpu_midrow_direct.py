@@ -244,18 +244,46 @@ def test_old_path_switch(name):
     check(f"{name}-{N_HI}", A, B, planted, split=False, SPGEMM_MIDDIRECT=0)
 
 
-def test_rehits_at_the_cap_and_one_more():
-    """case 4: exactly cap re-hits go direct, cap + 1 to the hash kernel, in both slots of bin 6 and in bin 7"""
-    cap = _cap()
-    assert cap == S // 8 * 7
+def _cap_and_one_more(sizes, **env):
+    """rows of `sizes` products with cap, cap - 1 (direct) and cap + 1, cap + 60 or so (hash kernel) re-hits"""
+    cap = _cap(**env)
     b = Bld(N_HI, 7)
-    for products in (1000, 2000, 3000):
+    for products in sizes:
         for r in (cap, cap + 1, cap - 1, min(cap + 60, products - 1)):
             b.add(64 if products != 2000 else 8, products, r)
     A, B, planted = b.finish(8)
-    _, p, h = run("cap", A, B, planted)
+    _, p, h = run(f"cap-{cap}-{sizes[0]}", A, B, planted, **env)
     h.close()
     assert (p["direct"], p["fallback"]) == (6, 6), p
+    return cap
+
+
+def test_rehits_at_the_cap_and_one_more():
+    """case 4: exactly cap re-hits go direct, cap + 1 to the hash kernel, in both slots of bin 6 and in bin 7"""
+    assert _cap_and_one_more((1000, 2000, 3000)) == S // 8 * 7
+
+
+# SPGEMM_MD_CFG: waves x table slots of k_num_middirect in both bins (by default bin 6 runs 0 and bin 7 runs 1); with
+# SPGEMM_MD_WAVE=0 the four-wave kernel sees the rows of bin 6 that the one-wave kernel takes otherwise
+GEOMETRIES = {0: 1024, 1: 1024, 2: 2048, 3: 2048}
+
+
+@pytest.mark.parametrize("cfg", sorted(GEOMETRIES))
+def test_rehits_at_the_cap_and_one_more_in_every_geometry(cfg):
+    """case 4 in every instantiation of the direct kernel; the cap is 7/8 of the table's slots (a row of 1000 products cannot
+    have 1792 re-hits: the larger tables get rows of the second slot of bin 6 and of bin 7)"""
+    slots = GEOMETRIES[cfg]
+    sizes = (1000, 2000, 3000) if slots == 1024 else (2000, 3000, 4000)
+    assert _cap_and_one_more(sizes, SPGEMM_MD_CFG=cfg, SPGEMM_MD_WAVE=0) == slots // 8 * 7
+
+
+@pytest.mark.parametrize("cfg", sorted(GEOMETRIES))
+def test_direct_rows_in_every_geometry(cfg):
+    """case 1 in every instantiation of the direct kernel: none of its rows may fall back"""
+    A, B, planted = CASES["walk"](N_HI)
+    _, p, h = run(f"walk-{N_HI}", A, B, planted, SPGEMM_MD_CFG=cfg, SPGEMM_MD_WAVE=0)
+    h.close()
+    assert p["fallback"] == 0, p
 
 
 def test_one_column_hit_many_times():
