@@ -89,8 +89,8 @@ struct spgemm_shard {
   int grank = 0;                                  // global rank of this shard
   spgemm_handle* h = nullptr;
   ncclComm_t comm = nullptr;
-  long long* dSizes = nullptr;                    // nranks int64 on the device (multi-process size exchange)
-  long long* hSizes = nullptr;                    // pinned twin
+  DevBlock<long long> dSizes;                     // nranks int64 on the device (multi-process size exchange)
+  PinBlock<long long> hSizes;                     // pinned twin
   std::string err;                                // message of a failure inside this shard's worker thread
   int rc = 0;
 };
@@ -173,8 +173,8 @@ static int group_make_shards(spgemm_group* g) {
   for (auto& s : g->sh) {
     CHK(spgemm_hip_create(&s.h, s.device));
     HIPCHK(hipSetDevice(s.device));
-    HIPCHK(hipMalloc((void**)&s.dSizes, sizeof(long long) * (size_t)g->nranks));
-    HIPCHK(hipHostMalloc((void**)&s.hSizes, sizeof(long long) * (size_t)g->nranks, hipHostMallocDefault));
+    HIPCHK(s.dSizes.reserve((size_t)g->nranks));
+    HIPCHK(s.hSizes.reserve((size_t)g->nranks));
   }
   return SPGEMM_OK;
 }
@@ -185,8 +185,6 @@ extern "C" int spgemm_hip_group_destroy(spgemm_group* g) {
   for (auto& s : g->sh) {
     hipSetDevice(s.device);
     if (s.comm && rccl().ok) rccl().CommDestroy(s.comm);
-    hipFree(s.dSizes);
-    hipHostFree(s.hSizes);
     spgemm_hip_destroy(s.h);
   }
   delete g;
@@ -404,12 +402,12 @@ static int allgatherv_segments(spgemm_group* g, const std::vector<int>& ends, co
       spgemm_shard& s = g->sh[0];
       const GatherView& v = view[0];
       HIPCHK(hipSetDevice(s.device));
-      int* tI = nullptr; int* tJ = nullptr; float* tV = nullptr;
-      auto done = [&](int rc) { pool().release(tI); pool().release(tJ); pool().release(tV); return rc; };
-      if (pool().alloc((void**)&tI, sizeof(int) * std::max<size_t>(rows_of(0), 1)) != hipSuccess ||
-          pool().alloc((void**)&tJ, sizeof(int) * std::max<size_t>(cnt_of(0), 1)) != hipSuccess ||
-          pool().alloc((void**)&tV, sizeof(float) * std::max<size_t>(cnt_of(0), 1)) != hipSuccess)
-        return done(fail(SPGEMM_ERR_HIP, "scratch allocation for the self exchange failed"));
+      hipStream_t st = s.h->stream;
+      DevBuf<int> tI, tJ;
+      DevBuf<float> tV;
+      if (tI.alloc(std::max<size_t>(rows_of(0), 1)) != hipSuccess || tJ.alloc(std::max<size_t>(cnt_of(0), 1)) != hipSuccess ||
+          tV.alloc(std::max<size_t>(cnt_of(0), 1)) != hipSuccess)
+        return fail(SPGEMM_ERR_HIP, "scratch allocation for the self exchange failed");
       ncclResult_t r = R.GroupStart();
       if (r == ncclSuccess && rows_of(0)) r = R.Send(v.gI, rows_of(0), ncclInt32, 0, s.comm, s.h->stream);
       if (r == ncclSuccess && rows_of(0)) r = R.Recv(tI, rows_of(0), ncclInt32, 0, s.comm, s.h->stream);
@@ -419,13 +417,13 @@ static int allgatherv_segments(spgemm_group* g, const std::vector<int>& ends, co
       if (r == ncclSuccess && cnt_of(0)) r = R.Recv(tV, cnt_of(0), ncclFloat32, 0, s.comm, s.h->stream);
       const ncclResult_t r2 = R.GroupEnd();
       if (r != ncclSuccess || r2 != ncclSuccess)
-        return done(fail(SPGEMM_ERR_HIP, "RCCL self exchange failed: %s", R.GetErrorString(r != ncclSuccess ? r : r2)));
+        return drained(st, fail(SPGEMM_ERR_HIP, "RCCL self exchange failed: %s", R.GetErrorString(r != ncclSuccess ? r : r2)));
       if (hipMemcpyAsync(v.gI, tI, sizeof(int) * rows_of(0), hipMemcpyDeviceToDevice, s.h->stream) != hipSuccess ||
           hipMemcpyAsync(v.gJ, tJ, sizeof(int) * cnt_of(0), hipMemcpyDeviceToDevice, s.h->stream) != hipSuccess ||
           hipMemcpyAsync(v.gV, tV, sizeof(float) * cnt_of(0), hipMemcpyDeviceToDevice, s.h->stream) != hipSuccess ||
           hipStreamSynchronize(s.h->stream) != hipSuccess)
-        return done(fail(SPGEMM_ERR_HIP, "RCCL self exchange: copy back failed: %s", hipGetErrorString(hipGetLastError())));
-      return done(SPGEMM_OK);
+        return drained(st, fail(SPGEMM_ERR_HIP, "RCCL self exchange: copy back failed: %s", hipGetErrorString(hipGetLastError())));
+      return SPGEMM_OK;
     }
     NCCLCHK(R.GroupStart());
     for (size_t li = 0; li < g->sh.size(); ++li) {
@@ -476,8 +474,8 @@ static int allgatherv_segments(spgemm_group* g, const std::vector<int>& ends, co
   // HOST: every segment once to pinned host memory, then to every other shard
   size_t need = 0;
   for (int r = 0; r < G; ++r) need = std::max(need, std::max(rows_of(r) * sizeof(int), cnt_of(r) * sizeof(float)));
-  void* stage = nullptr;
-  HIPCHK(hipHostMalloc(&stage, std::max<size_t>(need, 16), hipHostMallocDefault));
+  PinBlock<char> stage;
+  HIPCHK(stage.reserve(std::max<size_t>(need, 16)));
   auto bounce = [&](size_t q, int which) -> int {
     spgemm_shard& src = g->sh[q];
     const int r = src.grank;
@@ -498,7 +496,6 @@ static int allgatherv_segments(spgemm_group* g, const std::vector<int>& ends, co
   int rc = SPGEMM_OK;
   for (size_t q = 0; q < g->sh.size() && !rc; ++q)
     for (int which = 0; which < 3 && !rc; ++which) rc = bounce(q, which);
-  hipHostFree(stage);
   return rc;
 }
 
@@ -514,8 +511,8 @@ struct spgemm_sharded {
   struct Local {
     DevCSR A;                                     // this shard's row block of A
     DevCSR B;                                     // replica of B
-    int* lIC = nullptr;                           // local rowPtr of the block (m_s + 1)
-    int* gI = nullptr; int* gJ = nullptr; float* gV = nullptr;   // gathered C (or the block alone when not gathered)
+    DevBuf<int> lIC;                              // local rowPtr of the block (m_s + 1)
+    DevBuf<int> gI, gJ; DevBuf<float> gV;         // gathered C (or the block alone when not gathered)
     size_t capC = 0;
     long long nnz = 0;                            // entries the arrays hold after the last step
     bool gathered = false;
@@ -527,11 +524,9 @@ struct spgemm_sharded {
 extern "C" int hip_sharded_spmm_destroy(spgemm_sharded* job) {
   if (!job) return SPGEMM_OK;
   for (size_t i = 0; i < job->loc.size(); ++i) {
-    const int dev = job->g->sh[i].device;
-    auto& L = job->loc[i];
-    hipSetDevice(dev);
-    L.A.reset(); L.B.reset();
-    pool().release(L.lIC); pool().release(L.gI); pool().release(L.gJ); pool().release(L.gV);
+    hipSetDevice(job->g->sh[i].device);
+    hipStreamSynchronize(job->g->sh[i].h->stream);   // (a step whose symbolic phase failed may have left kernels queued)
+    job->loc[i] = spgemm_sharded::Local();
   }
   delete job;
   return SPGEMM_OK;
@@ -563,8 +558,8 @@ extern "C" int hip_sharded_spmm_create(spgemm_group* g, const int* IA, const int
     const int r0 = job->ends[s.grank], r1 = job->ends[s.grank + 1];
     CHK(upload_csr(s.device, IA, JA, A, r0, r1, k, &L.A));
     CHK(upload_csr(s.device, IB, JB, B, 0, k, n, &L.B));
-    HIPCHK(pool().alloc((void**)&L.lIC, sizeof(int) * ((size_t)(r1 - r0) + 1)));
-    HIPCHK(pool().alloc((void**)&L.gI, sizeof(int) * ((size_t)m + 1)));
+    HIPCHK(L.lIC.alloc((size_t)(r1 - r0) + 1));
+    HIPCHK(L.gI.alloc((size_t)m + 1));
     CHK(ws_ensure(s.h, r1 - r0));
     return SPGEMM_OK;
   });
@@ -575,11 +570,10 @@ extern "C" int hip_sharded_spmm_create(spgemm_group* g, const int* IA, const int
 
 static int ensure_cap(spgemm_sharded::Local& L, size_t entries) {
   if (entries <= L.capC && L.gJ) return SPGEMM_OK;
-  pool().release(L.gJ); pool().release(L.gV);
-  L.gJ = nullptr; L.gV = nullptr; L.capC = 0;
+  L.gJ.reset(); L.gV.reset(); L.capC = 0;
   const size_t cap = entries + entries / 16 + 1024;
-  HIPCHK(pool().alloc((void**)&L.gJ, sizeof(int) * cap));
-  HIPCHK(pool().alloc((void**)&L.gV, sizeof(float) * cap));
+  HIPCHK(L.gJ.alloc(cap));
+  HIPCHK(L.gV.alloc(cap));
   L.capC = cap;
   return SPGEMM_OK;
 }
@@ -622,13 +616,13 @@ extern "C" int hip_sharded_spmm_step(spgemm_sharded* job, int gather, long long*
     HIPCHK(hipSetDevice(s.device));
     const long long off = doGather ? offs[(size_t)s.grank] : 0;
     CHK(ensure_cap(L, (size_t)std::max<long long>(doGather ? total : localNnz[i], 1)));
-    CHK(numeric_phase(s.h, L.A.I, L.A.J, L.A.V.p, L.B.I, L.B.J, L.B.V.p, L.A.rows, job->n, L.lIC, L.gJ + off, L.gV + off));
+    CHK(numeric_phase(s.h, L.A.I, L.A.J, L.A.V.p, L.B.I, L.B.J, L.B.V.p, L.A.rows, job->n, L.lIC, L.gJ.p + off, L.gV.p + off));
     const int r0 = doGather ? job->ends[s.grank] : 0;
     const int cnt = L.A.rows + ((!doGather || s.grank == G - 1) ? 1 : 0);
     clear_stale_hip_error();
-    if (cnt > 0) hipLaunchKernelGGL(k_offset_copy, dim3(cdiv(cnt, 256)), dim3(256), 0, s.h->stream, cnt, L.lIC, (int)off, L.gI + r0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s.h->stream));
+    if (cnt > 0) hipLaunchKernelGGL(k_offset_copy, dim3(cdiv(cnt, 256)), dim3(256), 0, s.h->stream, cnt, L.lIC.p, (int)off, L.gI.p + r0);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s.h->stream) != hipSuccess)
+      return drained(s.h->stream, fail(SPGEMM_ERR_HIP, "sharded SpGEMM: row pointer of the block: %s", hipGetErrorString(hipGetLastError())));
     L.nnz = doGather ? total : localNnz[i];
     L.gathered = doGather;
     return SPGEMM_OK;

@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <sys/mman.h>
 #include <thread>
@@ -165,6 +166,32 @@ struct DevBuf {
   operator T*() const { return p; }
 };
 
+// One block of the driver's with one owner and a capacity in elements: device memory (hipMalloc), or pinned host memory
+// when Pinned.  The workspaces of a handle, a shard and the copy lanes are such blocks and NOT pool blocks: they live as
+// long as their owner, and the pool's cached bytes stay what the calls leave there.  One operation: room for n elements,
+// the contents discarded (n = 0: no block).  A failed reserve leaves no block and the error in the thread's slot.
+template <class T, bool Pinned = false>
+struct Block {
+  T* p = nullptr;
+  size_t cap = 0;
+  Block() = default;
+  Block(Block&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  Block& operator=(Block&& o) noexcept { if (this != &o) { reserve(0); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+  ~Block() { reserve(0); }
+  hipError_t reserve(size_t n) {
+    if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr; cap = 0;
+    if (n == 0) return hipSuccess;
+    const hipError_t e = Pinned ? hipHostMalloc((void**)&p, sizeof(T) * n, hipHostMallocDefault) : hipMalloc((void**)&p, sizeof(T) * n);
+    if (e == hipSuccess) cap = n; else p = nullptr;
+    return e;
+  }
+  operator T*() const { return p; }
+  T* operator->() const { return p; }
+};
+template <class T> using DevBlock = Block<T, false>;
+template <class T> using PinBlock = Block<T, true>;
+
 // A CSR matrix as a kernel reads it; nothing is owned.  len == nullptr: packed, row r is [I[r], I[r + 1]).  Otherwise row r
 // is [I[r], I[r] + len[r]) of (J, V), se[r] is the same extent as one {start, end} pair (what the classification gathers)
 // and nnz is the extent of the arrays.
@@ -201,7 +228,9 @@ using DevCSR = DevCSRT<float>;
 // The pool hands a released block to other handles and streams, so a block goes back only when no queued kernel can still
 // touch it.  The owners above release when they leave scope; two rules make that late enough.
 // Rule A: a failure may leave kernels queued that write the blocks of the failed step, so every error return of a function
-// that has queued work is `return drained(stream, rc)`: the stream is idle before the locals are destroyed.
+// that has queued work is `return drained(stream, rc)`: the stream is idle before the locals are destroyed.  It holds for
+// the whole library -- the product routes, the classification calls and the sharded jobs as much as R-MCL -- so a failed
+// call costs one stream wait; a call that succeeds waits where it always did.
 static int drained(hipStream_t s, int rc) {
   if (rc) (void)hipStreamSynchronize(s);
   return rc;
@@ -263,30 +292,29 @@ struct spgemm_handle {
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   // device workspace, sized for cap_m rows
   int cap_m = -1;
-  int* rowFlops = nullptr;
-  unsigned char* binId = nullptr;
-  int* blockHist = nullptr;
-  int* blockOff = nullptr;
-  int* rowIds = nullptr;
-  unsigned long long* tileSum = nullptr;
-  unsigned long long* blockP = nullptr;     // per-block sums of row flops (reduced by k_bin_scan)
-  int2* sbl = nullptr;                       // per A entry {B-row start, B-row length} (k_entry_lens), cap_nnz entries
-  int* batchStart = nullptr;                 // one-pass path: first row of every batch (3*cap_m + 64 entries)
-  unsigned long long* chainWords = nullptr;  // ... and the batches' words of the chained prefix
+  DevBlock<int> rowFlops;
+  DevBlock<unsigned char> binId;
+  DevBlock<int> blockHist;
+  DevBlock<int> blockOff;
+  DevBlock<int> rowIds;
+  DevBlock<unsigned long long> tileSum;
+  DevBlock<unsigned long long> blockP;       // per-block sums of row flops (reduced by k_bin_scan)
+  DevBlock<int2> sbl;                        // per A entry {B-row start, B-row length} (k_entry_lens); sized by nnz(A)
+  DevBlock<int> batchStart;                  // one-pass path: first row of every batch (3*cap_m + 64 entries)
+  DevBlock<unsigned long long> chainWords;   // ... and the batches' words of the chained prefix
   int pathMode = 0;                          // SPGEMM_PATH: 0 per-row kernels for every row (rounds 1-3); 1 rows up to smallMax
                                              // products through the wave-per-batch kernels, two passes; 2 the same in ONE pass
   int chainCfg = 0;                          // SPGEMM_CHAIN_CFG: kernel geometry (experiments)
-  long long cap_nnz = -1;
-  HostMirror* dsmall = nullptr;
-  HostMirror* hsmall = nullptr;
+  DevBlock<HostMirror> dsmall;
+  PinBlock<HostMirror> hsmall;
   HostMirror mirror;                 // host copy taken at the end of the symbolic phase
   const int* cur_rowIds = nullptr;   // row list of the pending symbolic phase (workspace or caller's)
   int sym_m = -1;                    // rows of the pending symbolic phase, -1 = none
-  hipEvent_t kev[2 * SPGEMM_NKERNELS];
-  bool kused[SPGEMM_NKERNELS];
+  hipEvent_t kev[2 * SPGEMM_NKERNELS] = {};
+  bool kused[SPGEMM_NKERNELS] = {};
   unsigned ktiming = 0;              // bit i: launches of kernel i are bracketed by events (spgemm_hip_set_kernel_timing)
   hipEvent_t evMid = nullptr;        // "classification is on the host" marker of the one-shot path
-  HostMirror* hmid = nullptr;        // pinned copy taken right after the classify kernels
+  PinBlock<HostMirror> hmid;         // pinned copy taken right after the classify kernels
   // side streams: the per-bin kernels of one phase are independent; SPGEMM_CONCURRENT=1 runs them concurrently
   // (default off: the 155 KB-LDS big-row kernel owns the CUs it runs on, overlap measured slower than serial)
   static constexpr int NSIDE = 4;
@@ -297,10 +325,10 @@ struct spgemm_handle {
   int U = 2;                         // rounds in flight per wave in the hash kernels (SPGEMM_U=2|4|8)
   // column bitmaps of the big rows, saved by the symbolic pass for the rank kernel (n <= BIG_WC).  Sized from
   // the previous calls (the number of big rows is only known on the host after the symbolic phase).
-  unsigned* bigBitmaps = nullptr;
-  int bm_cap = 0;
-  int2* spill = nullptr;
-  int spill_blocks = 0;
+  DevBlock<unsigned> bigBitmaps;
+  int bm_cap() const { return (int)(bigBitmaps.cap / BIG_WORDS); }          // big rows it has room for
+  DevBlock<int2> spill;
+  int spill_blocks() const { return (int)(spill.cap / BH_SPILL); }
   int bhCap = BH_CAP;
   int bhMargin = 125;                // parking region per hash class, % of products/npass (SPGEMM_BHMARGIN; tests force overflows)
   // direct big-row kernel (n > BIG_WC, float): the symbolic pass logs the re-hit columns of the big rows into rlLog (numCU
@@ -314,11 +342,11 @@ struct spgemm_handle {
                                      // CU count -- below it every row has a CU to itself in either kernel and the second launch costs more
                                      // than it saves (web surrogate: the bin 0.018 -> 0.023 ms); the tests set 1
   int rlRegionEnv = 0;               // SPGEMM_RLREGION: ints per block region instead of the computed size (tests fill a region)
-  int2* rlMeta = nullptr;
-  int rl_rows = 0;
-  int* rlLog = nullptr;
-  int rl_region = 0;
-  int* bigFallback = nullptr;        // rows of the fallback list (workspace block, one int per row of A)
+  DevBlock<int2> rlMeta;             // (the two come and go together: grow_rehit_log)
+  DevBlock<int> rlLog;
+  int rl_rows() const { return (int)rlMeta.cap; }
+  int rl_region() const { return (int)(rlLog.cap / (size_t)numCU); }
+  DevBlock<int> bigFallback;         // rows of the fallback list (workspace block, one int per row of A)
   bool bdLogged = false;             // the pending / current product's symbolic pass logged (launch_symbolic)
   bool bdRan = false;                // the latest numeric launch used k_num_bigdirect
   // direct kernel of bins 6-7 (513-4096 products, float, any n): k_sym_hash<.., true> logs the rows' re-hit columns into mrLog
@@ -358,11 +386,11 @@ struct spgemm_handle {
   int spPrevRows6 = 0;
   bool spRan = false;                // the latest symbolic launch used k_sym_midpair
   long long mrLogEnv = 0;            // SPGEMM_MRLOG: ints of the log instead of the computed size (tests run it out of space)
-  int2* mrMeta = nullptr;            // workspace block, one pair per row of A
-  int* midFallback = nullptr;        // workspace block, three ints per row of A: bin 6's list, then (at cap_m) bin 7's, then (at
+  DevBlock<int2> mrMeta;             // workspace block, one pair per row of A
+  DevBlock<int> midFallback;         // workspace block, three ints per row of A: bin 6's list, then (at cap_m) bin 7's, then (at
                                      // 2 cap_m) the rows of bin 6 that k_num_midwave passes on to k_num_middirect
-  int* mrLog = nullptr;
-  long long mr_cap = 0;
+  DevBlock<int> mrLog;
+  long long mr_cap() const { return (long long)mrLog.cap; }
   bool mdLogged = false;             // the pending / current product's symbolic pass logged bins 6-7
   bool mdRan[2] = {false, false};    // the latest numeric launch used k_num_middirect for bin 6 / bin 7
   int h1sym = 32;                    // blocks per CU of the wave-per-row symbolic kernel (SPGEMM_H1SYM, experiments)
@@ -374,51 +402,50 @@ struct spgemm_handle {
   int prev_m = -1;                   // shape and sizes of the previous one-shot SpGEMM (allocation policy of the next one)
   unsigned long long prev_P = 0;
   long long prev_nnzC = -1;
+  // The handle owns its streams, events and workspace blocks: the streams are waited for and destroyed with the events here
+  // (whichever of them a failed spgemm_hip_create got as far as making), the block owners above free the rest.
+  ~spgemm_handle() {
+    hipSetDevice(device);
+    if (stream) hipStreamSynchronize(stream);
+    for (auto& st : side) if (st && st != stream) { hipStreamSynchronize(st); hipStreamDestroy(st); }
+    if (evMid) hipEventDestroy(evMid);
+    for (auto& e : ev) if (e) hipEventDestroy(e);
+    for (auto& e : kev) if (e) hipEventDestroy(e);
+    if (fork_ev) hipEventDestroy(fork_ev);
+    for (auto& e : join_ev) if (e) hipEventDestroy(e);
+    if (stream) hipStreamDestroy(stream);
+  }
 };
 
 static std::mutex g_count_mu;
 static std::map<int, int> g_handles_on;          // device -> live handles (the pool is trimmed when the last one goes)
 
-// the workspace blocks sized by the row count: where each pointer lives and its bytes for `cap` rows
-struct WsBlock { void** ptr; size_t bytes; };
-static std::array<WsBlock, 12> ws_blocks(spgemm_handle* h, size_t cap) {
+// the workspace blocks sized by the row count: f(block, its elements for `cap` rows) for each of the twelve, until one fails
+template <class F>
+static int ws_blocks(spgemm_handle* h, size_t cap, F f) {
   const size_t nblk = (cap + K1_THREADS - 1) / K1_THREADS;
   const size_t ntile = (cap + 1 + SCAN_TILE - 1) / SCAN_TILE + 1;
-  return {{{(void**)&h->rowFlops, sizeof(int) * cap},
-           {(void**)&h->binId, cap},
-           {(void**)&h->blockHist, sizeof(int) * nblk * NSLOTS},
-           {(void**)&h->blockOff, sizeof(int) * nblk * NSLOTS},
-           {(void**)&h->rowIds, sizeof(int) * cap},
-           {(void**)&h->tileSum, sizeof(unsigned long long) * ntile},
-           {(void**)&h->blockP, sizeof(unsigned long long) * nblk},
-           {(void**)&h->bigFallback, sizeof(int) * cap},
-           {(void**)&h->mrMeta, sizeof(int2) * cap},
-           {(void**)&h->midFallback, sizeof(int) * 3 * cap},
-           {(void**)&h->batchStart, sizeof(int) * (3 * cap + 64)},
-           {(void**)&h->chainWords, sizeof(unsigned long long) * (3 * cap + 64)}}};
-}
-
-static int ws_free(spgemm_handle* h) {
-  for (const WsBlock& b : ws_blocks(h, 0)) { hipFree(*b.ptr); *b.ptr = nullptr; }
-  h->cap_m = -1;
+  int rc;
+  if ((rc = f(h->rowFlops, cap)) || (rc = f(h->binId, cap)) || (rc = f(h->blockHist, nblk * NSLOTS)) ||
+      (rc = f(h->blockOff, nblk * NSLOTS)) || (rc = f(h->rowIds, cap)) || (rc = f(h->tileSum, ntile)) ||
+      (rc = f(h->blockP, nblk)) || (rc = f(h->bigFallback, cap)) || (rc = f(h->mrMeta, cap)) ||
+      (rc = f(h->midFallback, 3 * cap)) || (rc = f(h->batchStart, 3 * cap + 64)) || (rc = f(h->chainWords, 3 * cap + 64)))
+    return rc;
   return SPGEMM_OK;
 }
 
 static int ws_ensure_entries(spgemm_handle* h, long long nnzA) {
-  if (nnzA <= h->cap_nnz) return SPGEMM_OK;
-  hipFree(h->sbl);
-  h->sbl = nullptr; h->cap_nnz = -1;
-  const long long cap = nnzA + nnzA / 8 + 1024;
-  HIPCHK(hipMalloc((void**)&h->sbl, sizeof(int2) * (size_t)cap));
-  h->cap_nnz = cap;
+  if (h->sbl && nnzA <= (long long)h->sbl.cap) return SPGEMM_OK;
+  HIPCHK(h->sbl.reserve((size_t)(nnzA + nnzA / 8 + 1024)));
   return SPGEMM_OK;
 }
 
 static int ws_ensure(spgemm_handle* h, int m) {
   if (m <= h->cap_m) return SPGEMM_OK;
-  ws_free(h);
   const size_t cap = (size_t)m + (size_t)m / 8 + 1024;
-  for (const WsBlock& b : ws_blocks(h, cap)) HIPCHK(hipMalloc(b.ptr, b.bytes));
+  h->cap_m = -1;
+  ws_blocks(h, cap, [](auto& b, size_t) { b.reserve(0); return SPGEMM_OK; });   // all of them go before the first comes back
+  CHK(ws_blocks(h, cap, [](auto& b, size_t n) { HIPCHK(b.reserve(n)); return SPGEMM_OK; }));
   h->cap_m = (int)std::min<size_t>(cap, 0x7fffffff);
   return SPGEMM_OK;
 }
@@ -460,7 +487,7 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
     return fail(SPGEMM_ERR_NODEVICE, "no HIP device visible: libspgemm_hip has no CPU fallback");
   if (device < 0 || device >= n) return fail(SPGEMM_ERR_ARG, "device %d out of range [0,%d)", device, n);
   HIPCHK(hipSetDevice(device));
-  spgemm_handle* h = new spgemm_handle();
+  std::unique_ptr<spgemm_handle> h(new spgemm_handle());   // a failed step below leaves nothing behind
   h->device = device;
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
@@ -468,7 +495,6 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   for (auto& e : h->ev) HIPCHK(hipEventCreate(&e));
   for (auto& e : h->kev) HIPCHK(hipEventCreate(&e));
-  for (auto& u : h->kused) u = false;
   { const char* e = getenv("SPGEMM_CONCURRENT"); h->serial = !(e && e[0] == '1'); }
 #ifdef SMF_ABLATE
   { int v = 0; env_int("SPGEMM_ABLATE", INT_MIN, INT_MAX, &v); HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(smf::g_ablate), &v, sizeof(int))); }
@@ -507,13 +533,12 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
   }
   HIPCHK(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
   for (auto& e : h->join_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIPCHK(hipMalloc((void**)&h->dsmall, sizeof(HostMirror)));
-  HIPCHK(hipHostMalloc((void**)&h->hsmall, sizeof(HostMirror), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&h->hmid, sizeof(HostMirror), hipHostMallocDefault));
+  HIPCHK(h->dsmall.reserve(1));
+  HIPCHK(h->hsmall.reserve(1));
+  HIPCHK(h->hmid.reserve(1));
   HIPCHK(hipEventCreateWithFlags(&h->evMid, hipEventDisableTiming));
   { const char* e = getenv("SPGEMM_KTIMING"); if (e) h->ktiming = (unsigned)strtoul(e, nullptr, 0); }
   memset(&h->stats, 0, sizeof(h->stats));
-  { std::lock_guard<std::mutex> lk(g_count_mu); ++g_handles_on[device]; }
   // the big-row kernels use more than the default 64 KB of dynamic LDS
   HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
   HIPCHK(hipFuncSetAttribute((const void*)k_sym_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigSymShared)));
@@ -522,35 +547,18 @@ extern "C" int spgemm_hip_create(spgemm_handle** out, int device) {
                                (int)sizeof(BigDirectShared<nw, slots>)); }));
   HIPCHK(hipFuncSetAttribute((const void*)k_num_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigNumShared)));
   HIPCHK(hipFuncSetAttribute((const void*)k_num_bighash, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(BigHashShared)));
-  *out = h;
+  { std::lock_guard<std::mutex> lk(g_count_mu); ++g_handles_on[device]; }
+  *out = h.release();
   return SPGEMM_OK;
 }
 
 extern "C" int spgemm_hip_destroy(spgemm_handle* h) {
   if (!h) return SPGEMM_OK;
-  hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
-  for (auto& st : h->side) if (st && st != h->stream) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-  ws_free(h);
-  hipFree(h->bigBitmaps);
-  hipFree(h->spill);
-  hipFree(h->rlMeta);
-  hipFree(h->rlLog);
-  hipFree(h->mrLog);
-  hipFree(h->sbl);
-  hipFree(h->dsmall);
-  hipHostFree(h->hsmall);
-  hipHostFree(h->hmid);
-  if (h->evMid) hipEventDestroy(h->evMid);
-  for (auto& e : h->ev) if (e) hipEventDestroy(e);
-  for (auto& e : h->kev) if (e) hipEventDestroy(e);
-  if (h->fork_ev) hipEventDestroy(h->fork_ev);
-  for (auto& e : h->join_ev) if (e) hipEventDestroy(e);
-  if (h->stream) hipStreamDestroy(h->stream);
-  bool last = false;
-  { std::lock_guard<std::mutex> lk(g_count_mu); last = --g_handles_on[h->device] <= 0; }
-  if (last) pool().trim(h->device);              // cached blocks are idle by the pool's invariant
+  const int device = h->device;
   delete h;
+  bool last = false;
+  { std::lock_guard<std::mutex> lk(g_count_mu); last = --g_handles_on[device] <= 0; }
+  if (last) pool().trim(device);                 // cached blocks are idle by the pool's invariant
   return SPGEMM_OK;
 }
 
@@ -574,7 +582,7 @@ extern "C" int spgemm_hip_debug_bigrow_paths(spgemm_handle* h, int* direct_rows,
   *fallback_rows = h->bdRan ? h->mirror.fbBin[1] : nbig;
   *direct_rows = nbig - *fallback_rows;
   *rehit_cap = bd_cap(slots_of(BdGeos(), h->bdCfg));
-  *region_ints = h->rl_region;
+  *region_ints = h->rl_region();
   return SPGEMM_OK;
 }
 
@@ -594,7 +602,7 @@ extern "C" int spgemm_hip_debug_midrow_log(spgemm_handle* h, long long* logged, 
   *logged = 0;
   for (int b = 0; b < 2; ++b) if (h->mdRan[b]) *logged += (long long)h->mirror.mrLogged[b];
   *reserved = h->mdLogged ? (long long)h->mirror.mrCursor : 0;
-  *capacity = h->mr_cap;
+  *capacity = h->mr_cap();
   return SPGEMM_OK;
 }
 
@@ -869,16 +877,16 @@ static int launch_symbolic(spgemm_handle* h, const int* dIA, const int* dJB,
     // (the grid never exceeds the CU count: rlLog has one region per CU)
     if (h->bdLogged)
       hipLaunchKernelGGL(k_sym_big<true>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
-                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
-                         h->rlMeta, h->rlLog ? h->rl_rows : 0, h->rlLog, h->rl_region, bd_cap(slots_of(BdGeos(), h->bdCfg)), h->bigFallback,
+                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap(), qc + 0 * 32,
+                         h->rlMeta, h->rlLog ? h->rl_rows() : 0, h->rlLog, h->rl_region(), bd_cap(slots_of(BdGeos(), h->bdCfg)), h->bigFallback,
                          &h->dsmall->fbBin[1]);
     else
       hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(m, 1, cu)), dim3(BIG_THREADS), sizeof(BigSymShared), st, bp, 8,
-                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap, qc + 0 * 32,
+                         rowIds, dIA, sbl, dJB, n, dIC, h->bigBitmaps, h->bm_cap(), qc + 0 * 32,
                          (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr); }
   // the logging variants of the two launches below: one log and one cursor for both, a fallback list each
   auto mid_log = [&](int which) {
-    return MidLogArgs{h->mrMeta, h->mrLog, h->mrLog ? h->mr_cap : 0ll, h->mdCap, &h->dsmall->mrCursor,
+    return MidLogArgs{h->mrMeta, h->mrLog, h->mrLog ? h->mr_cap() : 0ll, h->mdCap, &h->dsmall->mrCursor,
                       h->midFallback + (which ? h->cap_m : 0), &h->dsmall->fbMid[2 * which + 1], &h->dsmall->mrLogged[which]};
   };
   if (minBin <= 7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_SYM_HASH8, st);
@@ -954,7 +962,7 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
     hipStream_t st = h->side[3];
     if (n <= BIG_WC) { KTimer t(h, SPGEMM_K_NUM_BIG, st);
       hipLaunchKernelGGL(k_num_big, dim3(clampi(rows(8, 9), 1, cu)), dim3(BIG_THREADS), sizeof(BigNumShared), st,
-                         bp, 8, rowIds, dIA, sbl, dA, dJB, dB, n, dIC, dJC, dC, err, h->bigBitmaps, h->bm_cap,
+                         bp, 8, rowIds, dIA, sbl, dA, dJB, dB, n, dIC, dJC, dC, err, h->bigBitmaps, h->bm_cap(),
                          qc + 4 * 32);
     } else { KTimer t(h, SPGEMM_K_NUM_BIGHASH, st);   // both launches of the direct path are timed under this id
       const int blocks = clampi(rows(8, 9), 1, cu);
@@ -963,24 +971,19 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
       // (and so does a call with only a few such rows: bdMinRows)
       const bool direct = h->bdLogged && !pcnt && rows(8, 9) >= h->bdMinRows;
       h->bdRan = direct;
-      if (blocks > h->spill_blocks) {                  // parking space of multi-pass rows: 1 MB per block, kept
-        hipFree(h->spill);
-        h->spill = nullptr;
-        h->spill_blocks = 0;
-        if (hipMalloc((void**)&h->spill, (size_t)blocks * BH_SPILL * sizeof(int2)) == hipSuccess) h->spill_blocks = blocks;
-        else (void)hipGetLastError();                  // without it those rows walk once per pass
-      }
+      // parking space of multi-pass rows: 1 MB per block, kept; without it those rows walk once per pass
+      if (blocks > h->spill_blocks() && h->spill.reserve((size_t)blocks * BH_SPILL) != hipSuccess) (void)hipGetLastError();
       hipLaunchKernelGGL(k_num_bighash, dim3(blocks), dim3(BIG_THREADS), sizeof(BigHashShared), st,
                          direct ? h->dsmall->fbBin : bp, direct ? 0 : 8, direct ? h->bigFallback : rowIds, dIA, sbl, dA, dJB,
                          dB, dIC, dJC, dC, err, qc + 4 * 32, h->rowFlops,
-                         h->spill_blocks >= blocks ? h->spill : (int2*)nullptr, BH_SPILL, h->bhCap, h->bhMargin);
+                         h->spill_blocks() >= blocks ? h->spill.p : (int2*)nullptr, BH_SPILL, h->bhCap, h->bhMargin);
       if (direct && h->rlLog)                          // (no workspace yet: every row is in the fallback list)
         with_geometry(BdGeos(), h->bdCfg, [&](auto nw, auto slots) {
           const int lds = (int)sizeof(BigDirectShared<nw, slots>);
           const int perCU = blocks_per_cu(lds, nw);
           hipLaunchKernelGGL((k_num_bigdirect<nw, slots>), dim3(clampi(rows(8, 9), 1, cu * perCU)), dim3(WAVE * nw), lds, st,
                              bp, 8, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qc + 8 * 32,
-                             (const int2*)h->rlMeta, h->rl_rows, (const int*)h->rlLog);
+                             (const int2*)h->rlMeta, h->rl_rows(), (const int*)h->rlLog);
           return 0; }); }
     if (pcnt) hipLaunchKernelGGL(k_rmcl_fix_rows<float>, dim3(clampi(rows(8, 9), 1, cu * 8)), dim3(256), 0, st,
                                  bp, 8, 9, rowIds, dIC, dJC, dC, pcnt, -1);   // lmin = -1: every row of the bin
@@ -1004,7 +1007,7 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
       const int perCU = blocks_per_cu((int)sizeof(MidDirectShared<nw, slots>), nw);
       hipLaunchKernelGGL((k_num_middirect<nw, slots>), dim3(clampi(nrows, 1, cu * perCU)), dim3(WAVE * nw), 0, st,
                          lbp, lbin, lrows, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, qd, (const int*)h->rowFlops,
-                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, h->mdCap, wcap, took);
+                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap(), h->mdCap, wcap, took);
       return 0; });
   };
   if (mid7) { hipStream_t st = h->side[2]; KTimer t(h, SPGEMM_K_NUM_HASH8, st);
@@ -1015,7 +1018,7 @@ static int launch_numeric(spgemm_handle* h, const int* dIA, const float* dA,
     if (waveCap >= 0) {
       hipLaunchKernelGGL(k_num_midwave, dim3(grid8(rows(6, 7), cu * h->mwPerCU)), dim3(WAVE), 0, st, h->dsmall->slotBase,
                          SLOT_H4A, SLOT_H4B, rowIds, dIA, sbl, dA, dJB, dB, dIC, dJC, dC, err, (const int*)h->rowFlops,
-                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap, waveCap, &h->dsmall->mdTook[0],
+                         (const int2*)h->mrMeta, (const int*)h->mrLog, h->mr_cap(), waveCap, &h->dsmall->mdTook[0],
                          h->midFallback + 2 * (size_t)h->cap_m, &h->dsmall->mwRest[1]);
       launch_mid(6, rows(6, 7), qc + 6 * 32, st, waveCap, &h->dsmall->mdTook[1], h->dsmall->mwRest, 0,
                  (const int*)(h->midFallback + 2 * (size_t)h->cap_m));
@@ -1219,13 +1222,8 @@ static int symbolic_phase(spgemm_handle* h, const int* dIA, const int* dJA, int 
 // room for the big rows' bitmaps next time (rank kernel only)
 static void grow_bitmaps(spgemm_handle* h, int n) {
   const int nbig = h->mirror.binPtr[NBINS] - h->mirror.binPtr[NBINS - 1];
-  if (n <= BIG_WC && nbig > h->bm_cap) {
-    hipFree(h->bigBitmaps);
-    h->bigBitmaps = nullptr;
-    const int cap = nbig + nbig / 4 + 16;
-    if (hipMalloc((void**)&h->bigBitmaps, (size_t)cap * BIG_WORDS * sizeof(unsigned)) == hipSuccess) h->bm_cap = cap;
-    else { h->bm_cap = 0; (void)hipGetLastError(); }
-  }
+  if (n <= BIG_WC && nbig > h->bm_cap() && h->bigBitmaps.reserve((size_t)(nbig + nbig / 4 + 16) * BIG_WORDS) != hipSuccess)
+    (void)hipGetLastError();
 }
 
 // room for the big rows' re-hit log next time (direct kernel only).  Size: one metadata slot per big row seen (+25 %), and
@@ -1234,20 +1232,15 @@ static void grow_bitmaps(spgemm_handle* h, int n) {
 // region holds about twice what its block logs.  A row that finds its region full takes the fallback kernel: never wrong.
 static void grow_rehit_log(spgemm_handle* h, int n) {
   const int nbig = h->mirror.binPtr[NBINS] - h->mirror.binPtr[NBINS - 1];
-  if (!h->bigDirect || n <= BIG_WC || nbig <= h->rl_rows || nbig < h->bdMinRows) return;   // (too few rows: the log would not be used)
-  hipFree(h->rlMeta); hipFree(h->rlLog);
-  h->rlMeta = nullptr; h->rlLog = nullptr; h->rl_rows = 0; h->rl_region = 0;
+  if (!h->bigDirect || n <= BIG_WC || nbig <= h->rl_rows() || nbig < h->bdMinRows) return;   // (too few rows: the log would not be used)
+  h->rlMeta.reserve(0); h->rlLog.reserve(0);             // both go before either comes back
   const int cap = nbig + nbig / 4 + 16;
   const long long perBlock = ((long long)cap + h->numCU - 1) / h->numCU * RL_ROW_BUDGET;
   long long region = h->rlRegionEnv > 0 ? h->rlRegionEnv : std::max<long long>(RL_MIN_REGION, perBlock);
   region = std::min<long long>(region, (1ll << 30) / h->numCU);           // entry indices stay ints
-  if (hipMalloc((void**)&h->rlMeta, (size_t)cap * sizeof(int2)) == hipSuccess &&
-      hipMalloc((void**)&h->rlLog, (size_t)region * (size_t)h->numCU * sizeof(int)) == hipSuccess) {
-    h->rl_rows = cap; h->rl_region = (int)region;
-  } else {
+  if (h->rlMeta.reserve((size_t)cap) != hipSuccess || h->rlLog.reserve((size_t)region * (size_t)h->numCU) != hipSuccess) {
     (void)hipGetLastError();
-    hipFree(h->rlMeta); hipFree(h->rlLog);
-    h->rlMeta = nullptr; h->rlLog = nullptr;
+    h->rlMeta.reserve(0); h->rlLog.reserve(0);           // one without the other is no log
   }
 }
 
@@ -1258,21 +1251,21 @@ static void grow_midrow_log(spgemm_handle* h) {
   const int* hb = h->mirror.binPtr;
   if (!h->mdLogged || std::max(hb[7] - hb[6], hb[8] - hb[7]) < h->mdMinRows) return;   // (too few rows: the log would not be used)
   const long long used = (long long)std::min<unsigned long long>(h->mirror.mrCursor, 1ull << 30);
-  if (used == 0 || (h->mrLog && (h->mrLogEnv > 0 || used <= h->mr_cap))) return;
-  hipFree(h->mrLog);
-  h->mrLog = nullptr; h->mr_cap = 0;
+  if (used == 0 || (h->mrLog && (h->mrLogEnv > 0 || used <= h->mr_cap()))) return;
   const long long want = h->mrLogEnv > 0 ? h->mrLogEnv : std::min<long long>(used + used / 4 + 16 * MD_CHUNK, 1ll << 30);
-  if (hipMalloc((void**)&h->mrLog, (size_t)want * sizeof(int)) == hipSuccess) h->mr_cap = want;
-  else (void)hipGetLastError();
+  if (h->mrLog.reserve((size_t)want) != hipSuccess) (void)hipGetLastError();
 }
 
 // ---- double values (spgemm_f64_device.hpp): the numeric phase only; classification, symbolic pass and scan are the
 // float pipeline's.  One launch per bin, on the side streams launch_numeric uses, each timed into its bin's slot of
 // spgemm_stats.ms_kernel.  Rows of bin 8 wider than the multi-pass LDS kernel takes get device-memory tables: their largest
 // length sizes them (one small kernel and a host read, only when bin 8 has rows).
+// The launch's own device blocks, owned by the caller until the kernels are done: the probe word pair of bin 8 and the
+// device-memory tables (one block: keys, then values)
+struct F64Scratch { DevBuf<int> probe; DevBuf<char> tables; };
 static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB,
                               const int* rowIds, const int* hostBinPtr, const int* dIC, int* dJC, double* dC,
-                              int** gbuf, int* pcnt = nullptr) {
+                              F64Scratch* scratch, int* pcnt = nullptr) {
   const int2* sbl = h->sbl;
   clear_stale_hip_error();
   const int* bp = h->dsmall->binPtr;
@@ -1287,9 +1280,8 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   double* gvals = nullptr;
   int gslots = 0, gblocks = 0;
   if (rows(8, 9) > 0) {
-    int* dw = nullptr;
-    HIPCHK(pool().alloc((void**)&dw, sizeof(int) * 2));
-    *gbuf = dw;
+    HIPCHK(scratch->probe.alloc(2));
+    int* const dw = scratch->probe;
     HIPCHK(hipMemsetAsync(dw, 0, sizeof(int) * 2, s));
     hipLaunchKernelGGL(k_num64_wide_rows, dim3(clampi(cdiv(rows(8, 9), 256), 1, cu)), dim3(256), 0, s, bp, 8, rowIds, dIC,
                        F64_PASS_MAXL, dw);
@@ -1301,8 +1293,8 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
       const size_t perBlock = (size_t)gslots * (sizeof(int) + sizeof(double));
       gblocks = (int)std::max<size_t>(1, std::min<size_t>({(size_t)wide[1], (size_t)cu, (size_t(1) << 30) / perBlock}));
       // one allocation: keys, then values (8-byte aligned: gslots is a multiple of 64)
-      HIPCHK(pool().alloc((void**)&gbuf[1], perBlock * (size_t)gblocks));
-      gkeys = gbuf[1];
+      HIPCHK(scratch->tables.alloc(perBlock * (size_t)gblocks));
+      gkeys = reinterpret_cast<int*>(scratch->tables.p);
       gvals = reinterpret_cast<double*>(gkeys + (size_t)gslots * gblocks);
     }
   }
@@ -1351,18 +1343,18 @@ static int launch_numeric_f64(spgemm_handle* h, const int* dIA, const double* dA
   return SPGEMM_OK;
 }
 
-// the numeric launch of either value type behind one name.  `scratch` (double only): pool blocks that the caller releases
-// once the kernels are done -- the probe word pair and the device-memory tables
+// the numeric launch of either value type behind one name (`scratch`: double only)
 static int launch_numeric_of(spgemm_handle* h, const int* dIA, const float* dA, const int* dJB, const float* dB, int n,
-                             const int* dIC, int* dJC, float* dC, int**) {
+                             const int* dIC, int* dJC, float* dC, F64Scratch*) {
   return launch_numeric(h, dIA, dA, dJB, dB, n, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC);
 }
 static int launch_numeric_of(spgemm_handle* h, const int* dIA, const double* dA, const int* dJB, const double* dB, int,
-                             const int* dIC, int* dJC, double* dC, int** scratch) {
+                             const int* dIC, int* dJC, double* dC, F64Scratch* scratch) {
   return launch_numeric_f64(h, dIA, dA, dJB, dB, h->cur_rowIds, h->mirror.binPtr, dIC, dJC, dC, scratch);
 }
 
-// phase 2: numeric into caller-provided dJC/dC; one host sync at the end (error flags)
+// phase 2: numeric into dJC/dC, which it borrows like dIC (the caller's own, or the product routes' C); one host sync at
+// the end (error flags)
 template <class V>
 static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const V* dA, const int* dIB, const int* dJB,
                          const V* dB, int m, int n, const int* dIC, int* dJC, V* dC) {
@@ -1371,59 +1363,53 @@ static int numeric_phase(spgemm_handle* h, const int* dIA, const int* dJA, const
   if (h->sym_m != m) return fail(SPGEMM_ERR_ARG, "numeric phase without a matching symbolic phase on this handle");
   hipStream_t s = h->stream;
   const int nnzC = (int)h->mirror.nnzC64;
-  int* scratch[2] = {nullptr, nullptr};
-  auto done = [&](int rc) { pool().release(scratch[0]); pool().release(scratch[1]); return rc; };
+  F64Scratch scratch;
   hipEventRecord(h->ev[4], s);
   if (m > 0 && nnzC > 0) {
     if (!dJC || !dC) return fail(SPGEMM_ERR_ARG, "output buffers are null");
-    if (int rc = launch_numeric_of(h, dIA, dA, dJB, dB, n, dIC, dJC, dC, scratch)) {
-      if (!isFloat) (void)hipStreamSynchronize(s);     // kernels already queued may read the scratch blocks
-      return done(rc);
-    }
+    if (int rc = launch_numeric_of(h, dIA, dA, dJB, dB, n, dIC, dJC, dC, &scratch)) return drained(s, rc);
   }
   hipEventRecord(h->ev[5], s);
   // (only the error word: the rest of the mirror was read at the end of the symbolic phase)
   if (hipMemcpyAsync(&h->hsmall->err, &h->dsmall->err, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
-    return done(fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError())));
-  h->sym_m = -1;
+    return drained(s, fail(SPGEMM_ERR_HIP, "numeric phase failed: %s", hipGetErrorString(hipGetLastError())));
+  h->sym_m = -1;                                       // (the stream is idle from here on)
   if (!(kAblate && isFloat) && h->hsmall->err)
-    return done(fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err));
+    return fail(SPGEMM_ERR_INTERNAL, "device invariant broken in numeric phase (flags=%d)", h->hsmall->err);
   spgemm_stats& st = h->stats;
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
   collect_kernel_times(h, false);
   if (isFloat) { grow_bitmaps(h, n); grow_rehit_log(h, n); grow_midrow_log(h); }
-  return done(SPGEMM_OK);
-}
-
-// The end of every route that has nnz(C) on the host: allocate colInd/values exactly, run the numeric phase, hand the three
-// arrays to the caller.  Owns dIC: on failure it goes back to the pool with the rest.
-template <class V>
-static int finish_exact(spgemm_handle* h, const Product<V>& p, int nnzC, int* dIC, const Result<V>& out) {
-  int* dJC = nullptr;
-  V* dC = nullptr;
-  auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
-  const size_t cap = (size_t)std::max(nnzC, 1);
-  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * cap) || hipSuccess != pool().alloc((void**)&dC, sizeof(V) * cap))
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC));
-  if (int rc = numeric_phase(h, p.IA, p.JA, p.A, p.IB, p.JB, p.B, p.m, p.n, dIC, dJC, dC)) return cleanup(rc);
-  *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = nnzC;
   return SPGEMM_OK;
 }
 
-// the two-phase pipeline from its start: symbolic phase, exact allocation, numeric phase.  Owns dIC like finish_exact.
+// The C of a product lives in ONE DevCSRT<V> in the frame of the entry point's route (spgemm_device, hip_gpuSpMM_f64):
+// begin_product allocates its rowPtr, finish_exact or one_shot_back its colInd/values, and success ends in give() into the
+// caller's Result<V>.  The functions in between fill it and return a status; on an error the frame drains the stream (rule A)
+// and the blocks go back with the object.
+//
+// The end of every route that has nnz(C) on the host: allocate colInd/values exactly and run the numeric phase.
 template <class V>
-static int two_phase(spgemm_handle* h, const Product<V>& p, const PreClass* pre, int* dIC, const Result<V>& out) {
+static int finish_exact(spgemm_handle* h, const Product<V>& p, int nnzC, DevCSRT<V>* C) {
+  if (C->alloc_entries(nnzC) != hipSuccess) return fail(SPGEMM_ERR_HIP, "device allocation of C (%d entries) failed", nnzC);
+  C->nnz = nnzC;
+  return numeric_phase(h, p.IA, p.JA, p.A, p.IB, p.JB, p.B, p.m, p.n, C->I, C->J, C->V.p);
+}
+
+// the two-phase pipeline from its start: symbolic phase, exact allocation, numeric phase
+template <class V>
+static int two_phase(spgemm_handle* h, const Product<V>& p, const PreClass* pre, DevCSRT<V>* C) {
   int nnzC = 0;
   // (a double product's numeric kernels have no use for the big rows' re-hit log)
-  if (int rc = symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, pre, dIC, &nnzC, std::is_same<V, float>::value)) { pool().release(dIC); return rc; }
-  return finish_exact(h, p, nnzC, dIC, out);
+  CHK(symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, pre, C->I, &nnzC, std::is_same<V, float>::value));
+  return finish_exact(h, p, nnzC, C);
 }
 
 // what the C-producing entry points do first: outputs cleared, arguments checked, handle, device, workspace, C.rowPtr
 template <class V>
-static int begin_product(spgemm_handle** hp, const Product<V>& p, int nnzB, const Result<V>& out, int** dIC) {
+static int begin_product(spgemm_handle** hp, const Product<V>& p, int nnzB, const Result<V>& out, DevCSRT<V>* C) {
   if (!out.IC || !out.JC || !out.C || !out.nnz) return fail(SPGEMM_ERR_ARG, "output pointer is null");
   *out.IC = nullptr; *out.JC = nullptr; *out.C = nullptr; *out.nnz = 0;
   if (p.m < 0 || p.k < 0 || p.n < 0) return fail(SPGEMM_ERR_ARG, "negative dimension m=%d k=%d n=%d", p.m, p.k, p.n);
@@ -1432,7 +1418,7 @@ static int begin_product(spgemm_handle** hp, const Product<V>& p, int nnzB, cons
   if (!*hp) CHK(default_handle(hp));
   HIPCHK(hipSetDevice((*hp)->device));
   CHK(ws_ensure(*hp, p.m));
-  HIPCHK(pool().alloc((void**)dIC, sizeof(int) * ((size_t)p.m + 1)));
+  HIPCHK(C->I.alloc((size_t)p.m + 1));
   return SPGEMM_OK;
 }
 
@@ -1476,41 +1462,35 @@ static int one_shot_front(spgemm_handle* h, const Product<float>& p, const OptIn
 // Back half: colInd/values are allocated with capC entries -- P, an upper bound of nnz(C) (8*P bytes: HBM is 288 GB), or on
 // the one-pass path what the previous, identical-looking call produced (the kernels never write past that and say so if it
 // was not enough) -- so that the numeric kernels can be queued right behind the scan; nnz(C) and the error flags are read
-// once, at the end.  Owns dIC.
-static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInPath& o, const HostMirror& mid, size_t capC,
-                         int* dIC, const Result<float>& out) {
+// once, at the end.
+static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInPath& o, const HostMirror& mid, size_t capC, DevCSR* C) {
   const unsigned long long P = mid.totalP;
   hipStream_t s = h->stream;
-  int* dJC = nullptr;
-  float* dC = nullptr;
-  auto cleanup = [&](int rc) { pool().release(dIC); pool().release(dJC); pool().release(dC); return rc; };
-  if (hipSuccess != pool().alloc((void**)&dJC, sizeof(int) * capC) || hipSuccess != pool().alloc((void**)&dC, sizeof(float) * capC))
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation of C (%llu entries) failed", P));
+  if (C->J.alloc(capC) != hipSuccess || C->V.alloc(capC) != hipSuccess)
+    return fail(SPGEMM_ERR_HIP, "device allocation of C (%llu entries) failed", P);
   hipEventRecord(h->ev[4], s);
   h->mirror = mid;                                     // bin sizes for the numeric launch grids
-  int rc = SPGEMM_OK;
-  if (o.chain) rc = launch_wbatch<WB_CHAIN>(h, p.m, p.IA, p.A, p.JB, p.B, dIC, dJC, dC, (long long)capC);
-  if (!rc && o.wb2 && P > 0) rc = launch_wbatch<WB_NUM>(h, p.m, p.IA, p.A, p.JB, p.B, dIC, dJC, dC, (long long)capC);
-  if (!rc && P > 0) rc = launch_numeric(h, p.IA, p.A, p.JB, p.B, p.n, h->cur_rowIds, mid.binPtr, dIC, dJC, dC, nullptr, 1, o.minBin, o.skipH1A);
-  if (rc) return cleanup(rc);
+  if (o.chain) CHK(launch_wbatch<WB_CHAIN>(h, p.m, p.IA, p.A, p.JB, p.B, C->I, C->J, C->V, (long long)capC));
+  if (o.wb2 && P > 0) CHK(launch_wbatch<WB_NUM>(h, p.m, p.IA, p.A, p.JB, p.B, C->I, C->J, C->V, (long long)capC));
+  if (P > 0) CHK(launch_numeric(h, p.IA, p.A, p.JB, p.B, p.n, h->cur_rowIds, mid.binPtr, C->I, C->J, C->V, nullptr, 1, o.minBin, o.skipH1A));
   hipEventRecord(h->ev[5], s);
-  rc = read_mirror(h, "SpGEMM", kAblate ? ~0 : o.chain ? ERRF_CHAIN_CAP : 0);
+  const int rc = read_mirror(h, "SpGEMM", kAblate ? ~0 : o.chain ? ERRF_CHAIN_CAP : 0);
   if (rc != SPGEMM_ERR_HIP) h->sym_m = -1;             // the mirror of a pending symbolic phase is gone
-  if (rc) return cleanup(rc);
+  if (rc) return rc;
   const HostMirror& hm = h->mirror;
   if (o.chain && (hm.err & ERRF_CHAIN_CAP)) {          // (this condition misses overflows in rows above smallMax: ADVICE.md)
     // C sized from the previous call was too small for this product (same shape and product count, more distinct
     // columns): nothing was written out of bounds; forget the guess and compute the product the two-phase way
-    pool().release(dJC); pool().release(dC);
+    C->J.reset(); C->V.reset();
     h->prev_m = -1; h->prev_nnzC = -1;
-    return two_phase(h, p, nullptr, dIC, out);
+    return two_phase(h, p, nullptr, C);
   }
   publish_stats(h, hm, StatsForm::OneShot);
   grow_bitmaps(h, p.n);
   grow_rehit_log(h, p.n);
   grow_midrow_log(h);
   h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = (long long)hm.nnzC64;
-  *out.IC = dIC; *out.JC = dJC; *out.C = dC; *out.nnz = (int)hm.nnzC64;
+  C->nnz = (int)hm.nnzC64;
   return SPGEMM_OK;
 }
 
@@ -1521,14 +1501,11 @@ static int one_shot_back(spgemm_handle* h, const Product<float>& p, const OptInP
 //   4 P too large         P > 2^30, or a product known to compress: the queued symbolic phase is finished, C sized exactly
 //   5 pre-classified      a caller's classification, or no rows: two-phase pipeline
 // prev_m/prev_P/prev_nnzC (allocation policy of the next call): set by routes 1, 3 and 4, reset by 2, left alone by 5.
-static int spgemm_device(spgemm_handle* h, const Product<float>& p, int nnzB, const PreClass* pre, const Result<float>& out) {
-  int* dIC = nullptr;
-  CHK(begin_product(&h, p, nnzB, out, &dIC));
-  if (pre || p.m == 0) return two_phase(h, p, pre, dIC, out);                                  // route 5
+static int product_routes(spgemm_handle* h, const Product<float>& p, const PreClass* pre, DevCSR* C) {
+  if (pre || p.m == 0) return two_phase(h, p, pre, C);                                         // route 5
   const OptInPath o = opt_in_path(h);
   HostMirror mid;
-  int rc = one_shot_front(h, p, o, dIC, &mid);
-  if (rc) { pool().release(dIC); return rc; }
+  CHK(one_shot_front(h, p, o, C->I, &mid));
   const unsigned long long P = mid.totalP;
   // A product that compresses (real web graphs: nnz(C)/P ~ 0.5) would hold twice the memory it needs when sized by P.
   // The handle remembers the previous call: the same shape and product count with nnz(C) < 3/4 P sends this call down
@@ -1536,14 +1513,21 @@ static int spgemm_device(spgemm_handle* h, const Product<float>& p, int nnzB, co
   const bool compressive = h->prev_m == p.m && h->prev_P == P && h->prev_nnzC >= 0 && (double)h->prev_nnzC < 0.75 * (double)P;
   if (P <= (1ull << 30) && (!compressive || o.chain)) {
     const size_t capC = compressive ? (size_t)std::max<long long>(h->prev_nnzC, 1ll) : (size_t)std::max<unsigned long long>(P, 1ull);
-    return one_shot_back(h, p, o, mid, capC, dIC, out);                                          // routes 1 and 2
+    return one_shot_back(h, p, o, mid, capC, C);                                                // routes 1 and 2
   }
   int nnzC = 0;
-  rc = o.chain ? symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, nullptr, dIC, &nnzC)   // route 3
-               : finish_symbolic(h, p.m, &nnzC);                                                      // route 4
-  if (rc) { pool().release(dIC); return rc; }
+  CHK(o.chain ? symbolic_phase(h, p.IA, p.JA, p.nnzA, p.IB, p.JB, p.m, p.k, p.n, nullptr, C->I, &nnzC)   // route 3
+              : finish_symbolic(h, p.m, &nnzC));                                                      // route 4
   h->prev_m = p.m; h->prev_P = P; h->prev_nnzC = nnzC;
-  return finish_exact(h, p, nnzC, dIC, out);
+  return finish_exact(h, p, nnzC, C);
+}
+
+static int spgemm_device(spgemm_handle* h, const Product<float>& p, int nnzB, const PreClass* pre, const Result<float>& out) {
+  DevCSR C;
+  CHK(begin_product(&h, p, nnzB, out, &C));
+  if (int rc = product_routes(h, p, pre, &C)) return drained(h->stream, rc);
+  C.give(out.IC, out.JC, out.C, out.nnz);
+  return SPGEMM_OK;
 }
 
 extern "C" int hip_gpuSpMM(spgemm_handle* h, const int* dIA, const int* dJA, const float* dA, int nnzA,
@@ -1582,9 +1566,11 @@ extern "C" int hip_gpuSpMM_f64(spgemm_handle* h, const int* dIA, const int* dJA,
                                int** dICp, int** dJCp, double** dCp, int* nnzCp) {
   const Product<double> p{dIA, dJA, dA, nnzA, dIB, dJB, dB, m, k, n};
   const Result<double> out{dICp, dJCp, dCp, nnzCp};
-  int* dIC = nullptr;
-  CHK(begin_product(&h, p, nnzB, out, &dIC));
-  return two_phase(h, p, nullptr, dIC, out);
+  DevCSRT<double> C;
+  CHK(begin_product(&h, p, nnzB, out, &C));
+  if (int rc = two_phase(h, p, nullptr, &C)) return drained(h->stream, rc);
+  C.give(out.IC, out.JC, out.C, out.nnz);
+  return SPGEMM_OK;
 }
 
 extern "C" int hip_spgemm_numeric_f64(spgemm_handle* h, const int* dIA, const int* dJA, const double* dA, int nnzA,
@@ -1606,16 +1592,13 @@ extern "C" int hip_csr_row_flops(spgemm_handle* h, const int* dIA, const int* dJ
   HIPCHK(hipSetDevice(h->device));
   h->sym_m = -1;                                   // the classification workspace is about to be overwritten
   CHK(ws_ensure(h, m));
-  int* tmpIC = nullptr;
-  HIPCHK(pool().alloc((void**)&tmpIC, sizeof(int) * ((size_t)m + 1)));
-  int rc = launch_classify(h, dIA, dJA, dIB, m, -1, tmpIC);
-  if (rc == SPGEMM_OK && m > 0 &&
-      hipMemcpyAsync(dRowFlops, h->rowFlops, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, h->stream) != hipSuccess)
-    rc = fail(SPGEMM_ERR_HIP, "copy of row flops failed");
-  if (rc == SPGEMM_OK && !fetch_mirror(h))
-    rc = fail(SPGEMM_ERR_HIP, "row flops failed: %s", hipGetErrorString(hipGetLastError()));
-  pool().release(tmpIC);
-  if (rc) return rc;
+  hipStream_t s = h->stream;
+  DevBuf<int> tmpIC;
+  HIPCHK(tmpIC.alloc((size_t)m + 1));
+  if (int rc = launch_classify(h, dIA, dJA, dIB, m, -1, tmpIC)) return drained(s, rc);
+  if (m > 0 && hipMemcpyAsync(dRowFlops, h->rowFlops, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    return drained(s, fail(SPGEMM_ERR_HIP, "copy of row flops failed"));
+  if (!fetch_mirror(h)) return drained(s, fail(SPGEMM_ERR_HIP, "row flops failed: %s", hipGetErrorString(hipGetLastError())));
   collect_kernel_times(h, true);
   if (total_flops) *total_flops = (long long)h->hsmall->totalP;
   return SPGEMM_OK;
@@ -1653,29 +1636,25 @@ extern "C" int hip_gpuFlopsClassify(spgemm_handle* h, const int* dIA, const int*
   HIPCHK(hipSetDevice(h->device));
   h->sym_m = -1;
   CHK(ws_ensure(h, m));
-  int *ids = nullptr, *fl = nullptr, *tmpIC = nullptr;
-  auto cleanup = [&](int rc) { pool().release(ids); pool().release(fl); pool().release(tmpIC); return rc; };
-  HIPCHK(pool().alloc((void**)&ids, sizeof(int) * (size_t)std::max(m, 1)));
-  if (hipSuccess != pool().alloc((void**)&fl, sizeof(int) * ((size_t)m + 1)) ||
-      hipSuccess != pool().alloc((void**)&tmpIC, sizeof(int) * ((size_t)m + 1)))
-    return cleanup(fail(SPGEMM_ERR_HIP, "device allocation failed"));
-  int rc = launch_classify(h, dIA, dJA, dIB, m, -1, tmpIC);
-  if (rc) return cleanup(rc);
+  DevBuf<int> ids, fl, tmpIC;
+  HIPCHK(ids.alloc((size_t)std::max(m, 1)));
+  if (fl.alloc((size_t)m + 1) != hipSuccess || tmpIC.alloc((size_t)m + 1) != hipSuccess)
+    return fail(SPGEMM_ERR_HIP, "device allocation failed");
   hipStream_t s = h->stream;
+  if (int rc = launch_classify(h, dIA, dJA, dIB, m, -1, tmpIC)) return drained(s, rc);
   if (m > 0) {
     hipMemcpyAsync(ids, h->rowIds, sizeof(int) * (size_t)m, hipMemcpyDeviceToDevice, s);
-    hipLaunchKernelGGL(k_gather_flops, dim3(cdiv(m, 256)), dim3(256), 0, s, m, h->rowIds, h->rowFlops, fl);
-    if ((rc = launch_scan(h, fl, m, &h->dsmall->nnzC64, false))) return cleanup(rc);   // wraps: differences stay exact
+    hipLaunchKernelGGL(k_gather_flops, dim3(cdiv(m, 256)), dim3(256), 0, s, m, h->rowIds, h->rowFlops, fl.p);
+    if (int rc = launch_scan(h, fl, m, &h->dsmall->nnzC64, false)) return drained(s, rc);   // wraps: differences stay exact
   } else {
     hipMemsetAsync(fl, 0, sizeof(int), s);
   }
-  if (!fetch_mirror(h)) return cleanup(fail(SPGEMM_ERR_HIP, "classify failed: %s", hipGetErrorString(hipGetLastError())));
+  if (!fetch_mirror(h)) return drained(s, fail(SPGEMM_ERR_HIP, "classify failed: %s", hipGetErrorString(hipGetLastError())));
   hv_from_binptr(h->hsmall->binPtr, hv, hv_len);
   if (total_flops) *total_flops = (long long)h->hsmall->totalP;
   publish_stats(h, *h->hsmall, StatsForm::Classified);
-  pool().release(tmpIC);
-  *drowIds = ids;
-  *dflops = fl;
+  *drowIds = ids.release();                            // the caller's now (spgemm_hip_free); tmpIC goes back here
+  *dflops = fl.release();
   return SPGEMM_OK;
 }
 
@@ -1765,7 +1744,7 @@ namespace {
 struct CopyLanes {
   static constexpr int T = 8;
   static constexpr size_t SLOT = size_t(4) << 20;
-  char* slot[T][2] = {};
+  PinBlock<char> slot[T][2];
   hipEvent_t done[T][2] = {};                         // "the copy out of this slot has finished" (host -> device direction)
   hipStream_t st[T] = {};
   int device = -1;
@@ -1776,7 +1755,7 @@ struct CopyLanes {
     for (int t = 0; t < T; ++t) {
       HIPCHK(hipStreamCreateWithFlags(&st[t], hipStreamNonBlocking));
       for (int b = 0; b < 2; ++b) {
-        HIPCHK(hipHostMalloc((void**)&slot[t][b], SLOT, hipHostMallocDefault));
+        HIPCHK(slot[t][b].reserve(SLOT));
         HIPCHK(hipEventCreateWithFlags(&done[t][b], hipEventDisableTiming));
       }
     }
@@ -1786,9 +1765,9 @@ struct CopyLanes {
   void release() {
     for (int t = 0; t < T; ++t) {
       for (int b = 0; b < 2; ++b) {
-        if (slot[t][b]) hipHostFree(slot[t][b]);
+        slot[t][b].reserve(0);
         if (done[t][b]) hipEventDestroy(done[t][b]);
-        slot[t][b] = nullptr; done[t][b] = nullptr;
+        done[t][b] = nullptr;
       }
       if (st[t]) hipStreamDestroy(st[t]);
       st[t] = nullptr;
@@ -1882,15 +1861,23 @@ static int copy_pageable(int dev, const CopyJob* jobs, int njobs, bool toDevice)
         const size_t b = jobs[i].bytes;
         const size_t per = ((b + CopyLanes::T - 1) / CopyLanes::T + 4095) & ~size_t(4095);
         const size_t lo = std::min(b, per * (size_t)t), hi = std::min(b, lo + per);
-        if (hi > lo) errs[t] = lane_copy(dev, L.st[t], L.slot[t], L.done[t], (char*)jobs[i].host + lo, (char*)jobs[i].dev + lo, hi - lo, toDevice);
+        char* const slots[2] = {L.slot[t][0], L.slot[t][1]};
+        if (hi > lo) errs[t] = lane_copy(dev, L.st[t], slots, L.done[t], (char*)jobs[i].host + lo, (char*)jobs[i].dev + lo, hi - lo, toDevice);
       }
     });
   }
   for (auto& x : th) x.join();
   for (int t = 0; t < CopyLanes::T; ++t)
-    if (errs[t] != hipSuccess) return fail(SPGEMM_ERR_HIP, "pipelined %s copy failed: %s", toDevice ? "h2d" : "d2h", hipGetErrorString(errs[t]));
+    if (errs[t] != hipSuccess) {
+      for (hipStream_t st : L.st) (void)hipStreamSynchronize(st);   // rule A: the callers' blocks go back behind idle lanes
+      return fail(SPGEMM_ERR_HIP, "pipelined %s copy failed: %s", toDevice ? "h2d" : "d2h", hipGetErrorString(errs[t]));
+    }
   return SPGEMM_OK;
 }
+
+// a malloc()ed host array on its way to a caller who free()s it
+struct FreeHost { void operator()(void* p) const { free(p); } };
+template <class T> using HostArray = std::unique_ptr<T, FreeHost>;
 
 // the device product hip_CSR_SpMM{,_f64} runs between the copies
 template <class V>
@@ -1910,57 +1897,46 @@ static int csr_spmm_host(DeviceSpMM<V> device_spmm, const int* IA, const int* JA
   spgemm_handle* h = nullptr;
   CHK(default_handle(&h));
   HIPCHK(hipSetDevice(h->device));
-  int *dIA = nullptr, *dJA = nullptr, *dIB = nullptr, *dJB = nullptr, *dIC = nullptr, *dJC = nullptr;
-  V *dA = nullptr, *dB = nullptr, *dC = nullptr;
-  int *hIC = nullptr, *hJC = nullptr;
-  V* hC = nullptr;
-  auto cleanup = [&](int rc) {
-    for (void* p : {(void*)dIA, (void*)dJA, (void*)dA, (void*)dIB, (void*)dJB, (void*)dB, (void*)dIC, (void*)dJC, (void*)dC})
-      pool().release(p);
-    if (rc != SPGEMM_OK) { free(hIC); free(hJC); free(hC); }
-    return rc;
-  };
+  DevCSRT<V> dA, dB, dC;                               // the operands' copies and the product: all of them go back on return
   const bool same = (IA == IB && JA == JB && A == B && nnzA == nnzB && m == k);  // C = A*A: upload once
   const auto t0 = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-  int rc;
   std::vector<CopyJob> up;
-#define UP(dst, src, bytes)                                                                        \
-  if ((rc = spgemm_hip_malloc((void**)&dst, (bytes)))) return cleanup(rc);                          \
-  up.push_back(CopyJob{(void*)(src), (void*)dst, (size_t)(bytes)});
-  UP(dIA, IA, sizeof(int) * ((size_t)m + 1));
-  UP(dJA, JA, sizeof(int) * (size_t)nnzA);
-  UP(dA, A, sizeof(V) * (size_t)nnzA);
+  auto stage = [&up](auto& buf, const auto* src, size_t n) {        // a block for n elements and its place in the one copy
+    CHK(spgemm_hip_malloc((void**)&buf.p, sizeof(*src) * n));
+    up.push_back(CopyJob{(void*)src, (void*)buf.p, sizeof(*src) * n});
+    return SPGEMM_OK;
+  };
+  CHK(stage(dA.I, IA, (size_t)m + 1));
+  CHK(stage(dA.J, JA, (size_t)nnzA));
+  CHK(stage(dA.V, A, (size_t)nnzA));
   if (!same) {
-    UP(dIB, IB, sizeof(int) * ((size_t)k + 1));
-    UP(dJB, JB, sizeof(int) * (size_t)nnzB);
-    UP(dB, B, sizeof(V) * (size_t)nnzB);
+    CHK(stage(dB.I, IB, (size_t)k + 1));
+    CHK(stage(dB.J, JB, (size_t)nnzB));
+    CHK(stage(dB.V, B, (size_t)nnzB));
   }
-#undef UP
-  if ((rc = copy_pageable(h->device, up.data(), (int)up.size(), true))) return cleanup(rc);
+  const DevCSRT<V>& dBx = same ? dA : dB;
+  CHK(copy_pageable(h->device, up.data(), (int)up.size(), true));
   h->host_api.ms_h2d = ms_since(t0);
   const auto t1 = std::chrono::steady_clock::now();
   int nz = 0;
-  rc = device_spmm(h, dIA, dJA, dA, nnzA, same ? dIA : dIB, same ? dJA : dJB, same ? dA : dB, nnzB, m, k, n, &dIC,
-                   &dJC, &dC, &nz);
-  if (rc) return cleanup(rc);
+  CHK(device_spmm(h, dA.I, dA.J, dA.V, nnzA, dBx.I, dBx.J, dBx.V, nnzB, m, k, n, &dC.I.p, &dC.J.p, &dC.V.p, &nz));
   h->host_api.ms_device = ms_since(t1);
   const auto t2 = std::chrono::steady_clock::now();
   // outputs must be malloc()ed: the caller's CSR::dispose() is free() (nlibs/CSR.h:323-327)
-  hIC = (int*)malloc(sizeof(int) * ((size_t)m + 1));
-  hJC = (int*)malloc(sizeof(int) * (size_t)std::max(nz, 1));
-  hC = (V*)malloc(sizeof(V) * (size_t)std::max(nz, 1));
-  if (!hIC || !hJC || !hC) return cleanup(fail(SPGEMM_ERR_NOMEM, "host malloc of C failed"));
-  const CopyJob down[3] = {{hIC, dIC, sizeof(int) * ((size_t)m + 1)}, {hJC, dJC, sizeof(int) * (size_t)nz},
-                           {hC, dC, sizeof(V) * (size_t)nz}};
-  if ((rc = copy_pageable(h->device, down, 3, false))) return cleanup(rc);
+  HostArray<int> hIC((int*)malloc(sizeof(int) * ((size_t)m + 1))), hJC((int*)malloc(sizeof(int) * (size_t)std::max(nz, 1)));
+  HostArray<V> hC((V*)malloc(sizeof(V) * (size_t)std::max(nz, 1)));
+  if (!hIC || !hJC || !hC) return fail(SPGEMM_ERR_NOMEM, "host malloc of C failed");
+  const CopyJob down[3] = {{hIC.get(), dC.I, sizeof(int) * ((size_t)m + 1)}, {hJC.get(), dC.J, sizeof(int) * (size_t)nz},
+                           {hC.get(), dC.V, sizeof(V) * (size_t)nz}};
+  CHK(copy_pageable(h->device, down, 3, false));
   h->host_api.ms_d2h = ms_since(t2);
   h->host_api.ms_total = ms_since(t0);
   h->host_api.bytes_h2d = 0;
   for (auto& j : up) h->host_api.bytes_h2d += (long long)j.bytes;
   h->host_api.bytes_d2h = (long long)(down[0].bytes + down[1].bytes + down[2].bytes);
-  *IC = hIC; *JC = hJC; *C = hC; *nnzC = nz;
-  return cleanup(SPGEMM_OK);
+  *IC = hIC.release(); *JC = hJC.release(); *C = hC.release(); *nnzC = nz;
+  return SPGEMM_OK;
 }
 
 extern "C" int hip_CSR_SpMM(const int* IA, const int* JA, const float* A, int nnzA, const int* IB, const int* JB,
@@ -2191,7 +2167,7 @@ static int rmcl_size_rows_by_products(spgemm_handle* h, const CsrView& A, const 
     h->bdLogged = false;
     h->mdLogged = false;
     hipLaunchKernelGGL(k_sym_big<false>, dim3(clampi(nbig, 1, h->numCU)), dim3(BIG_THREADS), sizeof(BigSymShared), s,
-                       h->dsmall->binPtr, 8, h->cur_rowIds, A.I, h->sbl, B.J, n, dIC, h->bigBitmaps, h->bm_cap,
+                       h->dsmall->binPtr, 8, h->cur_rowIds, A.I, h->sbl, B.J, n, dIC, h->bigBitmaps, h->bm_cap(),
                        h->dsmall->qctr + 0 * 32, (int2*)nullptr, 0, (int*)nullptr, 0, 0, (int*)nullptr, (int*)nullptr);
     if (hipGetLastError() != hipSuccess) return rmcl_hipfail("symbolic launch");
   }
@@ -2485,15 +2461,15 @@ static int rmcl_expand_prune64_core(spgemm_handle* h, const Product<double>& p, 
   }
   if (hipMemsetAsync(C.len, 0, sizeof(int) * ((size_t)m + 1), s) != hipSuccess) return drained(s, rmcl_hipfail("memset"));
   if (C.alloc_entries(nnzC)) return drained(s, rmcl_hipfail("device allocation of the scratch product failed"));
-  int* scratch[2] = {nullptr, nullptr};                // the numeric launch's probe words and device-memory tables
-  auto done = [&](int r) { r = drained(s, r); pool().release(scratch[0]); pool().release(scratch[1]); return r; };
-  hipEventRecord(h->ev[4], s);
-  if (nnzC > 0 && (rc = launch_numeric_f64(h, p.IA, p.A, p.JB, p.B, h->cur_rowIds, h->mirror.binPtr, C.I, C.J, C.V, scratch, C.len)))
-    return done(rc);
-  hipEventRecord(h->ev[5], s);
-  if ((rc = launch_scan(h, C.len, m, &h->dsmall->kept64))) return done(rc);
-  if ((rc = read_mirror(h, "rmcl expand+prune (f64)"))) return done(rc);
-  done(SPGEMM_OK);                                     // (read_mirror waited for the stream)
+  {
+    F64Scratch scratch;
+    hipEventRecord(h->ev[4], s);
+    if (nnzC > 0 && (rc = launch_numeric_f64(h, p.IA, p.A, p.JB, p.B, h->cur_rowIds, h->mirror.binPtr, C.I, C.J, C.V, &scratch, C.len)))
+      return drained(s, rc);
+    hipEventRecord(h->ev[5], s);
+    if ((rc = launch_scan(h, C.len, m, &h->dsmall->kept64))) return drained(s, rc);
+    if ((rc = read_mirror(h, "rmcl expand+prune (f64)"))) return drained(s, rc);
+  }                                                    // (read_mirror waited for the stream: the scratch goes back)
   spgemm_stats& st = h->stats;
   hipEventElapsedTime(&st.ms_numeric, h->ev[4], h->ev[5]);
   st.ms_total += st.ms_numeric;
@@ -2593,20 +2569,17 @@ extern "C" int spgemm_hip_selftest(spgemm_handle* h) {
   std::vector<int> host(nb * WAVE);
   unsigned x = 12345u;
   for (auto& v : host) { x = x * 1664525u + 1013904223u; v = (int)((x >> 8) & 0xfffff); }
-  int* din = nullptr;
-  int* dbad = nullptr;
-  HIPCHK(hipMalloc((void**)&din, sizeof(int) * host.size()));
-  HIPCHK(hipMalloc((void**)&dbad, sizeof(int)));
+  DevBlock<int> din, dbad;
+  HIPCHK(din.reserve(host.size()));
+  HIPCHK(dbad.reserve(1));
   HIPCHK(hipMemcpy(din, host.data(), sizeof(int) * host.size(), hipMemcpyHostToDevice));
   HIPCHK(hipMemset(dbad, 0, sizeof(int)));
   clear_stale_hip_error();
-  hipLaunchKernelGGL(k_selftest, dim3(nb), dim3(WAVE), 0, h->stream, din, dbad);
+  hipLaunchKernelGGL(k_selftest, dim3(nb), dim3(WAVE), 0, h->stream, din.p, dbad.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   int bad = -1;
   HIPCHK(hipMemcpy(&bad, dbad, sizeof(int), hipMemcpyDeviceToHost));
-  hipFree(din);
-  hipFree(dbad);
   if (bad != 0) return fail(SPGEMM_ERR_INTERNAL, "wave primitive self-test: %d lanes disagree", bad);
   return SPGEMM_OK;
 }

@@ -40,6 +40,29 @@ def handle():
     h.close()
 
 
+@pytest.fixture(scope="module", autouse=True)
+def _seasoned_pool(built_gpu):
+    """For the modules that compare the pool's cached bytes (test_gpu_rmcl_pool.py, test_gpu_spgemm_pool.py).  The figure
+    compared is the pool's cached bytes, so no call may fetch a block from the driver: such a block is
+    cached when it is released, and the figure grows although nothing leaked -- in whichever call first finds no fitting
+    block, which depends on what earlier tests left in the pool (the best fit of a call's requests moves once its own
+    blocks are in the cache).  A ladder of blocks from 1 KiB to 8 MiB, 12 per octave, is cached up front: every request
+    of these calls (the largest is the 2.7 MB scratch product of iteration 2) finds a block, whatever ran before, and a
+    block that is not released always shows, because its replacement comes out of the cache."""
+    for p in [hs.dev_alloc(int(n)) for n in np.geomspace(1 << 10, 1 << 23, 160)]:
+        hs.dev_free(p)
+
+
+def twice(call, device=0):
+    """warm, record, run again: the cached bytes must not have moved; -> what the second run returned"""
+    call()
+    before = hs.pool_cached_bytes(device)
+    out = call()
+    after = hs.pool_cached_bytes(device)
+    assert after == before, f"cached bytes moved by {after - before}"
+    return out
+
+
 # ---- inputs (made once by their callers, never modified) -------------------------------------------------------------
 def with_nnz(rows, cols, nnz, seed):
     """exactly nnz entries over `rows` rows, random columns (repeats allowed), some rows empty"""
@@ -88,6 +111,14 @@ def _graph(m, seed):
     return po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))
 
 
+def start_graph(base):
+    """a 2000-node power-law graph as R-MCL starts from it (transpose + self loops + row-normalise); host and device"""
+    A = synth_csr(2000, 7, base)
+    ri = np.repeat(np.arange(A.rows, dtype=np.int32), np.diff(A.rowPtr))
+    M0 = po.rmcl_init(A.rows, A.cols, A.colInd, ri, np.ones_like(A.values))
+    return M0, hs.CSR.from_arrays(M0.rowPtr, M0.colInd, M0.values, M0.rows, M0.cols).toGpuCSR()
+
+
 def unpack(z, prefix):
     r, c = z[prefix + "_shape"]
     return po.CSRHost(z[prefix + "_rowPtr"], z[prefix + "_colInd"], z[prefix + "_values"], int(r), int(c))
@@ -114,6 +145,14 @@ def take(dev):
     host = dev.toCpuCSR()
     dev.deviceDispose()
     return host
+
+
+def taken(i, j, v, n, rows, dtype=np.float32):
+    """host copy of a raw device result, which is freed"""
+    out = (hs.d2h(i, rows + 1, np.int32), hs.d2h(j, n, np.int32), hs.d2h(v, n, dtype))
+    for p in (i, j, v):
+        hs.dev_free(p)
+    return out
 
 
 def assert_bits(got, want, what=""):
