@@ -2305,7 +2305,9 @@ __global__ __launch_bounds__(BIG_THREADS) void k_sym_big(const int* __restrict__
     const bool logging = LOG && q < rlRows;            // block-uniform
     const int room = logging ? min(rlCap, rlRegion - cursor) : 0;
     int logged = 0, logOvf = 0;
-    for (int w0 = 0; w0 < n; w0 += SYM_WC) {
+    // by window index: w0 += SYM_WC would overflow past the last window of an n > 2^31 - SYM_WC (w0 <= 2047 * SYM_WC here)
+    for (int wi = 0, nwin = (int)(((unsigned)n + (unsigned)(SYM_WC - 1)) / (unsigned)SYM_WC); wi < nwin; ++wi) {
+      const int w0 = wi * SYM_WC;
       const int wc = min(SYM_WC, n - w0);
       const int words = (wc + 31) >> 5;
       const int words4 = (words + 3) & ~3;             // the bitmap is cleared and counted four words at a time

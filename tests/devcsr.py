@@ -7,13 +7,14 @@ fixtures and helpers that two or more test modules used to spell out themselves.
 
 pytest does not rewrite the asserts of a helper module: every assert here carries its message."""
 import ctypes as C
+import os
 import socket
 
 import numpy as np
 import pytest
 
 import reorder_ref as rr
-from helpers import po, synth_csr
+from helpers import canonical_arrays, po, synth_csr
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 
@@ -161,6 +162,92 @@ def assert_bits(got, want, what=""):
     assert np.array_equal(np.asarray(got.colInd), np.asarray(want.colInd)), f"{what}: colInd"
     g, w = np.ascontiguousarray(got.values), np.ascontiguousarray(want.values)
     assert g.dtype == w.dtype and g.tobytes() == w.tobytes(), f"{what}: value bits"
+
+
+# ---- products on a fresh handle, compared bit for bit (the big-row, mid-row and wide-column modules) ------------------
+def env_handle(**env):
+    """a fresh handle; the SPGEMM_* knobs are read when it is created"""
+    for k, v in env.items():
+        os.environ[k] = str(v)
+    try:
+        return hs.Handle(0)
+    finally:
+        for k in env:
+            del os.environ[k]
+
+
+def int_csr(rows, ncols, seed, lo=1, hi=4):
+    """rows: column arrays; values: small integers (any summation order is exact)"""
+    rng = np.random.default_rng(seed)
+    rp = np.zeros(len(rows) + 1, np.int32)
+    rp[1:] = np.cumsum([len(r) for r in rows])
+    ci = np.concatenate([np.asarray(r, np.int64) for r in rows] + [np.zeros(0, np.int64)]).astype(np.int32)
+    v = rng.integers(lo, hi + 1, size=len(ci)).astype(np.float32)
+    return po.CSRHost(rp, ci, v, len(rows), ncols)
+
+
+def row_flops(A, B):
+    """products of every row of A * B"""
+    blen = np.diff(np.asarray(B.rowPtr, np.int64))
+    per = blen[np.asarray(A.colInd)]
+    rp = np.asarray(A.rowPtr, np.int64)
+    return np.array([per[rp[i]:rp[i + 1]].sum() for i in range(A.rows)])
+
+
+def float_bits(M):
+    c, v = canonical_arrays(M.rowPtr, M.colInd, M.values)
+    return np.asarray(M.rowPtr, np.int32).tobytes(), c.tobytes(), v.view(np.uint32).tobytes()
+
+
+def same_bits(got, want, what, zero_signs=True):
+    """rowPtr, per-row sorted columns and float value bits.  zero_signs=False: +0.0 and -0.0 count as equal (the oracle's
+    accumulators start from +0.0)"""
+    g, w = float_bits(got), float_bits(want)
+    assert g[0] == w[0], f"{what}: rowPtr differs"
+    assert g[1] == w[1], f"{what}: columns differ"
+    if zero_signs:
+        assert g[2] == w[2], f"{what}: value bits differ"
+    else:
+        assert np.array_equal(canonical_arrays(got.rowPtr, got.colInd, got.values)[1],
+                              canonical_arrays(want.rowPtr, want.colInd, want.values)[1]), f"{what}: values differ"
+
+
+def bigrow_handle(**env):
+    """env_handle with SPGEMM_BD_MINROWS=1 unless the caller says otherwise: a product with fewer big rows than the device has
+    CUs keeps the hash kernel by default, and the cases of these modules are a handful of rows"""
+    env.setdefault("SPGEMM_BD_MINROWS", 1)
+    return env_handle(**env)
+
+
+def bigrow_mul(h, A, B):
+    """-> (A * B on handle h as a host CSR, the big-row routes it took)"""
+    dA, dB = to_hs(A).toGpuCSR(), to_hs(B).toGpuCSR()
+    dC = hs.gpuSpMMWrapper(dA, dB, h)
+    got = dC.toCpuCSR()
+    for d in (dC, dA, dB):
+        d.deviceDispose()
+    return got, h.bigrow_paths()
+
+
+def bigrow_twice(A, B, what, direct, zero_signs=True, want=None, **env):
+    """A fresh handle whose first call has big rows (no log yet: every row takes the hash kernel), then the same call again
+    (`direct` rows take the direct kernel); both equal the reference bit for bit (want; None: the oracle's product).  Returns
+    the second result and its routes."""
+    if want is None:
+        want = po.sequential_spmm(A, B)
+    nbig = int((row_flops(A, B) > 4096).sum())
+    h = bigrow_handle(**env)
+    try:
+        got1, p1 = bigrow_mul(h, A, B)
+        same_bits(got1, want, what + " (first call)", zero_signs)
+        assert (p1["direct"], p1["fallback"]) == (0, nbig), f"{what}: first call {p1}"
+        got2, p2 = bigrow_mul(h, A, B)
+        same_bits(got2, want, what + " (second call)", zero_signs)
+        if direct is not None:
+            assert (p2["direct"], p2["fallback"]) == (direct, nbig - direct), f"{what}: second call {p2}"
+    finally:
+        h.close()
+    return got2, p2
 
 
 # ---- the rest --------------------------------------------------------------------------------------------------------

@@ -6,13 +6,14 @@ order is exact), compared with the CPU oracle after a per-row sort: rowPtr, colu
 re-hit log at the end of its first call with big rows, so `twice()` runs every product two times on a fresh handle: the
 first call takes the hash kernel for every row, the second the planned split (Handle.bigrow_paths() says which ran).
 """
-import os
-
 import numpy as np
 import pytest
 
-from devcsr import to_hs
-from helpers import canonical_arrays, po
+from devcsr import bigrow_handle as _handle
+from devcsr import bigrow_twice as twice
+from devcsr import int_csr as _csr
+from devcsr import row_flops as _flops
+from devcsr import same_bits as _same
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 pytestmark = pytest.mark.gpu
@@ -28,85 +29,10 @@ def _built():
     assert hs.device_count() >= 1, "GPU tests need a HIP device (no CPU fallback exists)"
 
 
-def _handle(**env):
-    """a fresh handle; the SPGEMM_* knobs are read when it is created.  SPGEMM_BD_MINROWS=1 unless the caller says otherwise: a
-    product with fewer big rows than the device has CUs keeps the hash kernel by default, and these cases are a handful of rows"""
-    env.setdefault("SPGEMM_BD_MINROWS", 1)
-    for k, v in env.items():
-        os.environ[k] = str(v)
-    try:
-        return hs.Handle(0)
-    finally:
-        for k in env:
-            del os.environ[k]
-
-
-def _csr(rows, ncols, seed, lo=1, hi=4):
-    """rows: column arrays; values: small integers"""
-    rng = np.random.default_rng(seed)
-    rp = np.zeros(len(rows) + 1, np.int32)
-    rp[1:] = np.cumsum([len(r) for r in rows])
-    ci = np.concatenate([np.asarray(r, np.int64) for r in rows] + [np.zeros(0, np.int64)]).astype(np.int32)
-    v = rng.integers(lo, hi + 1, size=len(ci)).astype(np.float32)
-    return po.CSRHost(rp, ci, v, len(rows), ncols)
-
-
 def _disjoint_rows(count, n=N, seed=1):
     """`count` B rows of L columns each, no column in two rows, spread over [0, n)"""
     perm = np.random.default_rng(seed).permutation(n)[:count * L]
     return [np.sort(perm[i * L:(i + 1) * L]) for i in range(count)]
-
-
-def _mul(h, A, B):
-    dA, dB = to_hs(A).toGpuCSR(), to_hs(B).toGpuCSR()
-    dC = hs.gpuSpMMWrapper(dA, dB, h)
-    got = dC.toCpuCSR()
-    for d in (dC, dA, dB):
-        d.deviceDispose()
-    return got, h.bigrow_paths()
-
-
-def _bits(M):
-    c, v = canonical_arrays(M.rowPtr, M.colInd, M.values)
-    return np.asarray(M.rowPtr, np.int32).tobytes(), c.tobytes(), v.view(np.uint32).tobytes()
-
-
-def _same(got, want, what, zero_signs=True):
-    """zero_signs=False: +0.0 and -0.0 count as equal (the oracle's accumulators start from +0.0)"""
-    g, w = _bits(got), _bits(want)
-    assert g[0] == w[0], f"{what}: rowPtr differs"
-    assert g[1] == w[1], f"{what}: columns differ"
-    if zero_signs:
-        assert g[2] == w[2], f"{what}: value bits differ"
-    else:
-        assert np.array_equal(canonical_arrays(got.rowPtr, got.colInd, got.values)[1],
-                              canonical_arrays(want.rowPtr, want.colInd, want.values)[1]), f"{what}: values differ"
-
-
-def twice(A, B, what, direct, zero_signs=True, **env):
-    """Case 7 for every input: a fresh handle whose first call has big rows (no log yet: every row takes the hash kernel), then
-    the same call again (`direct` rows take the direct kernel); both equal the oracle bit for bit.  Returns the second result."""
-    want = po.sequential_spmm(A, B)
-    nbig = int((_flops(A, B) > 4096).sum())
-    h = _handle(**env)
-    try:
-        got1, p1 = _mul(h, A, B)
-        _same(got1, want, what + " (first call)", zero_signs)
-        assert (p1["direct"], p1["fallback"]) == (0, nbig), f"{what}: first call {p1}"
-        got2, p2 = _mul(h, A, B)
-        _same(got2, want, what + " (second call)", zero_signs)
-        if direct is not None:
-            assert (p2["direct"], p2["fallback"]) == (direct, nbig - direct), f"{what}: second call {p2}"
-    finally:
-        h.close()
-    return got2, p2
-
-
-def _flops(A, B):
-    blen = np.diff(np.asarray(B.rowPtr, np.int64))
-    per = blen[np.asarray(A.colInd)]
-    rp = np.asarray(A.rowPtr, np.int64)
-    return np.array([per[rp[i]:rp[i + 1]].sum() for i in range(A.rows)])
 
 
 def _cap(**env):

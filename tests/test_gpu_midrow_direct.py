@@ -8,13 +8,14 @@ the result is compared with the CPU oracle after a per-row sort: rowPtr, columns
 the end of its first call with such rows, so `run()` multiplies twice on a fresh handle: the first call takes the hash
 kernels for every row, the second the planned split (Handle.midrow_paths() says which ran, and how much was logged).
 """
-import os
-
 import numpy as np
 import pytest
 
-from devcsr import to_hs
-from helpers import canonical_arrays, po
+from devcsr import env_handle, to_hs
+from devcsr import int_csr as _csr
+from devcsr import row_flops as _flops
+from devcsr import same_bits as _same
+from helpers import po
 from sparse_matrix_with_flops_amd import hipspgemm as hs
 
 pytestmark = pytest.mark.gpu
@@ -36,13 +37,7 @@ def _handle(**env):
     """a fresh handle; the SPGEMM_* knobs are read when it is created.  SPGEMM_MD_MINROWS=1 unless the caller says otherwise: a
     bin with fewer rows than four per CU keeps the hash kernel by default, and these cases are a handful of rows"""
     env.setdefault("SPGEMM_MD_MINROWS", 1)
-    for k, v in env.items():
-        os.environ[k] = str(v)
-    try:
-        return hs.Handle(0)
-    finally:
-        for k in env:
-            del os.environ[k]
+    return env_handle(**env)
 
 
 def _cap(**env):
@@ -107,22 +102,6 @@ class Bld:
         return A, B, np.asarray(self.rehits + [0] * pad_rows, np.int64)
 
 
-def _csr(rows, ncols, seed, lo=1, hi=4):
-    rng = np.random.default_rng(seed)
-    rp = np.zeros(len(rows) + 1, np.int32)
-    rp[1:] = np.cumsum([len(r) for r in rows])
-    ci = np.concatenate([np.asarray(r, np.int64) for r in rows] + [np.zeros(0, np.int64)]).astype(np.int32)
-    v = rng.integers(lo, hi + 1, size=len(ci)).astype(np.float32)
-    return po.CSRHost(rp, ci, v, len(rows), ncols)
-
-
-def _flops(A, B):
-    blen = np.diff(np.asarray(B.rowPtr, np.int64))
-    per = blen[np.asarray(A.colInd)]
-    rp = np.asarray(A.rowPtr, np.int64)
-    return np.array([per[rp[i]:rp[i + 1]].sum() for i in range(A.rows)])
-
-
 def _mul(h, A, B):
     dA, dB = to_hs(A).toGpuCSR(), to_hs(B).toGpuCSR()
     dC = hs.gpuSpMMWrapper(dA, dB, h)
@@ -130,23 +109,6 @@ def _mul(h, A, B):
     for d in (dC, dA, dB):
         d.deviceDispose()
     return got, h.midrow_paths()
-
-
-def _bits(M):
-    c, v = canonical_arrays(M.rowPtr, M.colInd, M.values)
-    return np.asarray(M.rowPtr, np.int32).tobytes(), c.tobytes(), v.view(np.uint32).tobytes()
-
-
-def _same(got, want, what, zero_signs=True):
-    """zero_signs=False: +0.0 and -0.0 count as equal (the oracle's accumulators start from +0.0)"""
-    g, w = _bits(got), _bits(want)
-    assert g[0] == w[0], f"{what}: rowPtr differs"
-    assert g[1] == w[1], f"{what}: columns differ"
-    if zero_signs:
-        assert g[2] == w[2], f"{what}: value bits differ"
-    else:
-        assert np.array_equal(canonical_arrays(got.rowPtr, got.colInd, got.values)[1],
-                              canonical_arrays(want.rowPtr, want.colInd, want.values)[1]), f"{what}: values differ"
 
 
 _ORACLE = {}
